@@ -42,6 +42,24 @@ Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
 torch.distributed.run, one process per GPU.  Rank 0 prints one JSON line.
 Other workloads: --scene sphere (the labelled Sylveon substitute) or
 --scene synthetic:<T> (SURVEY §8d config 5 cloud, camera at z=2.2).
+
+A plain run does only what the headline needs: setup, the stats-mode frame
+that counts the reference's rays, the frames in which the library measures
+its lane schedule, at least --prewarm-ms of the timed frames back to back
+(the GPU's clocks ramp up under load), the warmup, the K timed steps and the
+line (its roofline priced from the committed profile, no run of its own).
+Everything else described above -- the counting pass of the fast kernel, the
+culling-off frames, the one-context drop-in frame, the CPU baseline and the
+oracle check of the timed frame, the bitwise check between the contexts, the
+scene legs (`configs`), and at N > 1 the default --verify and the
+pt_create_multi leg -- runs only with --full.
+
+--dump-outputs DIR writes, after the timed steps, the accumulation buffer
+the last timed step rendered (what pt_read_accum hands a caller) as
+DIR/accum.npy, float32 [H, W, 4]; a frame above 64 MB is written as a fixed
+seeded sample of its pixels, [P, 4].  Scene, camera, light and sample
+batches are fixed by the arguments, so two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -200,12 +218,13 @@ KERNEL_NAMES = {1: "render_kernel<false,*>",
 TRACED_KEYS = ("closest_walks", "shadow_walks", "nodes", "tri_tests", "primaries")
 
 
-def reference_and_traced_counts(r, spp):
+def reference_and_traced_counts(r, spp, count_traced=True):
     """One untimed frame in stats mode (the reference-exhaustive traversal:
     every traceRay with its exhaustive node and leaf counts) and one with the
     fast kernel's counters on (PT_OPT_COUNT_TRACED: the walks, node visits
     and triangle tests it really performs).  Both frames are bit-identical
-    to the timed ones."""
+    to the timed ones.  count_traced=False: the stats-mode frame alone (the
+    rays the headline divides by), None for the traced counts."""
     import ptamd
     r.set_stats_mode(True)
     r.reset_stats()
@@ -213,6 +232,8 @@ def reference_and_traced_counts(r, spp):
     r.render(0, spp)
     st = r.stats()
     r.set_stats_mode(False)
+    if not count_traced:
+        return np.array([st["rays"], st["nodes"], st["leaf_tests"], st["samples"]], np.float64), None
     r.set_option(ptamd.PT_OPT_COUNT_TRACED, 1)
     r.reset_stats()
     r.render(0, spp)
@@ -1270,6 +1291,27 @@ def emit_line(full, detail_path=None):
     return line
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: every file of a run together stays below this
+DUMP_SEED = 20240229               # the pixel sample of a frame above it
+
+
+def dump_outputs(dirpath, accum, W, H):
+    """--dump-outputs: the accumulation buffer of the last timed step (flat
+    W*H*4 floats, as pt_read_accum returns it) as DIR/accum.npy, float32
+    [H, W, 4].  A frame above DUMP_MAX_BYTES is written as [P, 4]: the pixels
+    (row-major indices, ascending) a generator seeded with DUMP_SEED draws
+    without replacement from the W*H -- the same pixels for the same size."""
+    px = np.ascontiguousarray(accum, dtype=np.float32).reshape(H * W, 4)
+    if px.nbytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=DUMP_MAX_BYTES // 16, replace=False))
+        out = px[keep]
+    else:
+        out = px.reshape(H, W, 4)
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "accum.npy"), out)
+    log(f"--dump-outputs: {os.path.join(dirpath, 'accum.npy')} {out.shape} float32")
+
+
 def log(msg):
     """A progress line on stderr, tagged with the rank and the seconds since
     start: a run that stops shows where."""
@@ -1459,6 +1501,16 @@ def main():
     # steps keep the barrier/synchronize bracket a small part of the region
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: the fast kernel's counting pass, the culling-off "
+                         "frames, the one-context frame, the CPU baseline and oracle check, the scene legs "
+                         "(`configs`), and at N > 1 --verify and the pt_create_multi leg by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last step rendered to DIR/accum.npy (float32)")
+    ap.add_argument("--prewarm-ms", type=float, default=40.0,
+                    help="without --full: the timed frames run back to back for at least this long before the "
+                         "warmup, so the timed region starts at the GPU's loaded clocks (with --full the "
+                         "culling-off frames do that)")
     ap.add_argument("--scene", default="box")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -1471,7 +1523,7 @@ def main():
                          "buffers (HIP IPC), falling back to the gather if its self-check fails")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify", type=int, choices=[0, 1], default=None, nargs="?", const=1,
-                    help="N>1: compare the assembled frame with a 1-GPU render (default on at N > 1)")
+                    help="N>1: compare the assembled frame with a 1-GPU render (default on at N > 1 with --full)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VAL",
                     help="pt_set_option before timing (A/B of output-invariant kernel options)")
     ap.add_argument("--assemble", type=int, choices=[0, 1, 2], default=2,
@@ -1489,7 +1541,7 @@ def main():
     ap.add_argument("--packed", action="store_true", help="N=1: run the gather path (render_packed + assembly)")
     ap.add_argument("--compare-no-cull", type=int, choices=[0, 1], default=None,
                     help="also time the same frames with primary-ray culling off, before the warmup (reported "
-                         "as primary_cull_off); default on for the box headline")
+                         "as primary_cull_off); default on for the box headline with --full")
     ap.add_argument("--no-cull-min-ms", type=float, default=40.0,
                     help="the culling-off frames run for at least this long (and at least --steps frames)")
     ap.add_argument("--no-scene-legs", action="store_true",
@@ -1557,7 +1609,7 @@ def main():
     # the root's critical path, never a multi-GPU result (the line says so).
     emu = int(os.environ.get("PT_BENCH_EMULATE_RANKS", "1"))
     if args.verify is None:
-        args.verify = int(world > 1)
+        args.verify = int(world > 1 and args.full)
     if emu > 1 and world != 1:
         raise SystemExit("PT_BENCH_EMULATE_RANKS needs a 1-process run")
     if emu > 1 and (args.collective != "gather" or args.verify):
@@ -1693,10 +1745,11 @@ def main():
         traced = None
     else:
         # Stats pass (untimed): the reference's exact traversal counts for one frame.
-        mine, traced = reference_and_traced_counts(r, SPP)
+        mine, traced = reference_and_traced_counts(r, SPP, count_traced=args.full)
         counts = sum_ranks(mine)
         rays_per_frame = float(counts[0])
-        traced = dict(zip(TRACED_KEYS, (int(x) for x in sum_ranks([traced[k] for k in TRACED_KEYS]))))
+        if traced is not None:
+            traced = dict(zip(TRACED_KEYS, (int(x) for x in sum_ranks([traced[k] for k in TRACED_KEYS]))))
     # output-invariant kernel options apply to the timed frames (the stats
     # pass above always runs the path-recursive kernel)
     for kv in args.opt:
@@ -1955,8 +2008,24 @@ def main():
     # idle, 0.2374 -> 0.2302 -> 0.2216 in back-to-back runs, 0.2198 over 200).
     no_cull = None
     default_cfg = args.scene == "box" and (W, H, SPP, DEPTH, SSS) == (1920, 1080, 8, 4, 3)
+    prewarm = False
     if args.compare_no_cull is None:
-        args.compare_no_cull = int(default_cfg and not args.packed and not args.profile_run)
+        args.compare_no_cull = int(args.full and default_cfg and not args.packed and not args.profile_run)
+        # a plain run keeps the GPU busy here with the timed frames themselves
+        prewarm = (not args.full and default_cfg and not args.packed and not args.profile_run
+                   and args.prewarm_ms > 0)
+    if prewarm:
+        pw = ctxs if (dist is None and emu == 1) else [r]
+        pw_frames = 0
+        t1 = time.perf_counter()
+        for _ in range(64):   # bounded, as the culling-off runs below
+            for _ in range(16):
+                pw[pw_frames % len(pw)].render(0, SPP)
+                pw_frames += 1
+            torch.cuda.synchronize(dev)
+            if (time.perf_counter() - t1) * 1e3 >= args.prewarm_ms:
+                break
+        log(f"pre-warm frames: {pw_frames} in {(time.perf_counter() - t1) * 1e3:.1f} ms")
     if args.compare_no_cull:
         nc = ctxs if (dist is None and emu == 1 and not args.packed) else [r]
         for c in nc:
@@ -2025,7 +2094,7 @@ def main():
     # the last timed frame, checked bit for bit against the oracle's frame
     # (cpu_baseline renders the whole frame) before the line is printed
     timed_frame = None
-    if world == 1 and emu == 1 and not args.packed and args.collective == "gather":
+    if args.full and world == 1 and emu == 1 and not args.packed and args.collective == "gather":
         timed_frame = ctxs[0].read_accum()
     if pipelined:
         # frames overlap across the contexts: the GPU time per frame is the
@@ -2033,10 +2102,30 @@ def main():
         roof_ms = dt / args.steps * 1e3
         for c in ctxs[1:]:
             c.synchronize()
+    if pipelined and args.full:
         want = ctxs[0].read_accum().view(np.uint32)
         for c in ctxs[1:]:
             if not np.array_equal(c.read_accum().view(np.uint32), want):
                 raise SystemExit("bench: the pipelined contexts' frames differ")
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step, from where a caller of the timed
+        # path reads it
+        if dist is None and emu == 1 and not args.packed:
+            last = ctxs[(state1["k"] - 1) % len(ctxs)].read_accum()   # that step's context
+        elif ipc is not None:
+            last = ipc["frames"].read((state_ipc["k"] - 1) % ipc["frames"].nbuf)
+        elif args.collective == "reduce":
+            last = frame.cpu().numpy()
+        elif native is not None or out is not None:
+            # the root's assembled frame: the trailing assembly of the Python
+            # step writes outs[0]; the native loop's buffers each hold one of
+            # the last frames (every step renders the same frame)
+            last = (native["outs"][0] if native is not None else out).cpu().numpy()
+        else:
+            last = None
+            log("--dump-outputs: this rank assembles no frame (an emulated non-root rank)")
+        if last is not None:
+            dump_outputs(args.dump_outputs, last, W, H)
 
     # The drop-in frame: ONE context at the library's
     # defaults -- no bench-only options, its own stream -- frames one after
@@ -2045,7 +2134,8 @@ def main():
     # against the oracle with the timed frame below.
     single = None
     single_frame = None
-    if world == 1 and emu == 1 and not args.packed and args.collective == "gather" and not args.profile_run:
+    if (args.full and world == 1 and emu == 1 and not args.packed and args.collective == "gather"
+            and not args.profile_run):
         try:
             sc = ptamd.Renderer(device)
             sc.upload_scene(v, i, n, int_bits=int_bits)
@@ -2130,7 +2220,7 @@ def main():
     if native is not None and not native.get("emulated"):
         comm_ranks = r.dist_info()[0]   # what RCCL itself reports (ncclCommCount)
     dist_legs = None
-    if dist is not None and default_cfg and not (args.no_scene_legs or args.profile_run):
+    if args.full and dist is not None and default_cfg and not (args.no_scene_legs or args.profile_run):
         # configs 4 and 5 across the same N GPUs (every rank takes part)
         torch.cuda.synchronize(dev)
         dist.barrier()
@@ -2150,7 +2240,7 @@ def main():
     # drives every GPU while the other ranks wait at the barrier
     group = None
     gdevs = args.group_devices
-    if gdevs is None and world > 1 and default_cfg and not args.profile_run:
+    if gdevs is None and args.full and world > 1 and default_cfg and not args.profile_run:
         gdevs = ",".join(str(k) for k in range(world))
     if gdevs is not None and gdevs != "none":
         if dist is not None:
@@ -2238,7 +2328,7 @@ def main():
         if verified is not None:
             out_line["verified_bitwise_vs_single_gpu"] = verified
         oracle_mismatch = verify_error
-        if world == 1 and emu == 1 and not args.no_cpu_baseline and not args.profile_run:
+        if args.full and world == 1 and emu == 1 and not args.no_cpu_baseline and not args.profile_run:
             out_line["cpu_baseline"], oracle_img = cpu_baseline(v, i, n, cam, light, W, H, SPP, DEPTH, SSS)
             if oracle_img is not None and timed_frame is not None:
                 # raytrace_comp.comp:420-470 as restated by oracle/pt_oracle.cpp,
@@ -2267,7 +2357,8 @@ def main():
             out_line["config"]["rccl_comm_ranks"] = comm_ranks
         if ipc_error:
             out_line["config"]["exchange_fallback"] = ipc_error[:300]
-        if world == 1 and emu == 1 and default_cfg and not (args.no_scene_legs or args.profile_run or args.packed):
+        if (args.full and world == 1 and emu == 1 and default_cfg
+                and not (args.no_scene_legs or args.profile_run or args.packed)):
             torch.cuda.synchronize(dev)
             del r
             for c in ctxs:   # the N = 1 contexts go before the legs make theirs

@@ -116,3 +116,34 @@ def test_two_rank_dry_run_prints_one_compact_last_line(tmp_path):
     assert line["detail_file"] == str(tmp_path / "detail.json")
     detail = json.load(open(line["detail_file"]))
     assert detail["group_leg"]["peer_store_check"]["state"] == "matched"
+
+
+def test_dump_outputs_writes_the_whole_frame_as_float32(tmp_path):
+    """--dump-outputs: a frame within the size limit lands whole, bit for
+    bit, as float32 [H, W, 4]."""
+    import numpy as np
+    W, H = 37, 23
+    frame = np.random.default_rng(1).random(W * H * 4, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "out"), frame, W, H)
+    got = np.load(tmp_path / "out" / "accum.npy")
+    assert got.dtype == np.float32 and got.shape == (H, W, 4)
+    assert np.array_equal(got.reshape(-1).view(np.uint32), frame.view(np.uint32))
+
+
+def test_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_path, monkeypatch):
+    """A frame above the limit is written as a seeded sample of its pixels:
+    within the limit, the same pixels on every call, each a pixel of the
+    frame (its first float carries the pixel's index here)."""
+    import numpy as np
+    W, H = 64, 48
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 500)
+    frame = np.zeros((H * W, 4), np.float32)
+    frame[:, 0] = np.arange(H * W)
+    frame[:, 1:] = np.random.default_rng(2).random((H * W, 3), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame.reshape(-1), W, H)
+    a, b = np.load(tmp_path / "a" / "accum.npy"), np.load(tmp_path / "b" / "accum.npy")
+    assert a.dtype == np.float32 and a.shape == (500, 4) and a.nbytes <= 16 * 500
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    idx = a[:, 0].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(a.view(np.uint32), frame[idx].view(np.uint32))

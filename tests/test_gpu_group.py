@@ -197,7 +197,7 @@ def _devices():
     return torch.cuda.device_count()
 
 
-@pytest.mark.skipif("_devices() < 2")
+@pytest.mark.skipif("_devices() < 2", reason="needs at least 2 GPUs (members on distinct devices)")
 @pytest.mark.parametrize("exchange", [0, 1])
 def test_group_on_distinct_devices(exchange):
     """members on distinct GPUs -- peer stores into the

@@ -73,7 +73,7 @@ def test_two_rank_bench_verifies_bitwise(collective, extra):
     env = dict(os.environ, PT_BENCH_DEVICE="0", PT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--standalone", "--local-addr", "127.0.0.1",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--verify",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--verify",
            "--no-scene-legs", "--collective", collective] + extra
     res = _run(cmd, env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -97,7 +97,7 @@ def test_native_step_loop_single_rank_rccl(streams):
     self-check and by --verify over every assembled frame."""
     env = dict(os.environ, PT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "3", "--verify",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "7", "--warmup", "3", "--verify",
            "--no-scene-legs", "--no-cpu-baseline", "--streams", str(streams)]
     res = _run(cmd, env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -124,7 +124,7 @@ def test_native_step_loop_two_ranks_grouped_send_recv(streams):
                PT_RCCL_LIB=SHIM)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--standalone", "--local-addr", "127.0.0.1",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--verify",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "3", "--verify",
            "--no-scene-legs", "--streams", str(streams)]
     res = _run(cmd, env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -145,7 +145,7 @@ def test_two_rank_scene_legs_reduce_bitwise():
                PT_BENCH_DIST_LEGS="config4 sphere 640 360 4 8 2;config5 synthetic:300000 480 270 2 4 2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--standalone", "--local-addr", "127.0.0.1",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1"]
     res = _run(cmd, env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = _record(res)
@@ -262,8 +262,8 @@ def test_bench_group_leg_members_on_one_device():
     on device 0: both exchanges timed and each last frame bitwise the
     one-GPU frame; the peer-store probe check is not armed on one device."""
     env = dict(os.environ)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-scene-legs",
-           "--no-cpu-baseline", "--group-devices", "0,0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
+           "--no-scene-legs", "--no-cpu-baseline", "--group-devices", "0,0"]
     res = _run(cmd, env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = _record(res)

@@ -8,8 +8,16 @@ pt_scene_parse_obj (csrc/scene/obj_loader.cpp) and the oracle's
 oracle_obj_parse -- must reproduce its vertex floats bit for bit and its
 triangle index order exactly: the order decides the BVH the builder makes
 (BoundingVolumeHierarchy.cpp:25-82) and so every traversal tie-break.
+
+Where the reference tree (and so the library) is absent, the same checks run
+against tests/golden/ref_tinyobj.json: SHA-256 digests of the arrays the
+reference loader returned for every file these tests use, recorded by
+tests/golden/make_ref_tinyobj.py.  With the library present the recorded
+digests are checked against it as well, so they cannot go stale.
 """
 import ctypes
+import hashlib
+import json
 import os
 import subprocess
 
@@ -23,15 +31,39 @@ from test_host import OBJ_CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_tinyobj.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_tinyobj.json")
 _REF = None
+_GOLDEN = None
+
+
+def golden():
+    global _GOLDEN
+    if _GOLDEN is None:
+        with open(GOLDEN) as f:
+            _GOLDEN = json.load(f)
+    return _GOLDEN
+
+
+def digest(*arrays):
+    """SHA-256 over the arrays' lengths and 32-bit little-endian words
+    (floats by their bits, indices as uint32)."""
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a).reshape(-1)
+        w = a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.uint32)
+        h.update(np.uint64(w.size).tobytes())
+        h.update(w.astype("<u4").tobytes())
+    return h.hexdigest()
 
 
 def ref_lib():
+    """The reference loader's library, built on demand where the reference
+    tree exists; None where it does not (the recorded digests then stand in)."""
     global _REF
     if _REF is None:
         if not os.path.exists(REF_SO):
             if not os.path.exists("/root/reference/external/tiny_obj_loader.h"):
-                pytest.skip("oracle/_ref not built and the reference tree is absent")
+                return None
             subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
         L = ctypes.CDLL(REF_SO)
         sz = ctypes.c_size_t
@@ -129,34 +161,70 @@ for _s in range(6):
     CASES[f"combs_{_s}"] = _combs(_s)
 
 
+def fuzz_files():
+    """(key, text) of the 200 generated files of the fuzz test."""
+    for seed in range(100, 200):
+        yield f"random_polygons_{seed}", _random_polygons(seed)
+        yield f"combs_{seed}", _combs(seed)
+
+
+def case_record(text):
+    """What the golden file keeps of a case: the reference loader's array
+    sizes and a digest of each array (vertices, indices, uvs, materials)."""
+    v, i, t, m = ref_parse(text)
+    return {"sizes": [int(v.size), int(i.size), int(t.size), int(m.size)],
+            "v": digest(v), "i": digest(i), "t": digest(t), "m": digest(m)}
+
+
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_restatements_match_reference_tinyobj(case):
     text = CASES[case]
-    rv, ri, rt, rm = ref_parse(text)
+    want = golden()["cases"][case]
     pv, pi, _, pt, pm = ptamd.Scene.parse_obj(text).arrays()
     ov, oi, ot = O.obj_parse(text)
-    for name, v, i in (("product", pv, pi), ("oracle", ov, oi)):
-        assert v.shape == rv.shape and np.array_equal(v.view(np.uint32), rv.view(np.uint32)), f"{name} vertices"
-        assert np.array_equal(i, ri), f"{name} triangle index order"
-    assert np.array_equal(pt.view(np.uint32), rt.view(np.uint32)) and np.array_equal(ot.view(np.uint32),
-                                                                                    rt.view(np.uint32))
-    assert np.array_equal(pm, rm)
+    if ref_lib() is not None:
+        rv, ri, rt, rm = ref_parse(text)
+        assert case_record(text) == want, "tests/golden/ref_tinyobj.json no longer matches the reference loader"
+        for name, v, i in (("product", pv, pi), ("oracle", ov, oi)):
+            assert v.shape == rv.shape and np.array_equal(v.view(np.uint32), rv.view(np.uint32)), f"{name} vertices"
+            assert np.array_equal(i, ri), f"{name} triangle index order"
+        assert np.array_equal(pt.view(np.uint32), rt.view(np.uint32)) and np.array_equal(ot.view(np.uint32),
+                                                                                        rt.view(np.uint32))
+        assert np.array_equal(pm, rm)
+    for name, v, i, t in (("product", pv, pi, pt), ("oracle", ov, oi, ot)):
+        assert v.ndim == 1 and digest(v) == want["v"], f"{name} vertices"
+        assert digest(i) == want["i"], f"{name} triangle index order"
+        assert digest(t) == want["t"], f"{name} uvs"
+    assert digest(pm) == want["m"]
 
 
 def test_reference_loader_box_fixture():
     """The reference loader's box.obj: 8 vertices, 12 triangles, 14 uvs."""
-    v, i, t, m = ref_parse(CASES["box.obj"])
-    assert v.size == 24 and i.size == 36 and t.size == 28 and m.size == 12
+    if ref_lib() is not None:
+        v, i, t, m = ref_parse(CASES["box.obj"])
+        sizes = [int(v.size), int(i.size), int(t.size), int(m.size)]
+        assert sizes == golden()["cases"]["box.obj"]["sizes"]
+    else:
+        sizes = golden()["cases"]["box.obj"]["sizes"]
+    assert sizes == [24, 36, 28, 12]
 
 
 def test_fuzzed_polygons_match_reference_tinyobj():
     """200 more generated files (both generators): product, oracle and the
     reference loader agree on every vertex bit and triangle index."""
-    for seed in range(100, 200):
-        for text in (_random_polygons(seed), _combs(seed)):
+    want = golden()["fuzz"]
+    have_ref = ref_lib() is not None
+    n = 0
+    for key, text in fuzz_files():
+        pv, pi, _, _, pm = ptamd.Scene.parse_obj(text).arrays()
+        ov, oi, _ = O.obj_parse(text)
+        if have_ref:
             rv, ri, _, rm = ref_parse(text)
-            pv, pi, _, _, pm = ptamd.Scene.parse_obj(text).arrays()
-            ov, oi, _ = O.obj_parse(text)
-            assert np.array_equal(pv.view(np.uint32), rv.view(np.uint32)) and np.array_equal(pi, ri), seed
-            assert np.array_equal(ov.view(np.uint32), rv.view(np.uint32)) and np.array_equal(oi, ri), seed
-            assert np.array_equal(pm, rm), seed
+            assert digest(rv, ri, rm) == want[key], f"{key}: the golden file no longer matches the reference loader"
+            assert np.array_equal(pv.view(np.uint32), rv.view(np.uint32)) and np.array_equal(pi, ri), key
+            assert np.array_equal(ov.view(np.uint32), rv.view(np.uint32)) and np.array_equal(oi, ri), key
+            assert np.array_equal(pm, rm), key
+        assert digest(pv, pi, pm) == want[key], key
+        assert digest(ov, oi) == digest(pv, pi), key
+        n += 1
+    assert n == 200 and len(want) == 200

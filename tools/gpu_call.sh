@@ -11,7 +11,7 @@
 #   tests:EXPR        GPU tests matching -k EXPR
 #   smoke             __graft_entry__.smoke()
 #   bench             the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
-#   bench_default     bench.py with no flags (200 steps, legs, CPU baseline)
+#   bench_default     bench.py --full (200 steps, legs, CPU baseline)
 #   bench200          the box alone, 200 steps (no legs, no CPU baseline)
 #   single[:K]        tools/single_ctx.py K (default 200): the one-context drop-in frame
 #   emu:N             rank 0 of an emulated N-GPU box run (PT_BENCH_EMULATE_RANKS=N, 200 steps)
@@ -54,10 +54,10 @@ for step in "$@"; do
       PT_BENCH_DETAIL=$OUT/bench_detail.json run 600 "$OUT/bench.log" python bench.py --gpus 1 --steps 20 --warmup 5
       tail -1 "$OUT/bench.log" | cut -c1-600 ;;
     bench_default)
-      PT_BENCH_DETAIL=$OUT/bench_default_detail.json run 600 "$OUT/bench_default.log" python bench.py
+      PT_BENCH_DETAIL=$OUT/bench_default_detail.json run 600 "$OUT/bench_default.log" python bench.py --full
       tail -1 "$OUT/bench_default.log" | cut -c1-600 ;;
     bench200)
-      PT_BENCH_DETAIL=$OUT/bench200_detail.json run 300 "$OUT/bench200.log" python bench.py --steps 200 \
+      PT_BENCH_DETAIL=$OUT/bench200_detail.json run 300 "$OUT/bench200.log" python bench.py --full --steps 200 \
         --no-scene-legs --no-cpu-baseline
       tail -1 "$OUT/bench200.log" | cut -c1-400 ;;
     single|single:*)
@@ -66,7 +66,7 @@ for step in "$@"; do
       grep K= "$OUT/single.log" ;;
     emu:*)
       n=${step#emu:}
-      PT_BENCH_EMULATE_RANKS=$n PT_BENCH_DETAIL=$OUT/emu$n.json run 300 "$OUT/emu$n.log" python bench.py --steps 200 \
+      PT_BENCH_EMULATE_RANKS=$n PT_BENCH_DETAIL=$OUT/emu$n.json run 300 "$OUT/emu$n.log" python bench.py --full --steps 200 \
         --warmup 10 --no-scene-legs
       tail -1 "$OUT/emu$n.log" | cut -c1-300 ;;
     profile:*)

@@ -13,7 +13,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --ti
   || { echo "pytest rc=$?"; tail -30 $OUT/parity.log; exit 1; }
 tail -1 $OUT/parity.log
 for rep in $(seq ${REPS:-2}); do
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline ${EXTRA:---no-scene-legs} > $OUT/bench_$rep.log 2>&1 \
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline ${EXTRA:---no-scene-legs} > $OUT/bench_$rep.log 2>&1 \
     || { echo "bench rc=$?"; tail -5 $OUT/bench_$rep.log; exit 1; }
   grep '^{' $OUT/bench_$rep.log | python3 -c '
 import json,sys

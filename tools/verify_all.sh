@@ -15,6 +15,6 @@ timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/s
   || { echo "smoke rc=$?"; tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
 if [ "${SKIP_BENCH:-0}" = "1" ]; then exit 0; fi
-timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 \
+timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 \
   || { echo "bench rc=$?"; tail -20 $OUT/bench.log; exit 1; }
 grep '^{' $OUT/bench.log | tail -1 | cut -c1-400
