@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/pathtracer.h"
+#include "pt_denoise.h"
 #include "pt_device.h"
 #include "pt_group.h"
 #include "pt_math.h"
@@ -472,6 +473,17 @@ struct pt_context {
                               // a pair costs the one-stream frame ~10 us, profiles/r06a)
   long long launch_n = 0;     // render launches since pt_reset_launch_times
   long long ring_launch[kRing] = {};   // launch number of each recorded pair
+  // first-hit guide image and a-trous filter (pt_render_guide, pt_denoise):
+  // library-owned W x H float4 images, grown on demand
+  float4* d_guide = nullptr;
+  size_t guide_cap = 0;                // pixels d_guide holds
+  bool guide_valid = false;            // d_guide is the guide of the current scene, camera and size
+  float4* d_dn_scratch[2] = {nullptr, nullptr};   // the passes' ping-pong images
+  size_t dn_scratch_cap[2] = {0, 0};
+  float4* d_denoised = nullptr;        // pt_denoise's destination when the caller gives none
+  size_t denoised_cap = 0;
+  int denoised_w = 0, denoised_h = 0;  // size of the image d_denoised holds (0: none yet)
+  int opt_denoise_lds = 1;             // PT_OPT_DENOISE_LDS
   DistState* dist = nullptr;           // pt_dist_init
   pt_group* group = nullptr;           // pt_create_multi: every call goes to the group (pt_group.cpp)
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -1017,6 +1029,50 @@ extern "C" int pt_items_unpack_all(pt_context* c, const void* src, size_t slot_f
 namespace {
 // pt_render / pt_render_packed (pack_out != null: fresh frame, live items
 // written to pack_out in the pt_items_pack layout).
+// The camera block and the frame main() derives from it (:447-448, :457),
+// computed on the host with pt_math.h.
+void camera_params(const float cam[16], ptd::RenderParams* p) {
+  const ptdn::CamBasis b = ptdn::cam_basis(cam);
+  for (int i = 0; i < 3; ++i) {
+    p->cam_pos[i] = cam[i];
+    p->cam_dir[i] = cam[4 + i];
+    p->cam_up[i] = cam[8 + i];
+  }
+  p->fov = cam[12];
+  p->cam_right[0] = b.right.x; p->cam_right[1] = b.right.y; p->cam_right[2] = b.right.z;
+  p->cam_upv[0] = b.up.x; p->cam_upv[1] = b.up.y; p->cam_upv[2] = b.up.z;
+  p->tan_fov = b.tan_fov;
+}
+
+// The culled wide walk's arrays for a launch, its per-lane stack overflow
+// areas (re)allocated first when the grid or the scene's stack bound outgrew
+// them.
+int wide_params(pt_context* c, ptd::RenderParams* p) {
+  const long long lanes = ptd::wide_trace_lanes();
+  if (lanes <= 0) return fail(PT_ERR_HIP, "wide walk: occupancy query failed");
+  const int stack = c->wide_stack;
+  if (lanes > c->wide_ovf_lanes || stack > c->wide_ovf_stack) {   // every lane of the grid gets its area
+    { const int rc_ = quiesce(c); if (rc_) return rc_; }
+    dev_free(c->d_wide_ovf);
+    c->wide_ovf_lanes = 0;
+    // two sets: the two halves of a chunk trace concurrently (launch_wavefront)
+    PT_HIP(hipMalloc((void**)&c->d_wide_ovf, 2 * (size_t)lanes * (size_t)stack * sizeof(int2)));
+    c->wide_ovf_lanes = lanes;
+    c->wide_ovf_stack = stack;
+  }
+  // closest hits come back as leaf ranks
+  p->wide_qn = c->opt_wide_node == 64 ? 1 : 0;
+  p->wide = p->wide_qn ? c->d_wide_q : c->d_wide;
+  p->wide_leafbox = c->d_wide_leafbox;
+  p->wide_tris = c->d_wide_tris;
+  p->wide_rank_of = c->d_wide_rank_of;
+  p->hit_tris = c->d_wide_tris;
+  p->wide_ovf = c->d_wide_ovf;
+  p->wide_ovf_lanes = c->wide_ovf_lanes;
+  p->wide_stack = stack;
+  return PT_OK;
+}
+
 struct Assembly {   // pt_render_packed's optional gathered frame to assemble
   const void* src = nullptr;
   size_t slot_floats = 0;
@@ -1086,22 +1142,7 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   p.n_batches = n_batches;
   p.max_depth = c->params.max_depth;
   p.sss_bounces = c->params.sss_bounces;
-  for (int i = 0; i < 3; ++i) {
-    p.cam_pos[i] = c->cam[i];
-    p.cam_dir[i] = c->cam[4 + i];
-    p.cam_up[i] = c->cam[8 + i];
-  }
-  p.fov = c->cam[12];
-  {
-    using namespace ptm;
-    const v3 cdir = mk(p.cam_dir[0], p.cam_dir[1], p.cam_dir[2]);
-    const v3 cup = mk(p.cam_up[0], p.cam_up[1], p.cam_up[2]);
-    const v3 right = normalize(cross(cdir, neg(cup)));
-    const v3 up = normalize(cross(right, cdir));
-    p.cam_right[0] = right.x; p.cam_right[1] = right.y; p.cam_right[2] = right.z;
-    p.cam_upv[0] = up.x; p.cam_upv[1] = up.y; p.cam_upv[2] = up.z;
-    p.tan_fov = tan_(radians_(p.fov * 0.5f));
-  }
+  camera_params(c->cam, &p);
   p.blocks_x = (c->width + 15) / 16;
   p.blocks_total = p.blocks_x * ((c->height + 15) / 16);
   p.nranks = c->nranks;
@@ -1294,28 +1335,8 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
     ptd::WfBuffers b = c->wf;
     b.cap = chunk_paths;   // paths per chunk (the allocation may be larger)
     if (c->opt_wide && c->n_wide > 0 && !lds) {
-      const long long lanes = ptd::wide_trace_lanes();
-      if (lanes <= 0) return fail(PT_ERR_HIP, "wide walk: occupancy query failed");
-      const int stack = c->wide_stack;
-      if (lanes > c->wide_ovf_lanes || stack > c->wide_ovf_stack) {   // every lane of the grid gets its area
-        { const int rc_ = quiesce(c); if (rc_) return rc_; }
-        dev_free(c->d_wide_ovf);
-        c->wide_ovf_lanes = 0;
-        // two sets: the two halves of a chunk trace concurrently (launch_wavefront)
-        PT_HIP(hipMalloc((void**)&c->d_wide_ovf, 2 * (size_t)lanes * (size_t)stack * sizeof(int2)));
-        c->wide_ovf_lanes = lanes;
-        c->wide_ovf_stack = stack;
-      }
-      // closest hits come back as leaf ranks
-      p.wide_qn = c->opt_wide_node == 64 ? 1 : 0;
-      p.wide = p.wide_qn ? c->d_wide_q : c->d_wide;
-      p.wide_leafbox = c->d_wide_leafbox;
-      p.wide_tris = c->d_wide_tris;
-      p.wide_rank_of = c->d_wide_rank_of;
-      p.hit_tris = c->d_wide_tris;
-      p.wide_ovf = c->d_wide_ovf;
-      p.wide_ovf_lanes = c->wide_ovf_lanes;
-      p.wide_stack = stack;
+      const int rw = wide_params(c, &p);
+      if (rw) return rw;
       p.wide_handback = c->opt_wide == 2 ? 1 : 0;
       // fused shadow walks: hit records carry the rank in 29 bits
       p.wf_fuse = c->opt_wf_fuse && c->n_tris <= ptd::kHitRankMask && c->n_lights > 0 ? 1 : 0;
@@ -1498,6 +1519,10 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_unpack);
   dev_free(c->d_unpack_live);
   dev_free(c->wf_block);
+  dev_free(c->d_guide);
+  dev_free(c->d_dn_scratch[0]);
+  dev_free(c->d_dn_scratch[1]);
+  dev_free(c->d_denoised);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1580,6 +1605,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->wide_ovf_stack = 0;
   c->n_wide = 0;
   c->has_scene = false;
+  c->guide_valid = false;
   const int T = (int)(n_indices / 3);
   struct Staging {   // vertex/index copies live only until the triangle records are built
     float* v = nullptr;
@@ -1664,6 +1690,7 @@ int pt_upload_lights(pt_context* c, const pt_area_light* lights, size_t n) {
 int pt_set_camera(pt_context* c, const float ubo[16]) {
   if (c && c->group) return ptg::set_camera(c->group, ubo);
   if (!c || !ubo) return fail(PT_ERR_INVALID, "null argument");
+  if (!c->has_camera || memcmp(c->cam, ubo, sizeof c->cam) != 0) c->guide_valid = false;
   memcpy(c->cam, ubo, sizeof c->cam);
   c->has_camera = true;
   return PT_OK;
@@ -1731,6 +1758,7 @@ int pt_resize_and_clear(pt_context* c, int w, int h) {
   if (!c) return fail(PT_ERR_INVALID, "null context");
   if (w <= 0 || h <= 0 || (long long)w * h > (1ll << 31)) return fail(PT_ERR_INVALID, "bad resolution");
   PT_HIP(hipSetDevice(c->device));
+  if (c->width != w || c->height != h) c->guide_valid = false;
   if (!(c->own_accum && c->width == w && c->height == h)) {
     { const int rc_ = quiesce(c); if (rc_) return rc_; }
     if (c->own_accum) dev_free(c->d_accum);
@@ -1754,6 +1782,7 @@ int pt_bind_accum(pt_context* c, void* ptr, int w, int h) {
   if (c->own_accum) dev_free(c->d_accum);
   c->d_accum = (float4*)ptr;
   c->own_accum = false;
+  if (c->width != w || c->height != h) c->guide_valid = false;
   c->width = w;
   c->height = h;
   c->culled_state = 0;   // the caller's buffer: its content is not known
@@ -1905,6 +1934,187 @@ int pt_readback_end(pt_context* c, int ticket, float* rgba, size_t n) {
   return fail(PT_ERR_INVALID, "unknown or already collected readback ticket " + std::to_string(ticket));
 }
 
+// ---- first-hit guide image and a-trous denoiser (pt_denoise.h) --------------
+int pt_denoise_default_params(pt_denoise_params* out) {
+  if (!out) return fail(PT_ERR_INVALID, "null argument");
+  out->iterations = 5;
+  out->sigma_color = 16.0f;
+  out->sigma_normal = 0.35f;
+  out->sigma_depth = 0.25f;
+  return PT_OK;
+}
+
+static int denoise_params(const pt_denoise_params* in, pt_denoise_params* p) {
+  if (in)
+    *p = *in;
+  else
+    (void)pt_denoise_default_params(p);
+  if (!ptdn::params_ok(p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth))
+    return fail(PT_ERR_INVALID, "pt_denoise_params: iterations 1-6; sigmas finite, > 0 and with a finite non-zero square");
+  return PT_OK;
+}
+
+int pt_guide_ray(const float ubo[16], int w, int h, int x, int y, float o3[3], float d3[3]) {
+  if (!ubo || !o3 || !d3) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0 || x < 0 || y < 0 || x >= w || y >= h) return fail(PT_ERR_INVALID, "pixel outside the frame");
+  const ptdn::CamBasis b = ptdn::cam_basis(ubo);
+  const ptm::v3 d = ptdn::guide_dir(b.dir, b.right, b.up, b.tan_fov, w, h, x, y);
+  o3[0] = b.pos.x; o3[1] = b.pos.y; o3[2] = b.pos.z;
+  d3[0] = d.x; d3[1] = d.y; d3[2] = d.z;
+  return PT_OK;
+}
+
+int pt_denoise_host(const float* rgba, const float* guide, int w, int h, const pt_denoise_params* params, float* out) {
+  if (!rgba || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
+  pt_denoise_params p;
+  const int rp = denoise_params(params, &p);
+  if (rp) return rp;
+  const size_t n = (size_t)w * (size_t)h;
+  std::vector<float4> g(n), a(n), b(n);
+  memcpy(g.data(), guide, n * sizeof(float4));
+  memcpy(a.data(), rgba, n * sizeof(float4));
+  for (int i = 0; i < p.iterations; ++i) {
+    const ptdn::Sigma2 s = ptdn::pass_sigma2(p.sigma_color, p.sigma_normal, p.sigma_depth, i);
+    const ptdn::ImageFetch fetch = {a.data(), g.data(), w};
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) b[(size_t)y * w + x] = ptdn::atrous_pixel(fetch, w, h, x, y, 1 << i, s);
+    a.swap(b);
+  }
+  memcpy(out, a.data(), n * sizeof(float4));
+  return PT_OK;
+}
+
+// A library-owned image of at least n pixels.
+static int grow_image(pt_context* c, float4** img, size_t* cap, size_t n) {
+  if (*img && *cap >= n) return PT_OK;
+  { const int rc_ = quiesce(c); if (rc_) return rc_; }
+  dev_free(*img);
+  *cap = 0;
+  PT_HIP(hipMalloc((void**)img, n * sizeof(float4)));
+  *cap = n;
+  return PT_OK;
+}
+
+int pt_render_guide(pt_context* c) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_render_guide: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
+  if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
+  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
+  PT_HIP(hipSetDevice(c->device));
+  c->guide_valid = false;
+  ptd::RenderParams p{};
+  p.nodes = c->d_nodes;
+  p.n_nodes = c->n_nodes;
+  p.tris = c->d_tris;
+  p.hit_tris = c->d_tris;
+  p.n_tris = c->n_tris;
+  p.width = c->width;
+  p.height = c->height;
+  camera_params(c->cam, &p);
+  p.blocks_x = (c->width + 15) / 16;
+  p.blocks_total = p.blocks_x * ((c->height + 15) / 16);
+  p.n_cull = -1;
+  const bool wide = c->opt_wide && c->n_wide > 0;
+  const bool fits = ptd::scene_lds_bytes(p) <= ptd::kMaxSceneLds;
+  if (!wide && c->opt_scene_lds == 2 && !fits) return fail(PT_ERR_UNSUPPORTED, "scene too large for the LDS variant");
+  const bool lds = !wide && (c->opt_scene_lds == 2 || (c->opt_scene_lds == 1 && fits));
+  if (wide) {
+    const int rw = wide_params(c, &p);
+    if (rw) return rw;
+  }
+  const int rg = grow_image(c, &c->d_guide, &c->guide_cap, (size_t)c->width * c->height);
+  if (rg) return rg;
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(ptd::launch_guide(p, c->d_guide, lds, c->stream));
+  c->guide_valid = true;
+  return mark_shared(c);
+}
+
+void* pt_guide_device_ptr(pt_context* c) {
+  if (!c || c->group || !c->guide_valid) return nullptr;
+  return (void*)c->d_guide;
+}
+
+// Copies a library-owned W x H image to the host behind the work enqueued so far.
+static int read_image(pt_context* c, const float4* img, int w, int h, float* out, size_t n) {
+  const size_t need = (size_t)w * h * 4;
+  if (n < need) return fail(PT_ERR_INVALID, "output buffer too small: need " + std::to_string(need) + " floats");
+  PT_HIP(hipSetDevice(c->device));
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(hipMemcpyAsync(out, img, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+int pt_read_guide(pt_context* c, float* out, size_t n) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_guide: not on a multi-device context (pt_create_multi)");
+  if (!c || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (!c->guide_valid) return fail(PT_ERR_INVALID, "no guide image for the current scene, camera and size (pt_render_guide)");
+  return read_image(c, c->d_guide, c->width, c->height, out, n);
+}
+
+int pt_denoise(pt_context* c, const pt_denoise_params* params, const void* src, void* dst) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_denoise: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  pt_denoise_params p;
+  const int rp = denoise_params(params, &p);
+  if (rp) return rp;
+  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
+  if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
+  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
+  if ((((uintptr_t)src) & 15) || (((uintptr_t)dst) & 15)) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
+  const float4* in = src ? (const float4*)src : c->d_accum;
+  if (dst && (const float4*)dst == in) return fail(PT_ERR_INVALID, "pt_denoise: source and destination must differ");
+  PT_HIP(hipSetDevice(c->device));
+  if (!c->guide_valid) {
+    const int rg = pt_render_guide(c);
+    if (rg) return rg;
+  }
+  const int w = c->width, h = c->height;
+  const size_t n = (size_t)w * h;
+  for (int k = 0; k < 2 && k < p.iterations - 1; ++k) {   // the ping-pong images the passes need
+    const int rs = grow_image(c, &c->d_dn_scratch[k], &c->dn_scratch_cap[k], n);
+    if (rs) return rs;
+  }
+  float4* out = (float4*)dst;
+  if (!out) {
+    c->denoised_w = c->denoised_h = 0;
+    const int rd = grow_image(c, &c->d_denoised, &c->denoised_cap, n);
+    if (rd) return rd;
+    out = c->d_denoised;
+  }
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  // pass i reads the previous pass's image (the source first) and writes a
+  // scratch image, the last one the destination; the source is only read
+  const float4* cur = in;
+  for (int i = 0; i < p.iterations; ++i) {
+    float4* to = i == p.iterations - 1 ? out : c->d_dn_scratch[i & 1];
+    const ptdn::Sigma2 s = ptdn::pass_sigma2(p.sigma_color, p.sigma_normal, p.sigma_depth, i);
+    PT_HIP(ptd::launch_atrous(cur, c->d_guide, to, w, h, 1 << i, s.c, s.n, s.z, c->opt_denoise_lds != 0 && i < 2,
+                              c->stream));
+    cur = to;
+  }
+  if (!dst) {
+    c->denoised_w = w;
+    c->denoised_h = h;
+  }
+  if (out == c->d_accum) c->culled_state = 0;   // the accumulation buffer given as the destination
+  return mark_shared(c);
+}
+
+int pt_read_denoised(pt_context* c, float* rgba, size_t n) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_denoised: not on a multi-device context (pt_create_multi)");
+  if (!c || !rgba) return fail(PT_ERR_INVALID, "null argument");
+  if (!c->d_denoised || c->denoised_w == 0)
+    return fail(PT_ERR_INVALID, "no library-owned denoised image (pt_denoise with a null destination)");
+  return read_image(c, c->d_denoised, c->denoised_w, c->denoised_h, rgba, n);
+}
+
 int pt_last_kernel(pt_context* c, int* kernel) {
   if (c && c->group) return ptg::last_kernel(c->group, kernel);
   if (!c || !kernel) return fail(PT_ERR_INVALID, "null argument");
@@ -1996,6 +2206,10 @@ int pt_set_option(pt_context* c, int key, int value) {
     case PT_OPT_SCENE_IN_LDS:
       if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "PT_OPT_SCENE_IN_LDS takes 0, 1 or 2");
       c->opt_scene_lds = value;
+      return PT_OK;
+    case PT_OPT_DENOISE_LDS:
+      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_DENOISE_LDS takes 0 or 1");
+      c->opt_denoise_lds = value;
       return PT_OK;
     case PT_OPT_GROUP_EXCHANGE:
     case PT_OPT_GROUP_CHECK:

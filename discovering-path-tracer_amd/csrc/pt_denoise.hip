@@ -1,0 +1,81 @@
+// pt_denoise.hip — the edge-avoiding a-trous filter's pass kernels
+// (pt_denoise); the filter's statement is pt_denoise.h, shared with the host.
+//
+// One pixel per lane, 16x16 pixels per workgroup, a wave a 16x4 strip: the
+// lanes of a tile row read 256 consecutive bytes of each image per tap.
+// atrous_kernel reads every tap from the images (two 16-B loads per tap, the
+// reuse between neighbouring lanes left to the caches); atrous_staged_kernel
+// first copies the tile and its halo of 2 * STEP pixels to LDS (steps 1 and 2:
+// 20x20 and 24x24 pixels, 12.5 and 18 KB) and taps from there.  Both run
+// atrous_pixel over the same values, so their images are the same bits.
+#include "pt_denoise.h"
+#include "pt_device.h"
+
+#pragma clang fp contract(off)
+
+namespace ptd {
+namespace {
+using namespace ptdn;
+
+__global__ __launch_bounds__(256) void atrous_kernel(const float4* __restrict__ src, const float4* __restrict__ guide,
+                                                     float4* __restrict__ dst, int W, int H, int step, Sigma2 s) {
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const ImageFetch fetch = {src, guide, W};
+  dst[(size_t)y * (size_t)W + (size_t)x] = atrous_pixel(fetch, W, H, x, y, step, s);
+}
+
+template <int STEP>
+struct TileFetch {
+  static constexpr int kSide = 16 + 4 * STEP;
+  const float4* color;   // LDS, kSide x kSide, pixel (x0 - 2 STEP, y0 - 2 STEP) first
+  const float4* guide;
+  int x0, y0;            // frame position of the tile's first LDS pixel
+  __device__ inline void operator()(int qx, int qy, float4* c, float4* g) const {
+    const int i = (qy - y0) * kSide + (qx - x0);
+    *c = color[i];
+    *g = guide[i];
+  }
+};
+
+template <int STEP>
+__global__ __launch_bounds__(256) void atrous_staged_kernel(const float4* __restrict__ src,
+                                                            const float4* __restrict__ guide,
+                                                            float4* __restrict__ dst, int W, int H, Sigma2 s) {
+  constexpr int kSide = TileFetch<STEP>::kSide;
+  __shared__ float4 tc[kSide * kSide], tg[kSide * kSide];
+  const int x0 = (int)blockIdx.x * 16 - 2 * STEP, y0 = (int)blockIdx.y * 16 - 2 * STEP;
+  for (int i = (int)threadIdx.x; i < kSide * kSide; i += 256) {
+    const int gx = x0 + i % kSide, gy = y0 + i / kSide;
+    if (gx >= 0 && gx < W && gy >= 0 && gy < H) {   // atrous_pixel never fetches the others
+      const size_t g = (size_t)gy * (size_t)W + (size_t)gx;
+      tc[i] = src[g];
+      tg[i] = guide[g];
+    }
+  }
+  __syncthreads();
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const TileFetch<STEP> fetch = {tc, tg, x0, y0};
+  dst[(size_t)y * (size_t)W + (size_t)x] = atrous_pixel(fetch, W, H, x, y, STEP, s);
+}
+
+}  // namespace
+
+hipError_t launch_atrous(const float4* src, const float4* guide, float4* dst, int width, int height, int step,
+                         float sc2, float sn2, float sz2, bool staged, hipStream_t stream) {
+  if (width <= 0 || height <= 0 || step < 1) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+  const Sigma2 s = {sc2, sn2, sz2};
+  if (staged && step == 1)
+    atrous_staged_kernel<1><<<grid, 256, 0, stream>>>(src, guide, dst, width, height, s);
+  else if (staged && step == 2)
+    atrous_staged_kernel<2><<<grid, 256, 0, stream>>>(src, guide, dst, width, height, s);
+  else
+    atrous_kernel<<<grid, 256, 0, stream>>>(src, guide, dst, width, height, step, s);
+  return hipGetLastError();
+}
+
+}  // namespace ptd

@@ -216,6 +216,15 @@ inline int wf_max_rays(const RenderParams& p) {
 hipError_t launch_wavefront(const RenderParams& p, const WfBuffers& b, bool lds_scene, hipStream_t stream,
                             bool cnt = false, hipStream_t stream2 = nullptr, hipEvent_t ev_fork = nullptr,
                             hipEvent_t ev_join = nullptr);
+// First-hit guide image of the whole frame (pt_render_guide): float4 {n.xyz, t}
+// per pixel from p's camera, size and scene.  p.wide set: the culled wide
+// walk; else the exact walk, staged in LDS with lds_scene.
+hipError_t launch_guide(const RenderParams& p, float4* guide, bool lds_scene, hipStream_t stream);
+// One pass of the a-trous filter (pt_denoise.h atrous_pixel) from src to dst
+// (distinct images) at tap spacing `step` with the pass's squared sigmas;
+// staged: the tile and its halo go through LDS (steps 1 and 2 only).
+hipError_t launch_atrous(const float4* src, const float4* guide, float4* dst, int width, int height, int step,
+                         float sc2, float sn2, float sz2, bool staged, hipStream_t stream);
 // lanes of the wide walk's persistent grid on this device (overflow areas to allocate)
 long long wide_trace_lanes();
 // workgroups of the LDS-staged render kernel resident on this device at once

@@ -6,6 +6,7 @@
 //   pt_render scene.obj [-w 1920] [-h 1080] [-spp 8] [-depth 4] [-sss 3]
 //             [-fused] [-o out.pfm] [-png out.png] [-device 0 | -devices 0,1,..]
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
+//             [-denoise] [-guide normals.pfm]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -15,6 +16,9 @@
 // -devices renders on several GPUs from this one thread (pt_create_multi:
 // each renders its screen tiles straight into the frame on the first one);
 // every other call is unchanged.
+// -denoise filters the final image on the device (pt_denoise, default
+// parameters) before -o / -png are written; -guide writes the first-hit
+// normals of the guide image as a PFM.  Both need a single-device context.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,7 +40,11 @@ static int check(int rc, const char* what) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm]\n", argv[0]);
+    fprintf(stderr,
+            "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
+            "       [-denoise] [-guide normals.pfm] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
+            "       [-progressive N [-chunk K] [-orbit-at B]]\n",
+            argv[0]);
     return 2;
   }
   std::string scene_path = argv[1], out_path;
@@ -44,7 +52,8 @@ int main(int argc, char** argv) {
   pt_params params{4, 3};
   bool fused = false;
   int progressive = 0, chunk = 8, orbit_at = -1;
-  std::string cache_path, png_path;
+  std::string cache_path, png_path, guide_path;
+  bool denoise = false;
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -65,6 +74,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "-o")) out_path = next();
     else if (!strcmp(argv[i], "-cache")) cache_path = next();
     else if (!strcmp(argv[i], "-png")) png_path = next();
+    else if (!strcmp(argv[i], "-denoise")) denoise = true;
+    else if (!strcmp(argv[i], "-guide")) guide_path = next();
     else if (!strcmp(argv[i], "-progressive")) progressive = atoi(next());
     else if (!strcmp(argv[i], "-chunk")) chunk = atoi(next());
     else if (!strcmp(argv[i], "-orbit-at")) orbit_at = atoi(next());
@@ -158,9 +169,20 @@ int main(int argc, char** argv) {
     printf("rendered %dx%d x %d spp in %.3f ms\n", W, H, spp, std::chrono::duration<double, std::milli>(r1 - r0).count());
   if (!out_path.empty() || !png_path.empty()) {
     std::vector<float> rgba((size_t)W * H * 4);
-    check(pt_read_accum(ctx, rgba.data(), rgba.size()), "read");
+    if (denoise) {
+      check(pt_denoise(ctx, nullptr, nullptr, nullptr), "denoise");
+      check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+    } else {
+      check(pt_read_accum(ctx, rgba.data(), rgba.size()), "read");
+    }
     if (!out_path.empty()) check(pt_write_image(out_path.c_str(), rgba.data(), W, H, PT_IMAGE_PFM), "write pfm");
     if (!png_path.empty()) check(pt_write_image(png_path.c_str(), rgba.data(), W, H, PT_IMAGE_PNG), "write png");
+  }
+  if (!guide_path.empty()) {
+    std::vector<float> guide((size_t)W * H * 4);
+    check(pt_render_guide(ctx), "render guide");
+    check(pt_read_guide(ctx, guide.data(), guide.size()), "read guide");
+    check(pt_write_image(guide_path.c_str(), guide.data(), W, H, PT_IMAGE_PFM), "write guide pfm");
   }
   pt_destroy(ctx);
   pt_scene_free(scene);

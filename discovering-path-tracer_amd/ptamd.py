@@ -39,6 +39,7 @@ PT_OPT_GROUP_CHECK = 19
 PT_OPT_WF_GRID = 20
 PT_OPT_WF_REFILL = 21
 PT_OPT_MIXED_LANES = 22
+PT_OPT_DENOISE_LDS = 23
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -57,6 +58,8 @@ EXPORTS = [
     "pt_dist_unique_id", "pt_dist_init", "pt_dist_run", "pt_dist_slot_floats", "pt_dist_finalize",
     "pt_dist_set_streams", "pt_dist_wait", "pt_dist_abort", "pt_create_multi", "pt_group_info",
     "pt_group_check", "pt_dist_info", "pt_mixed_info",
+    "pt_denoise_default_params", "pt_guide_ray", "pt_render_guide", "pt_guide_device_ptr", "pt_read_guide",
+    "pt_denoise", "pt_read_denoised", "pt_denoise_host",
 ]
 
 
@@ -76,6 +79,11 @@ class Stats(ctypes.Structure):
 class Traced(ctypes.Structure):
     _fields_ = [("closest_walks", ctypes.c_uint64), ("shadow_walks", ctypes.c_uint64), ("nodes", ctypes.c_uint64),
                 ("tri_tests", ctypes.c_uint64), ("primaries", ctypes.c_uint64)]
+
+
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float)]
 
 
 _lib = None
@@ -142,6 +150,13 @@ def lib():
             "pt_items_unpack_all": ([vp, vp, sz, vp], i32),
             "pt_render_packed": ([vp, u32, vp, vp, sz, vp], i32),
             "pt_scene_load_cache": ([ctypes.c_char_p, ctypes.POINTER(vp)], i32),
+            "pt_denoise_default_params": ([ctypes.POINTER(DenoiseParams)], i32),
+            "pt_guide_ray": ([vp, i32, i32, i32, i32, vp, vp], i32),
+            "pt_render_guide": ([vp], i32), "pt_guide_device_ptr": ([vp], vp),
+            "pt_read_guide": ([vp, vp, sz], i32),
+            "pt_denoise": ([vp, ctypes.POINTER(DenoiseParams), vp, vp], i32),
+            "pt_read_denoised": ([vp, vp, sz], i32),
+            "pt_denoise_host": ([vp, vp, i32, i32, ctypes.POINTER(DenoiseParams), vp], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -340,6 +355,44 @@ def default_camera():
     return ubo
 
 
+def denoise_default_params():
+    """pt_denoise_default_params as a DenoiseParams."""
+    p = DenoiseParams()
+    _check(lib().pt_denoise_default_params(ctypes.byref(p)), "pt_denoise_default_params")
+    return p
+
+
+def _denoise_params(params):
+    """None (the library's defaults), a DenoiseParams, or (iterations,
+    sigma_color, sigma_normal, sigma_depth) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, DenoiseParams):
+        return ctypes.byref(params)
+    it, sc, sn, sz = params
+    return ctypes.byref(DenoiseParams(int(it), float(sc), float(sn), float(sz)))
+
+
+def guide_ray(camera_ubo, width, height, x, y):
+    """pt_guide_ray: (origin, direction) of pixel (x, y)'s guide ray (host only)."""
+    cam = np.ascontiguousarray(camera_ubo, np.float32).reshape(16)
+    o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _check(lib().pt_guide_ray(cam.ctypes.data, width, height, x, y, o.ctypes.data, d.ctypes.data), "pt_guide_ray")
+    return o, d
+
+
+def denoise_host(rgba, guide, width, height, params=None):
+    """pt_denoise_host: the a-trous filter on the host, (H, W, 4) float32."""
+    a = np.ascontiguousarray(rgba, np.float32).reshape(-1)
+    g = np.ascontiguousarray(guide, np.float32).reshape(-1)
+    if a.size != width * height * 4 or g.size != a.size:
+        raise PTError("rgba and guide must hold width*height*4 floats")
+    out = np.empty(a.size, np.float32)
+    _check(lib().pt_denoise_host(a.ctypes.data, g.ctypes.data, width, height, _denoise_params(params),
+                                 out.ctypes.data), "pt_denoise_host")
+    return out.reshape(height, width, 4)
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -498,6 +551,30 @@ class Renderer:
         out = np.empty(self.width * self.height * 4, np.float32)
         _check(lib().pt_read_accum(self._c, out.ctypes.data, out.size), "pt_read_accum")
         return out
+
+    def render_guide(self):
+        """Enqueue the first-hit guide image {n.xyz, t} of the current inputs."""
+        _check(lib().pt_render_guide(self._c), "pt_render_guide")
+
+    def guide_ptr(self):
+        return lib().pt_guide_device_ptr(self._c)
+
+    def read_guide(self):
+        """The guide image, (H, W, 4) float32."""
+        out = np.empty(self.width * self.height * 4, np.float32)
+        _check(lib().pt_read_guide(self._c, out.ctypes.data, out.size), "pt_read_guide")
+        return out.reshape(self.height, self.width, 4)
+
+    def denoise(self, params=None, src_ptr=None, dst_ptr=None):
+        """pt_denoise: filter src (default: the accumulation image) into dst;
+        with dst_ptr None the library-owned result is read back and returned
+        as (H, W, 4) float32."""
+        _check(lib().pt_denoise(self._c, _denoise_params(params), src_ptr, dst_ptr), "pt_denoise")
+        if dst_ptr is not None:
+            return None
+        out = np.empty(self.width * self.height * 4, np.float32)
+        _check(lib().pt_read_denoised(self._c, out.ctypes.data, out.size), "pt_read_denoised")
+        return out.reshape(self.height, self.width, 4)
 
     def set_stats_mode(self, on):
         _check(lib().pt_set_stats_mode(self._c, 1 if on else 0), "pt_set_stats_mode")

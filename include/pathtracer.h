@@ -36,7 +36,11 @@ extern "C" {
  * PT_OPT_WIDE_NODE 80 (kernels measured slower on every scene).
  * 3 (round 6): pt_mixed_info and PT_OPT_MIXED_LANES added; defaults changed:
  * PT_OPT_LAUNCH_TIMING 0 (was 1), PT_OPT_ITEM_ORDER -1 auto (was 1);
- * pt_group_check state 2 (probe failed). */
+ * pt_group_check state 2 (probe failed).
+ * Still 3, additions only: the guide image and the a-trous denoiser
+ * (pt_denoise_params, pt_denoise_default_params, pt_guide_ray,
+ * pt_render_guide, pt_guide_device_ptr, pt_read_guide, pt_denoise,
+ * pt_read_denoised, pt_denoise_host, PT_OPT_DENOISE_LDS). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -210,6 +214,90 @@ int pt_progressive_advance(pt_context* ctx, uint32_t max_new, uint32_t limit, ui
  * flight; a third begin recycles the oldest unclaimed one. */
 int pt_readback_begin(pt_context* ctx, int* ticket);
 int pt_readback_end(pt_context* ctx, int ticket, float* rgba, size_t n_floats);
+
+/* ---- first-hit guide image and edge-avoiding a-trous denoiser ---------- */
+/* Downstream of pt_render: nothing in the reference corresponds to it (its
+ * image leaves as it is, VulkanRayTracer.cpp:826-846).  Single-GPU contexts
+ * only: on a pt_create_multi context every call below that takes a context
+ * returns PT_ERR_UNSUPPORTED (pt_guide_device_ptr: null).
+ *
+ * The guide image holds, per pixel, float4 {n.x, n.y, n.z, t}: normal and
+ * distance of the first hit of the pixel's centre ray, {0, 0, 0, 1e30} for a
+ * miss (HitInfo's initial value).  The ray is main()'s without its random
+ * draws (raytrace_comp.comp:430-432, :458): origin = camera position,
+ *   ndcX = ((2 * float(x)) / float(W)) - 1, ndcY likewise, aspect = float(W) / float(H),
+ *   dir  = normalize((cameraDir + (-right) * ((ndcX * tanFov) * aspect)) - up * (ndcY * tanFov)),
+ * traced by one traceRay (:159-204) -- the same hit bit for bit on every walk
+ * the library has.  It is a pinhole ray: the shader's depth-of-field blur
+ * (aperture 0.02, focal distance 3) makes the guide's edges slightly sharper
+ * than the image's.  The image covers every pixel, whatever the partition.
+ *
+ * The filter (Dammertz, Sewtz, Hanika, Lensch: "Edge-avoiding A-trous wavelet
+ * transform for fast global illumination filtering", HPG 2010), restated so
+ * that it is bit-reproducible.  Pass i = 0 .. iterations-1 has tap spacing
+ * s = 1 << i and sc = sigma_color * 2^-i (exact); sn = sigma_normal, sz =
+ * sigma_depth.  For pixel p with colour c_p (the pass's input) and guide g_p,
+ * over the 25 taps q = p + s * (dx, dy), dy = -2..2 outer, dx = -2..2 inner
+ * (the summation order), those outside the frame skipped:
+ *   h   = k[|dx|] * k[|dy|],  k = {3/8, 1/4, 1/16}
+ *   d2c = (dr*dr + dg*dg) + db*db            (rgb of c_p - c_q)
+ *   d2n = (dnx*dnx + dny*dny) + dnz*dnz      (normals of g_p - g_q)
+ *   dz  = t_p - t_q
+ *   w   = h * exp(-((d2c / (sc*sc) + d2n / (sn*sn)) + (dz*dz) / (sz*sz)))
+ *   sum_c += w * c_q.rgb;  sum_w += w
+ * and out.rgb = sum_c / sum_w, out.a = c_p.a.  exp is the library's pinned
+ * fp32 exp (pt_selftest_math fn 1), divisions are IEEE, nothing is fused.  A
+ * hit next to a miss has dz*dz = inf, hence w = 0; two misses have dz = 0.
+ * The centre tap weighs 9/64, so sum_w > 0 for finite input.  The passes
+ * ping-pong between two library-owned images; the source is only read.
+ *
+ * Defaults (pt_denoise_default_params): 5 iterations, sigma_color 16,
+ * sigma_normal 0.35, sigma_depth 0.25, chosen on two 256x256 8-spp frames
+ * against 256-spp frames of the same view (mean squared rgb error, raw ->
+ * denoised): box.obj, default camera, 1.1497e-01 -> 2.0946e-02; the displaced
+ * sphere (5,120 triangles) from (3, 2, 4), 5.3595e-02 -> 2.5855e-02.  The
+ * image is linear radiance with the light (intensity 10) in view and 8-spp
+ * pixel noise of order 1, hence the large sigma_color; a tone-mapped or
+ * darker input wants a smaller one (DESIGN.md §9 has the search). */
+typedef struct pt_denoise_params {
+  int iterations;      /* 1 to 6 */
+  float sigma_color;   /* all three finite and > 0, their squares (and that of */
+  float sigma_normal;  /* sigma_color * 2^-(iterations-1)) finite and non-zero */
+  float sigma_depth;
+} pt_denoise_params;
+int pt_denoise_default_params(pt_denoise_params* out);
+/* The guide ray of pixel (x, y) of a W x H frame: origin and direction.
+ * Pure host function; the device computes the same bits. */
+int pt_guide_ray(const float camera_ubo[16], int width, int height, int x, int y, float o3[3], float d3[3]);
+/* Enqueues the guide image of the current scene, camera and frame size into
+ * a library-owned W x H float4 image (PT_ERR_INVALID without a scene, a
+ * camera or an accumulation image).  A scene with a culled wide tree
+ * (pt_wide_info, PT_OPT_WIDE not 0) is walked by it, rays with a zero
+ * direction component by the exact walk; other scenes by the exact walk, from
+ * LDS when PT_OPT_SCENE_IN_LDS puts them there. */
+int pt_render_guide(pt_context* ctx);
+/* The guide image in device memory, or null when there is none for the
+ * current inputs: a scene upload, a camera that differs (pt_set_camera,
+ * pt_progressive_camera) and a change of size (pt_resize_and_clear,
+ * pt_bind_accum) invalidate it. */
+void* pt_guide_device_ptr(pt_context* ctx);
+/* Waits for the guide and copies its W*H*4 floats. */
+int pt_read_guide(pt_context* ctx, float* out, size_t n_floats);
+/* Enqueues the filter, one launch per pass, on the context's stream, after
+ * rendering the guide if there is none for the current inputs.  params null:
+ * the defaults.  src_device null: the accumulation image, else W*H float4 in
+ * device memory (16-B aligned).  dst_device null: a library-owned image
+ * (pt_read_denoised), else W*H float4 in device memory, distinct from the
+ * source.  PT_ERR_INVALID for bad parameters, without a scene, a camera or an
+ * accumulation image (its size is the frame's). */
+int pt_denoise(pt_context* ctx, const pt_denoise_params* params, const void* src_device, void* dst_device);
+/* Waits for the last pt_denoise into the library-owned image and copies it. */
+int pt_read_denoised(pt_context* ctx, float* rgba, size_t n_floats);
+/* The same filter on the host (the same header code the kernels compile):
+ * rgba, guide and out hold W*H*4 floats; params null: the defaults.  Pure
+ * host function; bit-identical to pt_denoise. */
+int pt_denoise_host(const float* rgba, const float* guide, int width, int height, const pt_denoise_params* params,
+                    float* out);
 
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile
@@ -463,6 +551,12 @@ int pt_dist_finalize(pt_context* ctx);
  * never measured.  0 = off (every item at PT_OPT_SAMPLE_LANES).  Output is
  * identical for every value. */
 #define PT_OPT_MIXED_LANES 22
+/* PT_OPT_DENOISE_LDS: 1 (default) = pt_denoise's passes at tap spacing 1 and
+ * 2 stage their 16x16 tile and its halo in LDS; 0 = every tap is read from
+ * the images.  At 1080p the staged passes measured 0.1170 / 0.1095 ms against
+ * 0.1210 / 0.1124 ms, the 5-pass call 0.6430 against 0.6502 ms
+ * (profiles/denoise/timing_1080p.json).  Output is identical. */
+#define PT_OPT_DENOISE_LDS 23
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
