@@ -30,6 +30,8 @@
 #include "scene/camera.h"
 #include "scene/light.h"
 #include "scene/obj_loader.h"
+#include "scene/small_sweep.h"
+#include "scene/threaded_bvh.h"
 #include "scene/wide_bvh.h"
 
 namespace {
@@ -53,115 +55,23 @@ void dev_free(T*& p) {
   p = nullptr;
 }
 
-// Threads the reference node array: renumbers nodes in the order the
-// reference's DFS visits them (right child first) and records, for each, the
-// node visited after its subtree.  Fails on anything that is not a tree.
-int thread_bvh(const pt_bvh_node* nodes, size_t n, bool int_bits, size_t n_tris, std::vector<float4>* out) {
-  if (n == 0 || n > 0x7fffffffull) return fail(PT_ERR_SCENE, "BVH has no nodes or too many");
-  std::vector<int32_t> left(n), right(n);
-  for (size_t i = 0; i < n; ++i) {
-    float lw = nodes[i].min_bounds[3], rw = nodes[i].max_bounds[3];
-    int32_t l, r;
-    if (int_bits) {
-      memcpy(&l, &lw, 4);
-      memcpy(&r, &rw, 4);
-    } else {
-      // int(node.minBounds.w) (raytrace_comp.comp:173-174): only exact
-      // below 2^24, so refuse anything the float cannot hold exactly.
-      if (!(lw == floorf(lw)) || !(rw == floorf(rw)) || fabsf(lw) >= 16777216.0f || fabsf(rw) >= 16777216.0f)
-        return fail(PT_ERR_SCENE, "float-encoded BVH index is not an exact integer below 2^24 (node " +
-                                      std::to_string(i) + "); rebuild with PT_NODES_INT_BITS");
-      l = (int32_t)lw;
-      r = (int32_t)rw;
-    }
-    left[i] = l;
-    right[i] = r;
-    if (l == -1) {
-      if (r < 0 || (size_t)r >= n_tris)
-        return fail(PT_ERR_SCENE, "leaf " + std::to_string(i) + " has triangle index out of range");
-    } else if (l < 0 || (size_t)l >= n || r < 0 || (size_t)r >= n) {
-      return fail(PT_ERR_SCENE, "node " + std::to_string(i) + " has child index out of range");
-    }
-  }
-  std::vector<int32_t> order;
-  order.reserve(n);
-  std::vector<int32_t> newidx(n, -1);
-  std::vector<int32_t> stack;
-  stack.push_back(0);
-  while (!stack.empty()) {
-    const int32_t v = stack.back();
-    stack.pop_back();
-    if (newidx[v] != -1) return fail(PT_ERR_SCENE, "BVH node reachable twice (not a tree)");
-    newidx[v] = (int32_t)order.size();
-    order.push_back(v);
-    if (left[v] != -1) {
-      stack.push_back(left[v]);    // :198  push left
-      stack.push_back(right[v]);   // :199  push right -> popped first
-    }
-  }
-  const size_t m = order.size();
-  std::vector<int32_t> size(n, 1);
-  for (size_t k = m; k-- > 0;) {
-    const int32_t v = order[k];
-    if (left[v] != -1) size[v] = 1 + size[left[v]] + size[right[v]];
-  }
-  // A child whose bounds are bitwise its parent's is hit whenever it is
-  // visited (it is only visited after its parent was hit by the same ray, and
-  // the slab test is a pure function of ray and bounds): flag it in bit 31 of
-  // `skip` so the kernel can skip recomputing the test.
-  std::vector<int32_t> parent(n, -1);
-  for (size_t k = 0; k < m; ++k) {
-    const int32_t v = order[k];
-    if (left[v] != -1) parent[left[v]] = parent[right[v]] = v;
-  }
-  auto same_bounds = [&](int32_t a, int32_t b) {
-    return memcmp(nodes[a].min_bounds, nodes[b].min_bounds, 12) == 0 &&
-           memcmp(nodes[a].max_bounds, nodes[b].max_bounds, 12) == 0;
-  };
-  out->assign(2 * m, make_float4(0, 0, 0, 0));
-  for (size_t k = 0; k < m; ++k) {
-    const int32_t v = order[k];
-    const pt_bvh_node& nd = nodes[v];
-    const bool implied = parent[v] >= 0 && same_bounds(v, parent[v]);
-    const int32_t skip = (int32_t)(((uint32_t)k + (uint32_t)size[v]) | (implied ? 0x80000000u : 0u));
-    const int32_t tri = left[v] == -1 ? right[v] : -1;
-    float fs, ft;
-    memcpy(&fs, &skip, 4);
-    memcpy(&ft, &tri, 4);
-    (*out)[2 * k] = make_float4(nd.min_bounds[0], nd.min_bounds[1], nd.min_bounds[2], fs);
-    (*out)[2 * k + 1] = make_float4(nd.max_bounds[0], nd.max_bounds[1], nd.max_bounds[2], ft);
-  }
-  return PT_OK;
-}
+// The sweep walk's enabling bound (PT_OPT_SMALL_SWEEP -1, the default): a
+// scene that has a sweep table (at most pt::kSweepMaxLeaves triangles) is
+// walked by it when the table holds at most this many distinct boxes -- the
+// largest size at which the sweep did not lose to the threaded walk by the
+// mean and by the fastest launch alike (profiles/sweep/sweep_sizes.log,
+// 512x512 8 spp, on / off by mean and by minimum: 7 boxes 0.79-0.94 and
+// 0.78-0.97, 15 boxes 0.98 and 0.96; 21 boxes 0.79 by the mean but 1.04 by
+// the minimum, the threaded walk's launches scattering widely there; 31
+// boxes 1.11-1.17 and 1.18-1.22, 63 boxes 1.68 and 1.72).  The slab tests set
+// the cost: 32 leaves over 31 boxes lose like 16 leaves over 31.
+constexpr int kSweepAutoBoxes = 15;
 
-// Drops internal nodes flagged as implied-hit from a threaded array: such a
-// node does nothing but continue at k+1, so every link into it can point at
-// the next kept node instead.  The kept nodes' visit sequence (and every slab
-// and triangle test) is unchanged; only the pass-through visits disappear.
-// Used by the fast kernel; stats mode keeps the full array so it still counts
-// the reference's node visits.
-void collapse_implied(const std::vector<float4>& full, std::vector<float4>* out) {
-  const size_t m = full.size() / 2;
-  auto raw_skip = [&](size_t k) { int32_t s; memcpy(&s, &full[2 * k].w, 4); return s; };
-  auto tri_of = [&](size_t k) { int32_t t; memcpy(&t, &full[2 * k + 1].w, 4); return t; };
-  auto dropped = [&](size_t k) { return raw_skip(k) < 0 && tri_of(k) < 0; };
-  std::vector<int32_t> nxt(m + 1);
-  int32_t kept = 0;
-  for (size_t k = 0; k < m; ++k)
-    if (!dropped(k)) ++kept;
-  nxt[m] = kept;
-  for (size_t k = m; k-- > 0;) nxt[k] = dropped(k) ? nxt[k + 1] : --kept;
-  out->clear();
-  out->reserve(2 * (size_t)nxt[m]);
-  for (size_t k = 0; k < m; ++k) {
-    if (dropped(k)) continue;
-    const int32_t raw = raw_skip(k);
-    const int32_t skip = (int32_t)((uint32_t)nxt[raw & 0x7fffffff] | ((uint32_t)raw & 0x80000000u));
-    float4 a = full[2 * k];
-    memcpy(&a.w, &skip, 4);
-    out->push_back(a);
-    out->push_back(full[2 * k + 1]);
-  }
+// The threaded arrays of the exact walk (scene/threaded_bvh.h) as float4 pairs.
+std::vector<float4> as_float4(const std::vector<float>& f) {
+  std::vector<float4> v(f.size() / 4);
+  if (!v.empty()) memcpy(v.data(), f.data(), v.size() * sizeof(float4));
+  return v;
 }
 
 // ---- primary-ray bundle culling -----------------------------
@@ -321,6 +231,8 @@ struct pt_context {
   float4* d_nodes = nullptr;        // threaded, implied internal nodes collapsed (fast kernel)
   int n_nodes = 0;
   float4* d_nodes_full = nullptr;   // threaded, every reference node (stats mode)
+  float4* d_sweep = nullptr;        // the sweep table of a tiny scene (scene/small_sweep.h), or null
+  int sweep_boxes = 0, sweep_leaves = 0;
   // culled wide walk (wide_walk.h): nodes, triangle records by rank, rank ->
   // slot, per-lane stack overflow areas (grown on demand)
   float4* d_wide = nullptr;
@@ -374,6 +286,7 @@ struct pt_context {
   int opt_wf_paths = 0;       // PT_OPT_WF_PATHS (0 = 2^27)
   long long wf_fail = 0;      // wavefront paths whose allocation failed (0: none)
   int opt_count = 0;          // PT_OPT_COUNT_TRACED
+  int opt_small_sweep = -1;   // PT_OPT_SMALL_SWEEP: -1 auto (kSweepAutoBoxes), 0 off, 1 whenever the scene has a table
   int opt_wide_build = 1;     // PT_OPT_WIDE_BUILD (pt::WideBuild; read at upload)
   int opt_wf_streams = 1;     // PT_OPT_WF_STREAMS (2 measured slower: 10M cloud +9 %, sphere -0.8 %)
   hipStream_t wf_stream2 = nullptr;           // the wavefront pipeline's second half (created on first use)
@@ -407,6 +320,7 @@ struct pt_context {
   const void* culled_buf = nullptr;
   long long render_slots = -1;                 // resident LDS render workgroups (mixed lanes' budget)
   size_t render_slots_lds = 0;                 // ... at this many bytes of staged scene
+  int render_slots_sweep = 0;                  // ... of this sweep-walk kernel (0: the threaded walk's)
   size_t culled_org_off = 0;   // h_items / d_items: where the culled items' first pixels start
   size_t live_org_off = 0;     // ... and the live items' ones
   std::vector<int> h_items;
@@ -1087,6 +1001,14 @@ struct Launched {
   ptd::RenderParams p;
   bool lds = false, cnt = false, valid = false;
 };
+// Whether the context's launches walk the scene's sweep table (PT_OPT_SMALL_SWEEP): the
+// option admits the scene, and the launch is the plain LDS-staged path-recursive kernel
+// (a scene with a table always fits in LDS; the auto kernel choice is path-recursive for it).
+bool sweep_in_force(const pt_context* c) {
+  const bool wanted =
+      c->d_sweep && (c->opt_small_sweep == 1 || (c->opt_small_sweep < 0 && c->sweep_boxes <= kSweepAutoBoxes));
+  return wanted && c->opt_scene_lds != 0 && c->opt_kernel != 3 && !c->stats_mode && c->opt_count == 0;
+}
 // One path-recursive launch of prepared parameters, timed as render_impl
 // times its launches (PT_OPT_LAUNCH_TIMING).
 int relaunch(pt_context* c, const ptd::RenderParams& p, bool lds, bool cnt) {
@@ -1211,6 +1133,13 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   const bool wf = c->opt_kernel == 3 || (c->opt_kernel == 0 && !lds && !c->stats_mode && wf_auto);
   if (wf && c->stats_mode) return fail(PT_ERR_UNSUPPORTED, "stats mode runs the path-recursive kernel only");
   const bool cnt = c->opt_count != 0 && !c->stats_mode;
+  // the sweep walk (PT_OPT_SMALL_SWEEP): the plain LDS kernel of a scene with a table
+  const bool sweep = lds && !wf && !cnt && sweep_in_force(c);
+  if (sweep) {
+    p.sweep = c->d_sweep;
+    p.sweep_boxes = c->sweep_boxes;
+    p.sweep_leaves = c->sweep_leaves;
+  }
   // PT_OPT_ITEM_ORDER auto: scan order for a whole frame on the path-recursive
   // kernel (box 1080p8 at 4 lanes, one context: 0.2403 against 0.2463 ms
   // heaviest first, profiles/r06b), heaviest first on a share of the frame
@@ -1234,9 +1163,11 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
     if (c->opt_mixed != 0 && !wf && lds && c->nranks == 1 && !pack_out && (p.spl > 1 || c->opt_mixed < 0) &&
         !cnt) {
       mixed = true;
-      const size_t lds_b = ptd::scene_lds_bytes(p);
-      if (c->render_slots < 0 || c->render_slots_lds != lds_b) {
-        c->render_slots = ptd::render_slots(lds_b);
+      const size_t lds_b = sweep ? ptd::sweep_lds_bytes(p) : ptd::scene_lds_bytes(p);
+      const int sweep_kind = !sweep ? 0 : p.sweep_boxes > 32 ? 2 : 1;
+      if (c->render_slots < 0 || c->render_slots_lds != lds_b || c->render_slots_sweep != sweep_kind) {
+        c->render_slots_sweep = sweep_kind;
+        c->render_slots = ptd::render_slots(lds_b, sweep_kind);
         c->render_slots_lds = lds_b;
       }
       // auto: every item at PT_OPT_SAMPLE_LANES until the block costs are
@@ -1500,6 +1431,8 @@ int pt_destroy(pt_context* c) {
   c->uses.clear();
   dev_free(c->d_nodes);
   dev_free(c->d_nodes_full);
+  dev_free(c->d_sweep);
+  c->sweep_boxes = c->sweep_leaves = 0;
   dev_free(c->d_wide);
   dev_free(c->d_wide_q);
   dev_free(c->d_wide_leafbox);
@@ -1578,10 +1511,17 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   const size_t nv = n_vertex_floats / 3;
   for (size_t i = 0; i < n_indices; ++i)
     if (indices[i] >= nv) return fail(PT_ERR_SCENE, "vertex index out of range at " + std::to_string(i));
-  std::vector<float4> threaded, collapsed;
-  int rc = thread_bvh(nodes, n_nodes, (flags & PT_NODES_INT_BITS) != 0, n_indices / 3, &threaded);
-  if (rc) return rc;
-  collapse_implied(threaded, &collapsed);
+  std::vector<float> threaded_f, collapsed_f;
+  const std::string not_tree =
+      pt::thread_bvh((const float*)nodes, n_nodes, (flags & PT_NODES_INT_BITS) != 0, n_indices / 3, &threaded_f);
+  if (!not_tree.empty()) return fail(PT_ERR_SCENE, not_tree);
+  pt::collapse_implied(threaded_f, &collapsed_f);
+  std::vector<float4> threaded = as_float4(threaded_f), collapsed = as_float4(collapsed_f);
+  // tiny scenes: the sweep table of the LDS render kernel (PT_OPT_SMALL_SWEEP)
+  pt::SmallSweep sweep;
+  // (a node array with an unreachable node has fewer leaves than triangles: no table)
+  const bool has_sweep = pt::build_small_sweep(collapsed_f.data(), collapsed_f.size() / 8, &sweep) &&
+                         (size_t)sweep.n_leaves == n_indices / 3;
   pt::WideBVH wide;
   const std::string wide_reason =
       pt::build_wide_bvh((const float*)nodes, n_nodes, (flags & PT_NODES_INT_BITS) != 0, vertices, n_vertex_floats,
@@ -1592,6 +1532,8 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   { const int rc_ = quiesce(c); if (rc_) return rc_; }
   dev_free(c->d_nodes);
   dev_free(c->d_nodes_full);
+  dev_free(c->d_sweep);
+  c->sweep_boxes = c->sweep_leaves = 0;
   dev_free(c->d_wide);
   dev_free(c->d_wide_q);
   dev_free(c->d_wide_leafbox);
@@ -1628,6 +1570,12 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   PT_HIP(hipMemcpyAsync(st.v, vertices, n_vertex_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
   PT_HIP(hipMemcpyAsync(st.i, indices, n_indices * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   PT_HIP(ptd::launch_setup_tris(st.v, st.i, T, c->d_tris, c->stream));
+  const std::vector<float> sweep_table = sweep.pack();   // lives until the copy has run (synchronized below)
+  if (has_sweep) {
+    PT_HIP(hipMalloc((void**)&c->d_sweep, sweep_table.size() * sizeof(float)));
+    PT_HIP(hipMemcpyAsync(c->d_sweep, sweep_table.data(), sweep_table.size() * sizeof(float), hipMemcpyHostToDevice,
+                          c->stream));
+  }
   std::vector<int> rank_of_host(wide_reason.empty() ? (size_t)T : 0);
   if (wide_reason.empty()) {
     PT_HIP(hipMalloc((void**)&c->d_wide, wide.nodes.size() * sizeof(float)));
@@ -1656,6 +1604,8 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->n_nodes = (int)(collapsed.size() / 2) - 1;
   c->n_nodes_full = (int)(threaded.size() / 2) - 1;
   c->n_tris = T;
+  c->sweep_boxes = has_sweep ? sweep.n_boxes : 0;
+  c->sweep_leaves = has_sweep ? sweep.n_leaves : 0;
   memcpy(c->root_lo, lo, sizeof lo);
   memcpy(c->root_hi, hi, sizeof hi);
   c->has_scene = true;
@@ -2211,6 +2161,10 @@ int pt_set_option(pt_context* c, int key, int value) {
       if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_DENOISE_LDS takes 0 or 1");
       c->opt_denoise_lds = value;
       return PT_OK;
+    case PT_OPT_SMALL_SWEEP:
+      if (value < -1 || value > 1) return fail(PT_ERR_INVALID, "PT_OPT_SMALL_SWEEP takes -1 (auto), 0 or 1");
+      c->opt_small_sweep = value;
+      return PT_OK;
     case PT_OPT_GROUP_EXCHANGE:
     case PT_OPT_GROUP_CHECK:
       return fail(PT_ERR_UNSUPPORTED, "option " + std::to_string(key) + ": multi-device contexts only (pt_create_multi)");
@@ -2341,6 +2295,15 @@ int pt_wide_info(pt_context* c, int info[2]) {
   info[0] = c->n_wide;
   info[1] = c->n_wide ? c->wide_stack : 0;
   if (!c->n_wide) g_err = c->wide_reason;
+  return PT_OK;
+}
+
+int pt_sweep_info(pt_context* c, int* boxes, int* leaves) {
+  if (c && c->group) return ptg::sweep_info(c->group, boxes, leaves);
+  if (!c || !boxes || !leaves) return fail(PT_ERR_INVALID, "null argument");
+  const bool on = sweep_in_force(c);
+  *boxes = on ? c->sweep_boxes : 0;
+  *leaves = on ? c->sweep_leaves : 0;
   return PT_OK;
 }
 

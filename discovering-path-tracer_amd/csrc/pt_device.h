@@ -94,6 +94,10 @@ struct RenderParams {
   int wide_refill;          // PT_OPT_WF_REFILL: idle lanes at which a wave of the wide trace kernel refills
   const float4* nodes;
   const float4* tris;
+  // the sweep table of a tiny scene (sweep_walk.h SweepTable, PT_OPT_SMALL_SWEEP)
+  // or null: render_kernel<false, true, false> then walks it instead of nodes
+  const float4* sweep = nullptr;
+  int sweep_boxes = 0, sweep_leaves = 0;
   const LightDev* lights;
   float4* accum;
   // [0..3] rays, nodes, leaf tests, samples (stats mode); [4..8] closest walks,
@@ -176,6 +180,8 @@ constexpr size_t kMaxSceneLds = 48 * 1024;
 inline size_t scene_lds_bytes(const RenderParams& p) {
   return ((size_t)2 * p.n_nodes + (size_t)3 * p.n_tris) * 16;
 }
+// ... and what the sweep walk stages: the triangle records, by leaf
+inline size_t sweep_lds_bytes(const RenderParams& p) { return (size_t)3 * p.sweep_leaves * 16; }
 // cnt: the fast kernel with traced-work counters (PT_OPT_COUNT_TRACED)
 hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipStream_t stream, bool cnt = false);
 // Wavefront pipeline (PT_OPT_KERNEL 3): one path per (pixel, sample) held in
@@ -228,7 +234,7 @@ hipError_t launch_atrous(const float4* src, const float4* guide, float4* dst, in
 // lanes of the wide walk's persistent grid on this device (overflow areas to allocate)
 long long wide_trace_lanes();
 // workgroups of the LDS-staged render kernel resident on this device at once
-long long render_slots(size_t lds_bytes);
+long long render_slots(size_t lds_bytes, int sweep = 0);   // sweep: of its sweep-walk variant (1: up to 32 boxes, 2: more)
 // triangle records by rank: dst[r] = tris[tri_of[r]]
 hipError_t launch_gather_tris(const float4* tris, const int* tri_of, int n, float4* dst, hipStream_t stream);
 hipError_t launch_math(int fn, const float* x, float* y, size_t n, hipStream_t stream);

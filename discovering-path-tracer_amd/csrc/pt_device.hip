@@ -28,6 +28,7 @@
 #include "pt_denoise.h"
 #include "pt_isect.h"
 #include "wide_walk.h"
+#include "sweep_walk.h"
 #include "pt_math.h"
 
 #pragma clang fp contract(off)
@@ -311,6 +312,35 @@ __device__ __forceinline__ void walk_pair(const RenderParams& P, bool has_s, v3 
   hit->tri = bt;
 }
 
+// The walks of a tiny scene as a box sweep (sweep_walk.h; PT_OPT_SMALL_SWEEP):
+// P.tris holds the LDS-staged triangle records by leaf, and a hit's index is
+// its leaf's (P.hit_tris is the same array).  A wave none of whose rays passes
+// the root box has no candidates: it skips the leaf masks too.
+// M: the box mask, 32 bits for up to 32 distinct boxes, else 64.
+template <class M>
+__device__ Hit sweep_trace_closest(const RenderParams& P, v3 o, v3 d) {
+  const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
+  const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
+  Hit r;
+  r.t = 1e30f;
+  r.tri = -1;
+  bool none;
+  const M sb = sweep_mask<M>(o, inv, tb, &none);
+  if (none) return r;
+  sweep_closest(o, d, sweep_leaves(sb, tb), P.tris, &r.t, &r.tri);
+  return r;
+}
+
+template <class M>
+__device__ bool sweep_trace_occluded(const RenderParams& P, v3 o, v3 d, float limit) {
+  const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
+  const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
+  bool none;
+  const M sb = sweep_mask<M>(o, inv, tb, &none);
+  if (none) return false;
+  return sweep_occluded(o, d, limit, sweep_leaves(sb, tb), P.tris);
+}
+
 // Lights are read-only for the whole launch and indexed by a wave-uniform
 // loop counter: reading them through the constant address space lets the
 // compiler use scalar loads (scalar cache, one load per wave) instead of a
@@ -419,7 +449,15 @@ __device__ __forceinline__ void add_ctr(Ctr& a, const Ctr& b) {
 #ifndef PT_PARK_FUSED
 #define PT_PARK_FUSED 1
 #endif
-constexpr int kPark = (PT_PARK || PT_PARK_FUSED) ? 12 : 0;   // floats of path state parked in LDS around a walk
+// ... and with the sweep walk (PT_OPT_SMALL_SWEEP), measured on its own with
+// PT_RENDER_MIN_BLOCKS_SWEEP (box 1080p8, 200 frames, four runs each,
+// profiles/sweep/ab_occupancy.log): parked at 5 / 6 / 7 blocks 0.1721-0.1724 /
+// 0.1601-0.1625 / 0.1662-0.1734 ms, not parked 0.1706-0.1718 / 0.1636-0.1661 /
+// 0.1675-0.1719: parked at 6 blocks, as the threaded walk.
+#ifndef PT_PARK_SWEEP
+#define PT_PARK_SWEEP PT_PARK
+#endif
+constexpr int kPark = (PT_PARK || PT_PARK_FUSED || PT_PARK_SWEEP) ? 12 : 0;   // floats of path state parked in LDS around a walk
 __device__ __forceinline__ void park3(float* pk, int i, v3 v) {
   pk[i * 64] = v.x;
   pk[(i + 1) * 64] = v.y;
@@ -452,10 +490,28 @@ __device__ __forceinline__ v3 unpark3(const float* pk, int i) {
   } while (0)
 
 // pathTrace (:300-418)
-template <bool STATS, bool PF, bool CNT = false>
+// SWEEP: the walks are the box sweep's (no candidate queue: the parked state
+// starts at cand), 1 with a 32-bit box mask, 2 with a 64-bit one.
+template <bool STATS, bool PF, bool CNT = false, int SWEEP = 0>
 __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr& c, int* cand) {
-  constexpr bool PARK = PT_PARK && !STATS && !PF;
-  float* pk = (float*)(cand + kCand * 64);
+  constexpr bool PARK = (SWEEP ? PT_PARK_SWEEP : PT_PARK) && !STATS && !PF;
+  float* pk = (float*)(cand + (SWEEP ? 0 : kCand) * 64);
+  auto closest = [&](v3 o, v3 d, Ctr& cc) {
+    if constexpr (SWEEP == 2)
+      return sweep_trace_closest<uint64_t>(P, o, d);
+    else if constexpr (SWEEP == 1)
+      return sweep_trace_closest<uint32_t>(P, o, d);
+    else
+      return trace_closest<STATS, PF, false, CNT>(P, o, d, cc, cand);
+  };
+  auto shadowed = [&](v3 o, v3 d, float limit) {
+    if constexpr (SWEEP == 2)
+      return sweep_trace_occluded<uint64_t>(P, o, d, limit);
+    else if constexpr (SWEEP == 1)
+      return sweep_trace_occluded<uint32_t>(P, o, d, limit);
+    else
+      return occluded<STATS, PF, CNT>(P, o, d, limit, c);
+  };
   const float OFFSET = 0.001f;
   v3 thr = mk(1.0f, 1.0f, 1.0f);
   v3 rad = mk(0.0f, 0.0f, 0.0f);
@@ -473,7 +529,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
     float tl;
     if (intersect_area_light(ro, rd, L, &tl)) {
       if (!have_h0) {
-        h0 = trace_closest<STATS, PF, false, CNT>(P, ro, rd, cp0, cand);
+        h0 = closest(ro, rd, cp0);
         have_h0 = true;
       }
       if (STATS) add_ctr(c, c0);
@@ -485,13 +541,13 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
     Hit h;
     if (depth == 0) {
       if (!have_h0) {
-        h0 = trace_closest<STATS, PF, false, CNT>(P, ro, rd, cp0, cand);
+        h0 = closest(ro, rd, cp0);
         have_h0 = true;
       }
       if (STATS) add_ctr(c, c0);
       h = h0;
     } else {
-      PT_WALK2(PARK, h = (trace_closest<STATS, PF, false, CNT>(P, ro, rd, c, cand)));
+      PT_WALK2(PARK, h = closest(ro, rd, c));
     }
     if (h.tri < 0) {
       rad = add(rad, mul(thr, mk(0.0f, 0.0f, 0.0f)));  // background (:336)
@@ -509,7 +565,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
       const float diff = fmax_(dot(hn, ld), 0.0f);
       const float dist = length(sub(lp, hp));
       bool vis = !STATS && !shadow_needed(L, diff);
-      if (!vis) PT_WALK4(PARK, vis = !(occluded<STATS, PF, CNT>(P, add(hp, muls(hn, OFFSET)), ld, dist - OFFSET, c)));
+      if (!vis) PT_WALK4(PARK, vis = !shadowed(add(hp, muls(hn, OFFSET)), ld, dist - OFFSET));
       if (vis) {
         const float d2 = dist * dist;
         const v3 contrib = muls(muls(mk(L.inten[0], L.inten[1], L.inten[2]), diff), rcp_(fmax_(d2, 0.01f)));
@@ -525,7 +581,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
     v3 sd = sample_sphere(&rng);
     for (int k = 0; k < P.sss_bounces; ++k) {
       Hit sh;
-      PT_WALK4(PARK, sh = (trace_closest<STATS, PF, false, CNT>(P, so, sd, c, cand)));
+      PT_WALK4(PARK, sh = closest(so, sd, c));
       if (sh.tri < 0) break;
       const float travel = sh.t;
       const v3 cp = add(so, muls(sd, travel));
@@ -538,7 +594,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
         const float ediff = fmax_(dot(sn, ed), 0.0f);
         const float edist = length(sub(lp, cp));
         bool vis = !STATS && !shadow_needed(L, ediff);
-        if (!vis) PT_WALK4(PARK, vis = !(occluded<STATS, PF, CNT>(P, add(cp, muls(sn, OFFSET)), ed, edist - OFFSET, c)));
+        if (!vis) PT_WALK4(PARK, vis = !shadowed(add(cp, muls(sn, OFFSET)), ed, edist - OFFSET));
         if (vis) {
           const float d2 = edist * edist;
           sl = add(sl, muls(mul(muls(sss_albedo, ediff), mk(L.inten[0], L.inten[1], L.inten[2])),
@@ -849,14 +905,21 @@ __device__ unsigned long long g_wg_trace[kWgTraceCap][4];
 // LDS=true stages the whole scene (threaded nodes + triangle records) in LDS
 // once per workgroup; chosen by the host for scenes of at most a few tens of
 // KB (box.obj is 1.3 KB), where every lane re-reads the same few nodes.
-template <bool STATS, bool LDS, bool CNT = false>
+// SWEEP (LDS, no counters): a tiny scene's walks are the box sweep over
+// P.sweep (1: up to 32 distinct boxes, 2: more); only the triangle records
+// are staged, by leaf.
+template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0>
 #ifndef PT_RENDER_MIN_BLOCKS
 #define PT_RENDER_MIN_BLOCKS 5
 #endif
 #ifndef PT_RENDER_MIN_BLOCKS_LDS
 #define PT_RENDER_MIN_BLOCKS_LDS (PT_PARK ? 6 : PT_RENDER_MIN_BLOCKS)
 #endif
-__global__ __launch_bounds__(256, LDS && !STATS ? PT_RENDER_MIN_BLOCKS_LDS : PT_RENDER_MIN_BLOCKS) void render_kernel(
+#ifndef PT_RENDER_MIN_BLOCKS_SWEEP
+#define PT_RENDER_MIN_BLOCKS_SWEEP PT_RENDER_MIN_BLOCKS_LDS
+#endif
+__global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
+                                  : LDS && !STATS ? PT_RENDER_MIN_BLOCKS_LDS : PT_RENDER_MIN_BLOCKS) void render_kernel(
     RenderParams P) {
   const int tid = (int)threadIdx.x;
   // Work mapping.  A 16x16 pixel tile (the partition unit) is split into
@@ -907,9 +970,11 @@ __global__ __launch_bounds__(256, LDS && !STATS ? PT_RENDER_MIN_BLOCKS_LDS : PT_
   // per wave: the leaf-candidate queue, then a [slot][lane] area that holds
   // the path state parked during walks (kPark floats) and, between samples,
   // the colour hand-off (4 floats) -- never both at once
-  __shared__ int cand_buf[4][kCand + (kPark > 4 ? kPark : 4)][64];
+  static_assert(!SWEEP || (LDS && !STATS && !CNT), "the sweep walk is the plain LDS kernel's");
+  constexpr int kQueue = SWEEP ? 0 : kCand;   // the sweep walk queues nothing
+  __shared__ int cand_buf[4][kQueue + (kPark > 4 ? kPark : 4)][64];
   int* cand = &cand_buf[wave][0][lane];
-  float* colw = (float*)&cand_buf[wave][kCand][0];   // colour hand-off, [channel][lane]
+  float* colw = (float*)&cand_buf[wave][kQueue][0];   // colour hand-off, [channel][lane]
   const int q = wave * (64 / spl) + lane / spl;       // pixel within the workgroup
   const int j = lane % spl;                           // sample slot
   const int px = gx0 + q % 16;
@@ -964,7 +1029,16 @@ __global__ __launch_bounds__(256, LDS && !STATS ? PT_RENDER_MIN_BLOCKS_LDS : PT_
     emit_lane(P, active, pix, q, acc, spl, j);
     return;
   }
-  if (LDS) {
+  if (SWEEP) {
+    extern __shared__ float4 lds_scene[];
+    const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
+    const int* slot = sweep_slots(tb);
+    const int nt = 3 * P.sweep_leaves;
+    for (int i = tid; i < nt; i += 256) lds_scene[i] = P.tris[3 * slot[i / 3] + i % 3];
+    __syncthreads();
+    P.tris = lds_scene;
+    P.hit_tris = P.tris;   // hits are leaf indices
+  } else if (LDS) {
     extern __shared__ float4 lds_scene[];
     const int nn = 2 * P.n_nodes, nt = 3 * P.n_tris;
     for (int i = tid; i < nn; i += 256) lds_scene[i] = P.nodes[i];
@@ -1020,7 +1094,7 @@ __global__ __launch_bounds__(256, LDS && !STATS ? PT_RENDER_MIN_BLOCKS_LDS : PT_
       v3 col;
       if (CNT) c.prim++;
       if (STATS || LDS)
-        col = path_trace<STATS, !LDS, CNT>(P, origin, dir, seed, c, cand);
+        col = path_trace<STATS, !LDS, CNT, SWEEP>(P, origin, dir, seed, c, cand);
       else
         col = path_trace_fused<PT_REC_PF != 0, CNT>(P, origin, dir, seed, cand, c);
       col4 = make_float4(col.x, col.y, col.z, 1.0f);                      // vec4(color, 1.0)
@@ -2877,10 +2951,16 @@ hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipS
     grid = p.n_items + (px + 256 * kPixPerFill - 1) / (256 * kPixPerFill);
   }
   if (grid > 0x7fffffffll) return hipErrorInvalidValue;
-  const size_t lds = lds_scene ? scene_lds_bytes(p) : 0;
+  // the sweep walk (p.sweep, set by the host for tiny scenes): the plain LDS kernel only
+  const bool sweep = p.sweep && lds_scene && !stats && !cnt;
+  if (sweep && (p.sweep_boxes < 1 || p.sweep_boxes > 64 || p.sweep_leaves < 1 || p.sweep_leaves > 32))
+    return hipErrorInvalidValue;
+  const size_t lds = sweep ? sweep_lds_bytes(p) : lds_scene ? scene_lds_bytes(p) : 0;
   if (lds > kMaxSceneLds) return hipErrorInvalidValue;
   void (*kern)(RenderParams);
-  if (cnt)
+  if (sweep)
+    kern = sweep_wide(p.sweep_boxes) ? render_kernel<false, true, false, 2> : render_kernel<false, true, false, 1>;
+  else if (cnt)
     kern = lds_scene ? render_kernel<false, true, true> : render_kernel<false, false, true>;
   else
     kern = lds_scene ? (stats ? render_kernel<true, true> : render_kernel<false, true>)
@@ -2907,11 +2987,16 @@ hipError_t launch_guide(const RenderParams& p, float4* guide, bool lds_scene, hi
   return hipGetLastError();
 }
 
-long long render_slots(size_t lds_bytes) {
+long long render_slots(size_t lds_bytes, int sweep) {
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_kernel<false, true>, 256, lds_bytes) !=
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &per_cu,
+          sweep == 2   ? render_kernel<false, true, false, 2>
+          : sweep == 1 ? render_kernel<false, true, false, 1>
+                       : render_kernel<false, true>,
+          256, lds_bytes) !=
       hipSuccess)
     return 0;
   return (long long)cus * per_cu;

@@ -50,6 +50,7 @@ int get_stats(pt_group* g, pt_stats* out);
 int reset_stats(pt_group* g);
 int get_traced(pt_group* g, pt_traced* out);
 int wide_info(pt_group* g, int info[2]);
+int sweep_info(pt_group* g, int* boxes, int* leaves);
 int last_launch_ms(pt_group* g, float* ms);
 int launch_times_ms(pt_group* g, float* out, size_t max_n, size_t* n_out);
 int launch_span_ms(pt_group* g, float* ms, size_t* n_out);

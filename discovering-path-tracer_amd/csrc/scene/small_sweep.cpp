@@ -1,0 +1,62 @@
+#include "small_sweep.h"
+
+#include <string.h>
+
+namespace pt {
+
+std::vector<float> SmallSweep::pack() const {
+  const bool wide = n_boxes > 32;   // sweep_walk.h sweep_wide, sweep_need_words
+  const size_t need_words = ((wide ? 2 : 1) * (size_t)n_leaves + 3) & ~(size_t)3;
+  const size_t words = (size_t)8 * n_boxes + need_words + (size_t)n_leaves;
+  std::vector<float> t((words + 3) / 4 * 4, 0.0f);
+  if (n_boxes == 0) return t;
+  memcpy(t.data(), boxes.data(), (size_t)8 * n_boxes * 4);
+  for (int l = 0; l < n_leaves; ++l) {
+    const uint32_t w[2] = {(uint32_t)need[l], (uint32_t)(need[l] >> 32)};
+    memcpy(t.data() + 8 * (size_t)n_boxes + (wide ? 2 : 1) * (size_t)l, w, wide ? 8 : 4);
+  }
+  memcpy(t.data() + 8 * (size_t)n_boxes + need_words, slot.data(), (size_t)n_leaves * 4);
+  return t;
+}
+
+bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, int max_boxes, int max_leaves) {
+  *out = SmallSweep();
+  if (n_kept == 0 || max_boxes > kSweepMaxBoxes || max_leaves > kSweepMaxLeaves) return false;
+  auto skip_of = [&](size_t k) { int32_t s; memcpy(&s, collapsed + 8 * k + 3, 4); return (size_t)(s & 0x7fffffff); };
+  auto tri_of = [&](size_t k) { int32_t t; memcpy(&t, collapsed + 8 * k + 7, 4); return t; };
+  size_t leaves = 0;
+  for (size_t k = 0; k < n_kept; ++k) leaves += tri_of(k) >= 0 ? 1 : 0;
+  if (leaves > (size_t)max_leaves) return false;
+  // distinct boxes by the 24 bytes of min/max, numbered by first appearance:
+  // node 0 is the root, so its box is box 0.  An implied leaf (kept, bit 31)
+  // has the box of a kept ancestor bitwise, hence that ancestor's id.
+  SmallSweep s;
+  std::vector<int> box_id(n_kept);
+  for (size_t k = 0; k < n_kept; ++k) {
+    const float* nd = collapsed + 8 * k;
+    int id = -1;
+    for (int b = 0; b < s.n_boxes && id < 0; ++b)
+      if (memcmp(&s.boxes[8 * (size_t)b], nd, 12) == 0 && memcmp(&s.boxes[8 * (size_t)b + 4], nd + 4, 12) == 0) id = b;
+    if (id < 0) {
+      if (s.n_boxes == max_boxes) return false;
+      id = s.n_boxes++;
+      const float rec[8] = {nd[0], nd[1], nd[2], 0.0f, nd[4], nd[5], nd[6], 0.0f};
+      s.boxes.insert(s.boxes.end(), rec, rec + 8);
+    }
+    box_id[k] = id;
+  }
+  // a is an ancestor of k iff a < k < skip(a) (a leaf's skip is a + 1)
+  for (size_t k = 0; k < n_kept; ++k) {
+    if (tri_of(k) < 0) continue;
+    uint64_t need = 1ull << box_id[k];
+    for (size_t a = 0; a < k; ++a)
+      if (skip_of(a) > k) need |= 1ull << box_id[a];
+    s.need.push_back(need);
+    s.slot.push_back(tri_of(k));
+  }
+  s.n_leaves = (int)s.need.size();
+  *out = s;
+  return true;
+}
+
+}  // namespace pt

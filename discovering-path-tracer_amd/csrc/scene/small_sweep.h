@@ -1,0 +1,36 @@
+// The sweep table the LDS render kernel walks instead of the threaded node
+// array of a tiny scene (scene/threaded_bvh.h builds that array;
+// csrc/sweep_walk.h explains why the sweep returns the threaded walk's hits).
+// Host only: no HIP, usable from tests.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace pt {
+
+// Largest table the sweep walk takes: one bit per leaf in a 32-bit mask and
+// one per distinct box in a 32- or 64-bit mask (sweep_walk.h).  A tree of 32
+// leaves has 63 nodes, so the leaves bound both.
+constexpr int kSweepMaxBoxes = 64;
+constexpr int kSweepMaxLeaves = 32;
+
+struct SmallSweep {
+  std::vector<float> boxes;      // 8 floats per distinct box: {lo.xyz, 0} {hi.xyz, 0}; box 0 is the root's
+  std::vector<uint64_t> need;    // per leaf in kept-node (visit) order: the box bits of the leaf and its ancestors
+  std::vector<int32_t> slot;     // per leaf: its triangle slot
+  int n_boxes = 0, n_leaves = 0;
+  // The device table (sweep_walk.h SweepTable): boxes, need[] (32-bit words
+  // for up to 32 boxes, else 64-bit) padded to whole float4s, slot[].
+  std::vector<float> pack() const;
+};
+
+// Builds the table from a collapsed threaded array (n_kept nodes, no padding
+// node).  false (and an empty table) when the scene has more than max_boxes
+// distinct boxes or max_leaves leaves.
+bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, int max_boxes = kSweepMaxBoxes,
+                       int max_leaves = kSweepMaxLeaves);
+
+}  // namespace pt

@@ -1,0 +1,148 @@
+// sweep_walk.h — the exact walk of a tiny scene as a wave-uniform box sweep
+// (scene/small_sweep.h builds the table; pt_device.hip's LDS render kernel and
+// tests/sweep_check.cpp run these functions).
+//
+// Why it returns the threaded walk's hits bit for bit:
+//   * slab(o, inv, lo, hi) is a pure function of the ray and the 24 bytes of
+//     a box, and takes no tmax: nothing is culled by distance.  So the threaded
+//     walk tests the triangle of a leaf exactly when the leaf's box and every
+//     ancestor's box pass the slab test (an implied node passes with its
+//     parent, whose box it has bitwise), in kept-node index order.
+//   * The table holds each distinct box once.  sweep_mask sets bit b of `sb`
+//     iff box b passes; leaf l is a candidate iff sb holds every bit of
+//     need[l], the OR of the box bits of the leaf and all its ancestors.
+//     `sb` and need[] are 32 bits wide for up to 32 distinct boxes, else 64
+//     (a tree of 32 leaves has at most 63 boxes).
+//   * Candidates are popped from the leaf mask lowest bit first -- the visit
+//     order -- with the same tri_test and the same strict '<'.
+// The sweep loop is wave-uniform: on the device the boxes arrive through the
+// constant address space into scalar registers, with no LDS read and no
+// per-lane address.
+#pragma once
+#include "pt_isect.h"
+
+namespace ptd {
+using namespace ptm;
+
+// The device table of pt::SmallSweep::pack(): n_boxes records of 8 floats
+// {lo.xyz, 0, hi.xyz, 0}, then need[] (one word per leaf, two -- low, high --
+// with more than 32 boxes) padded to a multiple of 4 words, then
+// slot[n_leaves].  32-B aligned.
+struct SweepTable {
+  const float4* boxes;
+  int n_boxes, n_leaves;
+};
+
+// Whole records through the constant address space: a wave-uniform index
+// makes each a scalar load of 8 (4) dwords.
+typedef float SweepBox __attribute__((ext_vector_type(8)));
+typedef uint32_t SweepNeed4 __attribute__((ext_vector_type(4)));
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) SweepBox* SweepBoxP;
+typedef const __attribute__((address_space(4))) SweepNeed4* SweepNeedP;
+#else
+typedef const SweepBox* SweepBoxP;
+typedef const SweepNeed4* SweepNeedP;
+#endif
+PT_FN bool sweep_wide(int n_boxes) { return n_boxes > 32; }
+PT_FN int sweep_need_words(int n_boxes, int n_leaves) { return ((sweep_wide(n_boxes) ? 2 : 1) * n_leaves + 3) & ~3; }
+PT_FN SweepBoxP sweep_boxes(const SweepTable& t) { return (SweepBoxP)t.boxes; }
+PT_FN SweepNeedP sweep_need(const SweepTable& t) { return (SweepNeedP)(t.boxes + 2 * t.n_boxes); }
+PT_FN const int* sweep_slots(const SweepTable& t) {
+  return (const int*)(t.boxes + 2 * t.n_boxes) + sweep_need_words(t.n_boxes, t.n_leaves);
+}
+PT_FN bool sweep_slab(v3 o, v3 inv, SweepBox r) {
+  return slab(o, inv, make_float4(r[0], r[1], r[2], r[3]), make_float4(r[4], r[5], r[6], r[7]));
+}
+
+// Boxes per trip of the sweep loop (their scalar loads are issued together).
+#ifndef PT_SWEEP_UNROLL
+#define PT_SWEEP_UNROLL 4
+#endif
+
+// Bit b set iff distinct box b passes the slab test.  Box 0 is the root's and
+// every need mask holds bit 0: when no ray at hand passes it (no lane of the
+// wave on the device) the other boxes are not tested and *none is set: the
+// walk has no candidate.  M: uint32_t, or uint64_t for a table of more than
+// 32 boxes.
+template <class M>
+PT_FN M sweep_mask(v3 o, v3 inv, const SweepTable& t, bool* none) {
+  const SweepBoxP B = sweep_boxes(t);
+  const bool root = sweep_slab(o, inv, B[0]);
+#if defined(__HIP_DEVICE_COMPILE__)
+  *none = __builtin_amdgcn_ballot_w64(root) == 0;
+#else
+  *none = !root;
+#endif
+  if (*none) return 0;
+  M sb = root ? 1 : 0;
+  const int nb = t.n_boxes;
+#pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_UNROLL)
+  for (int b = 1; b < nb; ++b) sb |= sweep_slab(o, inv, B[b]) ? (M)1 << b : (M)0;
+  return sb;
+}
+
+// Bit l set iff leaf l (in visit order) is a candidate of the ray: sb holds
+// every box bit of need[l].  Four words of need[] per trip; the padding
+// words' bits are masked off.
+template <class M>
+PT_FN uint32_t sweep_leaves(M sb, const SweepTable& t) {
+  const SweepNeedP need = sweep_need(t);
+  const int nl = t.n_leaves;
+  uint32_t lm = 0u;
+  if constexpr (sizeof(M) == 4) {
+    const uint32_t s = (uint32_t)sb;
+#pragma clang loop vectorize(disable)
+    for (int l = 0; l < nl; l += 4) {
+      const SweepNeed4 nd = need[l >> 2];
+      uint32_t m = 0u;
+      m |= (s & nd[0]) == nd[0] ? 1u : 0u;
+      m |= (s & nd[1]) == nd[1] ? 2u : 0u;
+      m |= (s & nd[2]) == nd[2] ? 4u : 0u;
+      m |= (s & nd[3]) == nd[3] ? 8u : 0u;
+      lm |= m << l;
+    }
+  } else {
+    const uint64_t s = (uint64_t)sb;
+#pragma clang loop vectorize(disable)
+    for (int l = 0; l < nl; l += 2) {
+      const SweepNeed4 nd = need[l >> 1];
+      const uint64_t n0 = nd[0] | (uint64_t)nd[1] << 32, n1 = nd[2] | (uint64_t)nd[3] << 32;
+      uint32_t m = 0u;
+      m |= (s & n0) == n0 ? 1u : 0u;
+      m |= (s & n1) == n1 ? 2u : 0u;
+      lm |= m << l;
+    }
+  }
+  return nl >= 32 ? lm : lm & ((1u << nl) - 1u);
+}
+
+// Closest hit over the leaf mask: leaves in visit order, triangle records by
+// leaf (tris[3 * l ..]); *bt is the leaf index of the hit.
+PT_FN void sweep_closest(v3 o, v3 d, uint32_t lm, const float4* tris, float* best, int* bt) {
+  while (lm) {
+    const int l = __builtin_ctz(lm);
+    lm &= lm - 1u;
+    const float4* T = tris + 3 * l;
+    float t;
+    if (tri_test(o, d, T[0], T[1], T[2], &t) && t < *best) {
+      *best = t;
+      *bt = l;
+    }
+  }
+}
+
+// Shadow query over the leaf mask: true iff some candidate the reference
+// would accept (t < 1e30) has !(t >= limit).  "Any" does not depend on order.
+PT_FN bool sweep_occluded(v3 o, v3 d, float limit, uint32_t lm, const float4* tris) {
+  while (lm) {
+    const int l = __builtin_ctz(lm);
+    lm &= lm - 1u;
+    const float4* T = tris + 3 * l;
+    float t;
+    if (tri_test(o, d, T[0], T[1], T[2], &t) && t < 1e30f && !(t >= limit)) return true;
+  }
+  return false;
+}
+
+}  // namespace ptd

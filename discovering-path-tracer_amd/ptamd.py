@@ -40,6 +40,7 @@ PT_OPT_WF_GRID = 20
 PT_OPT_WF_REFILL = 21
 PT_OPT_MIXED_LANES = 22
 PT_OPT_DENOISE_LDS = 23
+PT_OPT_SMALL_SWEEP = 24
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -57,7 +58,7 @@ EXPORTS = [
     "pt_set_partition_slots", "pt_get_traced", "pt_wide_info", "pt_partition_items",
     "pt_dist_unique_id", "pt_dist_init", "pt_dist_run", "pt_dist_slot_floats", "pt_dist_finalize",
     "pt_dist_set_streams", "pt_dist_wait", "pt_dist_abort", "pt_create_multi", "pt_group_info",
-    "pt_group_check", "pt_dist_info", "pt_mixed_info",
+    "pt_group_check", "pt_dist_info", "pt_mixed_info", "pt_sweep_info",
     "pt_denoise_default_params", "pt_guide_ray", "pt_render_guide", "pt_guide_device_ptr", "pt_read_guide",
     "pt_denoise", "pt_read_denoised", "pt_denoise_host",
 ]
@@ -121,6 +122,7 @@ def lib():
             "pt_reset_stats": ([vp], i32), "pt_get_traced": ([vp, ctypes.POINTER(Traced)], i32),
             "pt_wide_info": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
             "pt_mixed_info": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
+            "pt_sweep_info": ([vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], i32),
             "pt_partition_items": ([i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, psz, vp, psz, vp], i32),
             "pt_dist_unique_id": ([vp, sz], i32), "pt_dist_init": ([vp, vp, i32, i32], i32),
             "pt_dist_run": ([vp, u32, i32, i32, vp, i32], i32), "pt_dist_slot_floats": ([vp, psz], i32),
@@ -640,6 +642,13 @@ class Renderer:
         if info[0] == 0:
             return 0, 0, lib().pt_last_error().decode()
         return info[0], info[1]
+
+    def sweep_info(self):
+        """(distinct boxes, leaves) of the sweep walk's table when it is in
+        force (PT_OPT_SMALL_SWEEP), else (0, 0)."""
+        b, n = ctypes.c_int(0), ctypes.c_int(0)
+        _check(lib().pt_sweep_info(self._c, ctypes.byref(b), ctypes.byref(n)), "pt_sweep_info")
+        return b.value, n.value
 
     def mixed_info(self):
         """(schedule, live workgroups, measured launches) of the last launch:

@@ -40,7 +40,8 @@ extern "C" {
  * Still 3, additions only: the guide image and the a-trous denoiser
  * (pt_denoise_params, pt_denoise_default_params, pt_guide_ray,
  * pt_render_guide, pt_guide_device_ptr, pt_read_guide, pt_denoise,
- * pt_read_denoised, pt_denoise_host, PT_OPT_DENOISE_LDS). */
+ * pt_read_denoised, pt_denoise_host, PT_OPT_DENOISE_LDS); the sweep walk of
+ * tiny scenes (pt_sweep_info, PT_OPT_SMALL_SWEEP). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -460,7 +461,10 @@ int pt_dist_finalize(pt_context* ctx);
  * pt_launch_span_ms.  Output-invariant. */
 #define PT_OPT_LAUNCH_TIMING 9
 /* PT_OPT_COUNT_TRACED: 1 = run the fast kernels with counters of the work
- * they actually do (pt_get_traced); slower, output identical.  Default 0. */
+ * they actually do (pt_get_traced); slower, output identical.  Default 0.
+ * The counting kernels always run the threaded walk: with the sweep walk in
+ * force (PT_OPT_SMALL_SWEEP) the counts are still the threaded walk's node
+ * visits and triangle tests, not the sweep's box tests. */
 #define PT_OPT_COUNT_TRACED 10
 /* PT_OPT_PAIRS: 0 only.  1 (child-pair records, measured slower on every
  * scene) was removed: PT_ERR_UNSUPPORTED. */
@@ -557,6 +561,22 @@ int pt_dist_finalize(pt_context* ctx);
  * 0.1210 / 0.1124 ms, the 5-pass call 0.6430 against 0.6502 ms
  * (profiles/denoise/timing_1080p.json).  Output is identical. */
 #define PT_OPT_DENOISE_LDS 23
+/* PT_OPT_SMALL_SWEEP: a scene of at most 32 triangles, staged in LDS
+ * (PT_OPT_SCENE_IN_LDS), can be walked by the path-recursive kernel as a
+ * wave-uniform sweep: one slab test per distinct node box, read through the
+ * scalar cache, then per leaf a mask test "its box and every ancestor's box
+ * passed", then the triangle tests in visit order.  The slab test is pure and
+ * culls nothing by distance, so the candidates, their order and every hit are
+ * the threaded walk's bit for bit.  -1 (default) = the sweep
+ * for scenes of at most 15 distinct boxes, the largest size at which it
+ * measured no slower than the threaded walk by mean and by fastest launch
+ * (box.obj has 7: 1080p 8 spp 0.192 -> 0.159 ms per frame; profiles/sweep/);
+ * 1 = the sweep for every scene of at most 32 triangles (63 boxes: +70 %);
+ * 0 = the threaded walk.
+ * pt_sweep_info reports whether the sweep is in force.  Stats mode and
+ * PT_OPT_COUNT_TRACED run the threaded walk either way.  Output is
+ * identical. */
+#define PT_OPT_SMALL_SWEEP 24
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
@@ -586,6 +606,13 @@ int pt_get_traced(pt_context* ctx, pt_traced* out);
  * nodes (0 = not built; pt_last_error() then says why), info[1] = the most
  * stack entries one walk can hold. */
 int pt_wide_info(pt_context* ctx, int info[2]);
+/* The sweep walk of the uploaded scene (PT_OPT_SMALL_SWEEP): the distinct
+ * boxes and the leaves of its table when the context's launches, as its
+ * options stand, walk it -- the option's value admits the scene,
+ * PT_OPT_SCENE_IN_LDS is not 0, PT_OPT_KERNEL is not 3, and neither stats
+ * mode nor PT_OPT_COUNT_TRACED is on (the same predicate pt_render uses) --
+ * else zeros. */
+int pt_sweep_info(pt_context* ctx, int* boxes, int* leaves);
 /* Mixed sample lanes of the last path-recursive launch (PT_OPT_MIXED_LANES):
  * info[0] = 0 uniform lanes, 1 the static mixed schedule, 2 the measured one;
  * info[1] = live workgroups it launched; info[2] = measuring launches folded
