@@ -320,7 +320,7 @@ struct pt_context {
   const void* culled_buf = nullptr;
   long long render_slots = -1;                 // resident LDS render workgroups (mixed lanes' budget)
   size_t render_slots_lds = 0;                 // ... at this many bytes of staged scene
-  int render_slots_sweep = 0;                  // ... of this sweep-walk kernel (0: the threaded walk's)
+  bool render_slots_sweep = false;             // ... of the sweep-walk kernel (false: the threaded walk's)
   size_t culled_org_off = 0;   // h_items / d_items: where the culled items' first pixels start
   size_t live_org_off = 0;     // ... and the live items' ones
   std::vector<int> h_items;
@@ -1164,10 +1164,9 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
         !cnt) {
       mixed = true;
       const size_t lds_b = sweep ? ptd::sweep_lds_bytes(p) : ptd::scene_lds_bytes(p);
-      const int sweep_kind = !sweep ? 0 : p.sweep_boxes > 32 ? 2 : 1;
-      if (c->render_slots < 0 || c->render_slots_lds != lds_b || c->render_slots_sweep != sweep_kind) {
-        c->render_slots_sweep = sweep_kind;
-        c->render_slots = ptd::render_slots(lds_b, sweep_kind);
+      if (c->render_slots < 0 || c->render_slots_lds != lds_b || c->render_slots_sweep != sweep) {
+        c->render_slots_sweep = sweep;
+        c->render_slots = ptd::render_slots(lds_b, sweep);
         c->render_slots_lds = lds_b;
       }
       // auto: every item at PT_OPT_SAMPLE_LANES until the block costs are

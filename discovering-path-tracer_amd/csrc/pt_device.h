@@ -234,7 +234,7 @@ hipError_t launch_atrous(const float4* src, const float4* guide, float4* dst, in
 // lanes of the wide walk's persistent grid on this device (overflow areas to allocate)
 long long wide_trace_lanes();
 // workgroups of the LDS-staged render kernel resident on this device at once
-long long render_slots(size_t lds_bytes, int sweep = 0);   // sweep: of its sweep-walk variant (1: up to 32 boxes, 2: more)
+long long render_slots(size_t lds_bytes, bool sweep = false);   // sweep: of its sweep-walk variant
 // triangle records by rank: dst[r] = tris[tri_of[r]]
 hipError_t launch_gather_tris(const float4* tris, const int* tri_of, int n, float4* dst, hipStream_t stream);
 hipError_t launch_math(int fn, const float* x, float* y, size_t n, hipStream_t stream);

@@ -315,9 +315,8 @@ __device__ __forceinline__ void walk_pair(const RenderParams& P, bool has_s, v3 
 // The walks of a tiny scene as a box sweep (sweep_walk.h; PT_OPT_SMALL_SWEEP):
 // P.tris holds the LDS-staged triangle records by leaf, and a hit's index is
 // its leaf's (P.hit_tris is the same array).  A wave none of whose rays passes
-// the root box has no candidates: it skips the leaf masks too.
-// M: the box mask, 32 bits for up to 32 distinct boxes, else 64.
-template <class M>
+// the root box has no candidates.  One kernel for every table (up to 64
+// boxes, 32 leaves): the lanes hold a leaf mask only, no box mask.
 __device__ Hit sweep_trace_closest(const RenderParams& P, v3 o, v3 d) {
   const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
   const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
@@ -325,20 +324,19 @@ __device__ Hit sweep_trace_closest(const RenderParams& P, v3 o, v3 d) {
   r.t = 1e30f;
   r.tri = -1;
   bool none;
-  const M sb = sweep_mask<M>(o, inv, tb, &none);
+  const uint32_t lm = sweep_cands(o, inv, tb, &none);
   if (none) return r;
-  sweep_closest(o, d, sweep_leaves(sb, tb), P.tris, &r.t, &r.tri);
+  sweep_closest(o, d, lm, P.tris, &r.t, &r.tri);
   return r;
 }
 
-template <class M>
 __device__ bool sweep_trace_occluded(const RenderParams& P, v3 o, v3 d, float limit) {
   const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
   const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
   bool none;
-  const M sb = sweep_mask<M>(o, inv, tb, &none);
+  const uint32_t lm = sweep_cands(o, inv, tb, &none);
   if (none) return false;
-  return sweep_occluded(o, d, limit, sweep_leaves(sb, tb), P.tris);
+  return sweep_occluded(o, d, limit, lm, P.tris);
 }
 
 // Lights are read-only for the whole launch and indexed by a wave-uniform
@@ -491,24 +489,20 @@ __device__ __forceinline__ v3 unpark3(const float* pk, int i) {
 
 // pathTrace (:300-418)
 // SWEEP: the walks are the box sweep's (no candidate queue: the parked state
-// starts at cand), 1 with a 32-bit box mask, 2 with a 64-bit one.
-template <bool STATS, bool PF, bool CNT = false, int SWEEP = 0>
+// starts at cand).
+template <bool STATS, bool PF, bool CNT = false, bool SWEEP = false>
 __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr& c, int* cand) {
   constexpr bool PARK = (SWEEP ? PT_PARK_SWEEP : PT_PARK) && !STATS && !PF;
   float* pk = (float*)(cand + (SWEEP ? 0 : kCand) * 64);
   auto closest = [&](v3 o, v3 d, Ctr& cc) {
-    if constexpr (SWEEP == 2)
-      return sweep_trace_closest<uint64_t>(P, o, d);
-    else if constexpr (SWEEP == 1)
-      return sweep_trace_closest<uint32_t>(P, o, d);
+    if constexpr (SWEEP)
+      return sweep_trace_closest(P, o, d);
     else
       return trace_closest<STATS, PF, false, CNT>(P, o, d, cc, cand);
   };
   auto shadowed = [&](v3 o, v3 d, float limit) {
-    if constexpr (SWEEP == 2)
-      return sweep_trace_occluded<uint64_t>(P, o, d, limit);
-    else if constexpr (SWEEP == 1)
-      return sweep_trace_occluded<uint32_t>(P, o, d, limit);
+    if constexpr (SWEEP)
+      return sweep_trace_occluded(P, o, d, limit);
     else
       return occluded<STATS, PF, CNT>(P, o, d, limit, c);
   };
@@ -906,9 +900,8 @@ __device__ unsigned long long g_wg_trace[kWgTraceCap][4];
 // once per workgroup; chosen by the host for scenes of at most a few tens of
 // KB (box.obj is 1.3 KB), where every lane re-reads the same few nodes.
 // SWEEP (LDS, no counters): a tiny scene's walks are the box sweep over
-// P.sweep (1: up to 32 distinct boxes, 2: more); only the triangle records
-// are staged, by leaf.
-template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0>
+// P.sweep; only the triangle records are staged, by leaf.
+template <bool STATS, bool LDS, bool CNT = false, bool SWEEP = false>
 #ifndef PT_RENDER_MIN_BLOCKS
 #define PT_RENDER_MIN_BLOCKS 5
 #endif
@@ -2959,7 +2952,7 @@ hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipS
   if (lds > kMaxSceneLds) return hipErrorInvalidValue;
   void (*kern)(RenderParams);
   if (sweep)
-    kern = sweep_wide(p.sweep_boxes) ? render_kernel<false, true, false, 2> : render_kernel<false, true, false, 1>;
+    kern = render_kernel<false, true, false, true>;
   else if (cnt)
     kern = lds_scene ? render_kernel<false, true, true> : render_kernel<false, false, true>;
   else
@@ -2987,17 +2980,13 @@ hipError_t launch_guide(const RenderParams& p, float4* guide, bool lds_scene, hi
   return hipGetLastError();
 }
 
-long long render_slots(size_t lds_bytes, int sweep) {
+long long render_slots(size_t lds_bytes, bool sweep) {
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &per_cu,
-          sweep == 2   ? render_kernel<false, true, false, 2>
-          : sweep == 1 ? render_kernel<false, true, false, 1>
-                       : render_kernel<false, true>,
-          256, lds_bytes) !=
-      hipSuccess)
+          sweep ? render_kernel<false, true, false, true> : render_kernel<false, true>, 256, lds_bytes) != hipSuccess)
     return 0;
   return (long long)cus * per_cu;
 }

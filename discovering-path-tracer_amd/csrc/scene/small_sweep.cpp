@@ -27,9 +27,10 @@ bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, i
   size_t leaves = 0;
   for (size_t k = 0; k < n_kept; ++k) leaves += tri_of(k) >= 0 ? 1 : 0;
   if (leaves > (size_t)max_leaves) return false;
-  // distinct boxes by the 24 bytes of min/max, numbered by first appearance:
-  // node 0 is the root, so its box is box 0.  An implied leaf (kept, bit 31)
-  // has the box of a kept ancestor bitwise, hence that ancestor's id.
+  // distinct boxes by the 24 bytes of min/max, numbered by first appearance
+  // (reordered by kind below): node 0 is the root, so its box is box 0.  An
+  // implied leaf (kept, bit 31) has the box of a kept ancestor bitwise, hence
+  // that ancestor's id.
   SmallSweep s;
   std::vector<int> box_id(n_kept);
   for (size_t k = 0; k < n_kept; ++k) {
@@ -45,6 +46,31 @@ bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, i
     }
     box_id[k] = id;
   }
+  // order: root, general boxes, then the boxes flat (lo == hi bitwise) in x, y, z
+  // (by their first flat axis); the four counts in the root record's last word
+  {
+    auto cls = [&](int b) {
+      if (b == 0) return 0;
+      for (int a = 0; a < 3; ++a)
+        if (memcmp(&s.boxes[8 * (size_t)b + a], &s.boxes[8 * (size_t)b + 4 + a], 4) == 0) return 2 + a;
+      return 1;
+    };
+    std::vector<int> new_id((size_t)s.n_boxes);
+    std::vector<float> sorted;
+    uint32_t counts[5] = {0, 0, 0, 0, 0};
+    int next = 0;
+    for (int c = 0; c < 5; ++c)
+      for (int b = 0; b < s.n_boxes; ++b)
+        if (cls(b) == c) {
+          new_id[(size_t)b] = next++;
+          ++counts[c];
+          sorted.insert(sorted.end(), s.boxes.begin() + 8 * (size_t)b, s.boxes.begin() + 8 * (size_t)b + 8);
+        }
+    s.boxes = sorted;
+    for (size_t k = 0; k < n_kept; ++k) box_id[k] = new_id[(size_t)box_id[k]];
+    const uint32_t w = counts[1] | counts[2] << 8 | counts[3] << 16 | counts[4] << 24;
+    memcpy(&s.boxes[7], &w, 4);
+  }
   // a is an ancestor of k iff a < k < skip(a) (a leaf's skip is a + 1)
   for (size_t k = 0; k < n_kept; ++k) {
     if (tri_of(k) < 0) continue;
@@ -55,6 +81,13 @@ bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, i
     s.slot.push_back(tri_of(k));
   }
   s.n_leaves = (int)s.need.size();
+  // under[b]: the leaves box b guards, as the bit pattern of the record's
+  // fourth word (sweep_walk.h sweep_cands; slab never reads it)
+  s.under.assign((size_t)s.n_boxes, 0u);
+  for (int l = 0; l < s.n_leaves; ++l)
+    for (int b = 0; b < s.n_boxes; ++b)
+      if (s.need[(size_t)l] >> b & 1u) s.under[(size_t)b] |= 1u << l;
+  for (int b = 0; b < s.n_boxes; ++b) memcpy(&s.boxes[8 * (size_t)b + 3], &s.under[(size_t)b], 4);
   *out = s;
   return true;
 }

@@ -11,15 +11,20 @@
 
 namespace pt {
 
-// Largest table the sweep walk takes: one bit per leaf in a 32-bit mask and
-// one per distinct box in a 32- or 64-bit mask (sweep_walk.h).  A tree of 32
-// leaves has 63 nodes, so the leaves bound both.
+// Largest table the sweep walk takes: one bit per leaf in a 32-bit mask
+// (the walk's own, and each box's under word) and one per distinct box in a
+// 64-bit need word (sweep_walk.h).  A tree of 32 leaves has 63 nodes, so the
+// leaves bound both.
 constexpr int kSweepMaxBoxes = 64;
 constexpr int kSweepMaxLeaves = 32;
 
 struct SmallSweep {
-  std::vector<float> boxes;      // 8 floats per distinct box: {lo.xyz, 0} {hi.xyz, 0}; box 0 is the root's
+  // 8 floats per distinct box: {lo.xyz, under's bits} {hi.xyz, 0}.  Box 0 is the root's; then the general
+  // boxes, then those flat (lo == hi bitwise) in x, in y, in z, each by its first flat axis.  The root's
+  // last word holds the bits of: general | x-flat << 8 | y-flat << 16 | z-flat << 24 (counts, the root apart)
+  std::vector<float> boxes;
   std::vector<uint64_t> need;    // per leaf in kept-node (visit) order: the box bits of the leaf and its ancestors
+  std::vector<uint32_t> under;   // per box: the leaves whose need holds its bit (box 0: every leaf)
   std::vector<int32_t> slot;     // per leaf: its triangle slot
   int n_boxes = 0, n_leaves = 0;
   // The device table (sweep_walk.h SweepTable): boxes, need[] (32-bit words

@@ -1,6 +1,6 @@
 // sweep_walk.h — the exact walk of a tiny scene as a wave-uniform box sweep
 // (scene/small_sweep.h builds the table; pt_device.hip's LDS render kernel and
-// tests/sweep_check.cpp run these functions).
+// tests/sweep_check.cpp, tests/sweep_fold_check.cpp run these functions).
 //
 // Why it returns the threaded walk's hits bit for bit:
 //   * slab(o, inv, lo, hi) is a pure function of the ray and the 24 bytes of
@@ -8,11 +8,24 @@
 //     walk tests the triangle of a leaf exactly when the leaf's box and every
 //     ancestor's box pass the slab test (an implied node passes with its
 //     parent, whose box it has bitwise), in kept-node index order.
-//   * The table holds each distinct box once.  sweep_mask sets bit b of `sb`
-//     iff box b passes; leaf l is a candidate iff sb holds every bit of
-//     need[l], the OR of the box bits of the leaf and all its ancestors.
-//     `sb` and need[] are 32 bits wide for up to 32 distinct boxes, else 64
-//     (a tree of 32 leaves has at most 63 boxes).
+//   * The table holds each distinct box once.  need[l] is the OR of the box
+//     bits of leaf l and all its ancestors: leaf l is a candidate iff every
+//     box of need[l] passes.  Which leaves a box guards is a property of the
+//     box, the same for every ray, so each box's record carries
+//     under[b] = { l : need[l] has bit b } in its fourth word, and the sweep
+//     (sweep_cands) ORs the under masks of the boxes that fail: the
+//     candidates are the leaves no failing box guards.  One pass, one 32-bit
+//     leaf mask per lane whatever the number of boxes (up to 64).
+//   * A box with lo == hi bitwise on an axis (every axis-aligned face: six of
+//     the box's seven) has t0 == t1 there, so slab's fmin_(t, t) and
+//     fmax_(t, t) are t itself.  The table lists the root, the general boxes,
+//     then the x-, y- and z-flat ones, and the sweep runs one loop per group;
+//     the flat loops (sweep_slab_flat) skip one subtract, multiply, min and
+//     max per box and answer as slab does, NaNs included.
+//   * sweep_mask / sweep_leaves state the same predicate from need[] in two
+//     passes (box bits, then (sb & need[l]) == need[l] per leaf).  The device
+//     does not call them: they are the restatement the tests hold sweep_cands
+//     to, ray by ray.
 //   * Candidates are popped from the leaf mask lowest bit first -- the visit
 //     order -- with the same tri_test and the same strict '<'.
 // The sweep loop is wave-uniform: on the device the boxes arrive through the
@@ -25,8 +38,11 @@ namespace ptd {
 using namespace ptm;
 
 // The device table of pt::SmallSweep::pack(): n_boxes records of 8 floats
-// {lo.xyz, 0, hi.xyz, 0}, then need[] (one word per leaf, two -- low, high --
-// with more than 32 boxes) padded to a multiple of 4 words, then
+// {lo.xyz, under, hi.xyz, 0} (under: the bit pattern of the box's leaf mask;
+// slab never reads that word) in the order root, general, x-flat, y-flat,
+// z-flat, the root's last word holding the four counts after it (general |
+// x << 8 | y << 16 | z << 24), then need[] (one word per leaf, two -- low,
+// high -- with more than 32 boxes) padded to a multiple of 4 words, then
 // slot[n_leaves].  32-B aligned.
 struct SweepTable {
   const float4* boxes;
@@ -115,6 +131,80 @@ PT_FN uint32_t sweep_leaves(M sb, const SweepTable& t) {
     }
   }
   return nl >= 32 ? lm : lm & ((1u << nl) - 1u);
+}
+
+// Flat boxes per trip of their loops (the box has two per axis; at four its
+// pairs ran through the one-box remainder and measured slower, profiles/fold).
+#ifndef PT_SWEEP_FLAT_UNROLL
+#define PT_SWEEP_FLAT_UNROLL 2
+#endif
+// slab() for a box with lo == hi bitwise on AXIS: there t0 == t1, so
+// fmin_(t, t) and fmax_(t, t) are t itself (a NaN stays a NaN and the outer
+// min/max drop it as before).  Same operations in the same order otherwise.
+template <int AXIS>
+PT_FN bool sweep_slab_flat(v3 o, v3 inv, SweepBox r) {
+  const float t0x = (r[0] - o.x) * inv.x, t0y = (r[1] - o.y) * inv.y, t0z = (r[2] - o.z) * inv.z;
+  const float t1x = AXIS == 0 ? t0x : (r[4] - o.x) * inv.x;
+  const float t1y = AXIS == 1 ? t0y : (r[5] - o.y) * inv.y;
+  const float t1z = AXIS == 2 ? t0z : (r[6] - o.z) * inv.z;
+  const float nx = AXIS == 0 ? t0x : fmin_(t0x, t1x), fx = AXIS == 0 ? t0x : fmax_(t0x, t1x);
+  const float ny = AXIS == 1 ? t0y : fmin_(t0y, t1y), fy = AXIS == 1 ? t0y : fmax_(t0y, t1y);
+  const float nz = AXIS == 2 ? t0z : fmin_(t0z, t1z), fz = AXIS == 2 ? t0z : fmax_(t0z, t1z);
+  const float tmin = fmax_(fmax_(nx, ny), nz);
+  const float tmax = fmin_(fmin_(fx, fy), fz);
+  return tmin <= tmax && tmax >= 0.0f;
+}
+// Bit l set iff leaf l (in visit order) is a candidate of the ray: no box that
+// fails the slab test has l in its under mask (the record's fourth word).
+// Box 0 is the root's and guards every leaf: when no ray at hand passes it (no
+// lane of the wave on the device) the other boxes are not tested and *none is
+// set: the walk has no candidate.  Equal to sweep_leaves(sweep_mask(...)) and
+// its *none for every ray, NaNs of 0 * inf included: both go through slab.
+//
+// sweep_fold is the sweep past the root's test: `root` is this ray's answer,
+// false in a lane that rides along because another lane of its wave passed.
+PT_FN uint32_t sweep_fold(v3 o, v3 inv, const SweepTable& t, bool root) {
+  const SweepBoxP B = sweep_boxes(t);
+  const SweepBox r0 = B[0];
+  const uint32_t all = f2u(r0[3]);
+  uint32_t fail = root ? 0u : all;
+  // the table's order: root, general boxes, x-flat, y-flat, z-flat; their counts in the root record's last word
+  const uint32_t cnt = f2u(r0[7]);
+  int b = 1, e = 1 + (int)(cnt & 0xffu);
+#pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_UNROLL)
+  for (; b < e; ++b) {
+    const SweepBox r = B[b];
+    fail |= sweep_slab(o, inv, r) ? 0u : f2u(r[3]);
+  }
+  e += (int)(cnt >> 8 & 0xffu);
+#pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_FLAT_UNROLL)
+  for (; b < e; ++b) {
+    const SweepBox r = B[b];
+    fail |= sweep_slab_flat<0>(o, inv, r) ? 0u : f2u(r[3]);
+  }
+  e += (int)(cnt >> 16 & 0xffu);
+#pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_FLAT_UNROLL)
+  for (; b < e; ++b) {
+    const SweepBox r = B[b];
+    fail |= sweep_slab_flat<1>(o, inv, r) ? 0u : f2u(r[3]);
+  }
+  e += (int)(cnt >> 24 & 0xffu);
+#pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_FLAT_UNROLL)
+  for (; b < e; ++b) {
+    const SweepBox r = B[b];
+    fail |= sweep_slab_flat<2>(o, inv, r) ? 0u : f2u(r[3]);
+  }
+  return all & ~fail;
+}
+PT_FN uint32_t sweep_cands(v3 o, v3 inv, const SweepTable& t, bool* none) {
+  const bool root = sweep_slab(o, inv, sweep_boxes(t)[0]);
+#if defined(__HIP_DEVICE_COMPILE__)
+  *none = __builtin_amdgcn_ballot_w64(root) == 0;
+#else
+  *none = !root;
+#endif
+  if (*none) return 0u;
+  return sweep_fold(o, inv, t, root);
 }
 
 // Closest hit over the leaf mask: leaves in visit order, triangle records by

@@ -21,7 +21,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BOX_KERNEL = "render_kernel<false, true, false"   # ...>: the threaded walk; ..., 1> / 2>: the sweep walk
+BOX_KERNEL = "render_kernel<false, true, false"   # ..., false>: the threaded walk; ..., true>: the sweep walk
 KERNEL_SOURCES = ("pt_device.hip", "pt_device.h", "pt_isect.h", "wide_walk.h", "pt_math.h", "scene/wide_bvh.cpp",
                   "../Makefile")   # the Makefile: the device build flags   # == bench.py
 # (bench.py's list predates csrc/sweep_walk.h, which holds the box kernel's walk: after an edit
