@@ -25,6 +25,7 @@
 #include "pt_denoise.h"
 #include "pt_device.h"
 #include "pt_group.h"
+#include "pt_cull.h"
 #include "pt_math.h"
 #include "scene/bvh.h"
 #include "scene/camera.h"
@@ -93,7 +94,11 @@ std::vector<float4> as_float4(const std::vector<float>& f) {
 // primary ray misses the root box (so traceRay returns no hit) and every light
 // (the pre-pass hits nothing), and the sample is exactly (0,0,0).  All maths
 // in double with margins far above the kernel's float rounding.
-constexpr double kGaussR = 13.25;
+// The derivation holds for any bound Rg on the two radii of a sample: with
+// ptd::kGaussR it covers every sample; with ptd::kCullTightR it covers the
+// samples whose two draws u1 are at least ptd::kCullTightU0 (pt_cull.h), which
+// the kernel checks per sample before it skips one (PT_OPT_CULL_TIGHT).
+using ptd::kGaussR;
 
 struct D3 { double x, y, z; };
 D3 d3(const float* f) { return {f[0], f[1], f[2]}; }
@@ -105,9 +110,10 @@ D3 dcross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.
 double dlen(D3 a) { return sqrt(ddot(a, a)); }
 
 // Returns the rectangle count (>= 0) or -1 when no guarantee is derived.
+// Rg: the bound on the Box-Muller radii the rectangles hold for.
 int cull_rects(const float cam[16], int W, int H, const float* lo, const float* hi, const pt_area_light* lights,
-               int n_lights, float* rects, int max_rects) {
-  if (W <= 0 || H <= 0 || n_lights < 0 || n_lights + 1 > max_rects) return -1;
+               int n_lights, float* rects, int max_rects, double Rg = kGaussR) {
+  if (W <= 0 || H <= 0 || n_lights < 0 || n_lights + 1 > max_rects || !(Rg >= 0.0 && Rg <= kGaussR)) return -1;
   const D3 cpos = d3(cam), cdir = d3(cam + 4), cup = d3(cam + 8);
   const double fov = cam[12];
   const double L = dlen(cdir);
@@ -120,10 +126,10 @@ int cull_rects(const float cam[16], int W, int H, const float* lo, const float* 
   const D3 up = dmul(ux, 1.0 / dlen(ux));
   const D3 ez = dmul(cdir, 1.0 / L);
   const double T = tan(fov * 0.5 * M_PI / 180.0), A = (double)W / (double)H;
-  const double jx = kGaussR * 0.5 / W, jy = kGaussR * 0.5 / H;              // jitter in NDC
+  const double jx = Rg * 0.5 / W, jy = Rg * 0.5 / H;                        // jitter in NDC
   const double amax = (1.0 + jx) * T * A / L, bmax = (1.0 + jy) * T / L;
   const double fz_min = 3.0 / sqrt(1.0 + amax * amax + bmax * bmax), fz_max = 3.0;
-  const double rho = 0.02 * kGaussR * 1.001;
+  const double rho = 0.02 * Rg * 1.001;
   int n = 0;
   auto add_object = [&](const D3* pts, int np) -> bool {
     double sx0 = INFINITY, sx1 = -INFINITY, sy0 = INFINITY, sy1 = -INFINITY, z0 = INFINITY, z1 = -INFINITY;
@@ -232,7 +238,9 @@ struct pt_context {
   int n_nodes = 0;
   float4* d_nodes_full = nullptr;   // threaded, every reference node (stats mode)
   float4* d_sweep = nullptr;        // the sweep table of a tiny scene (scene/small_sweep.h), or null
+  float4* d_sweep_plain = nullptr;  // ... and the same table without hull codes (PT_OPT_SWEEP_HULL 0)
   int sweep_boxes = 0, sweep_leaves = 0;
+  int sweep_hull = 0;               // boxes of the table with a hull code
   // culled wide walk (wide_walk.h): nodes, triangle records by rank, rank ->
   // slot, per-lane stack overflow areas (grown on demand)
   float4* d_wide = nullptr;
@@ -283,10 +291,12 @@ struct pt_context {
   int opt_mixed = -1;         // PT_OPT_MIXED_LANES: -1 auto, 0 off, k = whole tiles for k % of the resident slots
   int opt_kernel = 0;         // PT_OPT_KERNEL: 0 auto, 1 path-recursive, 3 wavefront
   int opt_cull = 1;           // PT_OPT_PRIMARY_CULL
+  int opt_cull_tight = 1;     // PT_OPT_CULL_TIGHT
   int opt_wf_paths = 0;       // PT_OPT_WF_PATHS (0 = 2^27)
   long long wf_fail = 0;      // wavefront paths whose allocation failed (0: none)
   int opt_count = 0;          // PT_OPT_COUNT_TRACED
   int opt_small_sweep = -1;   // PT_OPT_SMALL_SWEEP: -1 auto (kSweepAutoBoxes), 0 off, 1 whenever the scene has a table
+  int opt_sweep_hull = 1;     // PT_OPT_SWEEP_HULL
   int opt_wide_build = 1;     // PT_OPT_WIDE_BUILD (pt::WideBuild; read at upload)
   int opt_wf_streams = 1;     // PT_OPT_WF_STREAMS (2 measured slower: 10M cloud +9 %, sphere -0.8 %)
   hipStream_t wf_stream2 = nullptr;           // the wavefront pipeline's second half (created on first use)
@@ -1136,7 +1146,8 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   // the sweep walk (PT_OPT_SMALL_SWEEP): the plain LDS kernel of a scene with a table
   const bool sweep = lds && !wf && !cnt && sweep_in_force(c);
   if (sweep) {
-    p.sweep = c->d_sweep;
+    p.sweep = c->opt_sweep_hull ? c->d_sweep : c->d_sweep_plain;
+    p.sweep_hull = c->opt_sweep_hull && c->sweep_hull > 0;
     p.sweep_boxes = c->sweep_boxes;
     p.sweep_leaves = c->sweep_leaves;
   }
@@ -1154,6 +1165,15 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   if (c->opt_cull && !c->stats_mode)
     p.n_cull = cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
                           c->n_lights, &p.cull[0][0], ptd::kMaxCullRects);
+  // the tight rectangles (PT_OPT_CULL_TIGHT): the kernel's per-sample skip; every host-side use of the
+  // rectangles (items, fills, partitions) keeps the loose ones.  Off (-1, "never skip") unless both derive
+  p.n_cull_tight = -1;
+  p.cull_u0 = ptd::kCullTightU0;
+  if (p.n_cull >= 0 && c->opt_cull_tight) {
+    p.n_cull_tight = cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
+                                c->n_lights, &p.cull_tight[0][0], ptd::kMaxCullRects, ptd::kCullTightR);
+    if (p.n_cull_tight != p.n_cull) p.n_cull_tight = -1;
+  }
   if (p.n_cull >= 0) {
     // mixed lanes (PT_OPT_MIXED_LANES): one rank, LDS-staged path-recursive
     // launches that render into the accumulation buffer
@@ -1431,7 +1451,8 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_nodes);
   dev_free(c->d_nodes_full);
   dev_free(c->d_sweep);
-  c->sweep_boxes = c->sweep_leaves = 0;
+  dev_free(c->d_sweep_plain);
+  c->sweep_boxes = c->sweep_leaves = c->sweep_hull = 0;
   dev_free(c->d_wide);
   dev_free(c->d_wide_q);
   dev_free(c->d_wide_leafbox);
@@ -1532,7 +1553,8 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   dev_free(c->d_nodes);
   dev_free(c->d_nodes_full);
   dev_free(c->d_sweep);
-  c->sweep_boxes = c->sweep_leaves = 0;
+  dev_free(c->d_sweep_plain);
+  c->sweep_boxes = c->sweep_leaves = c->sweep_hull = 0;
   dev_free(c->d_wide);
   dev_free(c->d_wide_q);
   dev_free(c->d_wide_leafbox);
@@ -1569,11 +1591,15 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   PT_HIP(hipMemcpyAsync(st.v, vertices, n_vertex_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
   PT_HIP(hipMemcpyAsync(st.i, indices, n_indices * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   PT_HIP(ptd::launch_setup_tris(st.v, st.i, T, c->d_tris, c->stream));
-  const std::vector<float> sweep_table = sweep.pack();   // lives until the copy has run (synchronized below)
+  // (both live until the copies have run: synchronized below)
+  const std::vector<float> sweep_table = sweep.pack(), sweep_plain = sweep.pack(false);
   if (has_sweep) {
     PT_HIP(hipMalloc((void**)&c->d_sweep, sweep_table.size() * sizeof(float)));
     PT_HIP(hipMemcpyAsync(c->d_sweep, sweep_table.data(), sweep_table.size() * sizeof(float), hipMemcpyHostToDevice,
                           c->stream));
+    PT_HIP(hipMalloc((void**)&c->d_sweep_plain, sweep_plain.size() * sizeof(float)));
+    PT_HIP(hipMemcpyAsync(c->d_sweep_plain, sweep_plain.data(), sweep_plain.size() * sizeof(float),
+                          hipMemcpyHostToDevice, c->stream));
   }
   std::vector<int> rank_of_host(wide_reason.empty() ? (size_t)T : 0);
   if (wide_reason.empty()) {
@@ -1605,6 +1631,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->n_tris = T;
   c->sweep_boxes = has_sweep ? sweep.n_boxes : 0;
   c->sweep_leaves = has_sweep ? sweep.n_leaves : 0;
+  c->sweep_hull = has_sweep ? sweep.n_hull : 0;
   memcpy(c->root_lo, lo, sizeof lo);
   memcpy(c->root_hi, hi, sizeof hi);
   c->has_scene = true;
@@ -2163,6 +2190,14 @@ int pt_set_option(pt_context* c, int key, int value) {
     case PT_OPT_SMALL_SWEEP:
       if (value < -1 || value > 1) return fail(PT_ERR_INVALID, "PT_OPT_SMALL_SWEEP takes -1 (auto), 0 or 1");
       c->opt_small_sweep = value;
+      return PT_OK;
+    case PT_OPT_CULL_TIGHT:
+      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_CULL_TIGHT takes 0 or 1");
+      c->opt_cull_tight = value;
+      return PT_OK;
+    case PT_OPT_SWEEP_HULL:
+      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_SWEEP_HULL takes 0 or 1");
+      c->opt_sweep_hull = value;
       return PT_OK;
     case PT_OPT_GROUP_EXCHANGE:
     case PT_OPT_GROUP_CHECK:
@@ -2746,6 +2781,19 @@ int pt_primary_cull_rects(const float cam[16], int w, int h, const float root_mi
     return fail(PT_ERR_INVALID, "null argument");
   if (max_rects < 1) return fail(PT_ERR_INVALID, "max_rects must be >= 1");
   *n_rects = cull_rects(cam, w, h, root_min, root_max, lights, n_lights, rects, max_rects);
+  return PT_OK;
+}
+
+int pt_primary_cull_rects_r(const float cam[16], int w, int h, const float root_min[3], const float root_max[3],
+                            const pt_area_light* lights, int n_lights, double radius_bound, float* rects,
+                            int max_rects, int* n_rects, float* u0) {
+  if (!cam || !root_min || !root_max || !rects || !n_rects || (n_lights > 0 && !lights))
+    return fail(PT_ERR_INVALID, "null argument");
+  if (max_rects < 1) return fail(PT_ERR_INVALID, "max_rects must be >= 1");
+  const double R = radius_bound < 0.0 ? ptd::kCullTightR : radius_bound;
+  if (!(R <= ptd::kGaussR)) return fail(PT_ERR_INVALID, "radius bound above 13.25");
+  *n_rects = cull_rects(cam, w, h, root_min, root_max, lights, n_lights, rects, max_rects, R);
+  if (u0) *u0 = ptd::kCullTightU0;
   return PT_OK;
 }
 

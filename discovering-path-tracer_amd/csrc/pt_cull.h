@@ -1,0 +1,34 @@
+// pt_cull.h — the radius bounds of primary-ray culling, shared by the host
+// derivation (pt_api.cpp cull_rects), the render kernel's per-sample test
+// (pt_device.hip) and tests/cull_radius_check.cpp.
+#pragma once
+#include "pt_math.h"
+
+namespace ptd {
+
+// Every Box-Muller radius sqrt(-2 log u1) with u1 >= 1e-38
+// (raytrace_comp.comp:220) is below this: sqrt(-2 ln 1e-38) = 13.2286.
+constexpr double kGaussR = 13.25;
+
+// The tight bound (PT_OPT_CULL_TIGHT): a second set of rectangles is derived
+// with it, and a sample of a pixel outside them is traced only if one of its
+// two radii can exceed it.  A radius above 4.25 is drawn with probability
+// e^-9.03 = 1.2e-4.  (The two macros are for A/B builds of other bounds; they
+// go together: tests/cull_radius_check.cpp R prints the u0 of a bound R.)
+#ifndef PT_CULL_TIGHT_R
+#define PT_CULL_TIGHT_R 4.25
+#define PT_CULL_TIGHT_U0 0x1.f5b12ep-14f
+#endif
+constexpr double kCullTightR = PT_CULL_TIGHT_R;
+
+// randomGaussian's radius (:218-226) for the draw u, the kernel's own ops.
+PT_FN float cull_radius(float u) { return ptm::sqrt_(-2.0f * ptm::log_(ptm::fmax_(1e-38f, u))); }
+
+// The least float u0 such that cull_radius(u) <= kCullTightR for every float
+// u in [u0, 1]: all 1.1e8 of them evaluated, none assumed monotone, by
+// tests/cull_radius_check.cpp (bits 0x38fad897: radius 4.25 exactly; the float
+// below it gives 4.25000048).  A draw u1 >= kCullTightU0 has its radius within
+// the tight bound.
+constexpr float kCullTightU0 = PT_CULL_TIGHT_U0;
+
+}  // namespace ptd

@@ -95,9 +95,10 @@ struct RenderParams {
   const float4* nodes;
   const float4* tris;
   // the sweep table of a tiny scene (sweep_walk.h SweepTable, PT_OPT_SMALL_SWEEP)
-  // or null: render_kernel<false, true, false> then walks it instead of nodes
+  // or null: render_kernel<false, true, false, 1 or 2> then walks it instead of nodes
   const float4* sweep = nullptr;
   int sweep_boxes = 0, sweep_leaves = 0;
+  int sweep_hull = 0;   // host only: the table holds hull codes (PT_OPT_SWEEP_HULL), which picks the kernel that reads them
   const LightDev* lights;
   float4* accum;
   // [0..3] rays, nodes, leaf tests, samples (stats mode); [4..8] closest walks,
@@ -133,6 +134,13 @@ struct RenderParams {
   int n_culled_items;
   int n_cull;
   float cull[8][4];
+  // the tight rectangles (pt_cull.h, PT_OPT_CULL_TIGHT): derived like cull[] but for radii of at most
+  // kCullTightR; -1 = none.  Outside all of them a sample whose two radius draws u1 are at least cull_u0
+  // (kCullTightU0: both radii within the bound) is (0,0,0) and is not traced.  Kernel only: the host's
+  // item lists, fills and partitions go by cull[]
+  int n_cull_tight = -1;
+  float cull_tight[8][4] = {};
+  float cull_u0 = 0.0f;
   // pt_render_packed: live workgroup i stores its pixels to pack_out[i*256/spl
   // + q] (the pt_items_pack layout) instead of the accumulation buffer, and no
   // culled-item fill runs; null = normal rendering

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "pt_device.h"
+#include "pt_cull.h"
 #include "pt_denoise.h"
 #include "pt_isect.h"
 #include "wide_walk.h"
@@ -317,6 +318,7 @@ __device__ __forceinline__ void walk_pair(const RenderParams& P, bool has_s, v3 
 // its leaf's (P.hit_tris is the same array).  A wave none of whose rays passes
 // the root box has no candidates.  One kernel for every table (up to 64
 // boxes, 32 leaves): the lanes hold a leaf mask only, no box mask.
+template <bool HULL>
 __device__ Hit sweep_trace_closest(const RenderParams& P, v3 o, v3 d) {
   const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
   const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
@@ -324,17 +326,18 @@ __device__ Hit sweep_trace_closest(const RenderParams& P, v3 o, v3 d) {
   r.t = 1e30f;
   r.tri = -1;
   bool none;
-  const uint32_t lm = sweep_cands(o, inv, tb, &none);
+  const uint32_t lm = sweep_cands<HULL>(o, inv, tb, &none);
   if (none) return r;
   sweep_closest(o, d, lm, P.tris, &r.t, &r.tri);
   return r;
 }
 
+template <bool HULL>
 __device__ bool sweep_trace_occluded(const RenderParams& P, v3 o, v3 d, float limit) {
   const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
   const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
   bool none;
-  const uint32_t lm = sweep_cands(o, inv, tb, &none);
+  const uint32_t lm = sweep_cands<HULL>(o, inv, tb, &none);
   if (none) return false;
   return sweep_occluded(o, d, limit, lm, P.tris);
 }
@@ -489,20 +492,20 @@ __device__ __forceinline__ v3 unpark3(const float* pk, int i) {
 
 // pathTrace (:300-418)
 // SWEEP: the walks are the box sweep's (no candidate queue: the parked state
-// starts at cand).
-template <bool STATS, bool PF, bool CNT = false, bool SWEEP = false>
+// starts at cand); 2: of a table with hull faces (sweep_walk.h sweep_slab_hull).
+template <bool STATS, bool PF, bool CNT = false, int SWEEP = 0>
 __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr& c, int* cand) {
   constexpr bool PARK = (SWEEP ? PT_PARK_SWEEP : PT_PARK) && !STATS && !PF;
   float* pk = (float*)(cand + (SWEEP ? 0 : kCand) * 64);
   auto closest = [&](v3 o, v3 d, Ctr& cc) {
     if constexpr (SWEEP)
-      return sweep_trace_closest(P, o, d);
+      return sweep_trace_closest<SWEEP == 2>(P, o, d);
     else
       return trace_closest<STATS, PF, false, CNT>(P, o, d, cc, cand);
   };
   auto shadowed = [&](v3 o, v3 d, float limit) {
     if constexpr (SWEEP)
-      return sweep_trace_occluded(P, o, d, limit);
+      return sweep_trace_occluded<SWEEP == 2>(P, o, d, limit);
     else
       return occluded<STATS, PF, CNT>(P, o, d, limit, c);
   };
@@ -809,6 +812,18 @@ __device__ __forceinline__ void emit_lane(const RenderParams& P, bool active, si
     store_lane(P.accum + pix, acc, spl, j);
 }
 
+// Whether a pixel lies in one of the tight rectangles (pt_cull.h); true
+// without them.  Static indices: P stays in SGPRs/kernarg.
+__device__ __forceinline__ bool pixel_tight(const RenderParams& P, float ndcX0, float ndcY0) {
+  if (P.n_cull_tight < 0) return true;
+  bool tight = false;
+#pragma unroll
+  for (int r = 0; r < kMaxCullRects; ++r)
+    tight = tight || (r < P.n_cull_tight && ndcX0 >= P.cull_tight[r][0] && ndcX0 <= P.cull_tight[r][1] &&
+                      ndcY0 >= P.cull_tight[r][2] && ndcY0 <= P.cull_tight[r][3]);
+  return tight;
+}
+
 // Items (tile parts) whose every pixel is culled, listed by the host with
 // their first pixel: each thread folds the constant colour (0,0,0,1) into one
 // pixel's running mean, closed form where exact (fold_constant) — kPixPerFill
@@ -900,8 +915,11 @@ __device__ unsigned long long g_wg_trace[kWgTraceCap][4];
 // once per workgroup; chosen by the host for scenes of at most a few tens of
 // KB (box.obj is 1.3 KB), where every lane re-reads the same few nodes.
 // SWEEP (LDS, no counters): a tiny scene's walks are the box sweep over
-// P.sweep; only the triangle records are staged, by leaf.
-template <bool STATS, bool LDS, bool CNT = false, bool SWEEP = false>
+// P.sweep; only the triangle records are staged, by leaf.  SWEEP 2: the table
+// has hull faces (P.sweep_hull) and the walk reuses the root's slab products
+// for them; a table without any runs SWEEP 1, the walk that keeps nothing
+// from the root's test.
+template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0>
 #ifndef PT_RENDER_MIN_BLOCKS
 #define PT_RENDER_MIN_BLOCKS 5
 #endif
@@ -999,6 +1017,12 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
                             wy0 <= P.cull[r][3]);
     }
   }
+  // The tight rectangles (pt_cull.h, PT_OPT_CULL_TIGHT): the same theorem per
+  // sample, for radii of at most kCullTightR.  A live pixel outside all of
+  // them traces a sample only if one of the sample's two radius draws is below
+  // P.cull_u0 (its radius may then exceed the bound); every other sample of it
+  // is (0,0,0), the value the trace would produce.  Stats mode never skips.
+  const bool tight = STATS || pixel_tight(P, ndcX0, ndcY0);
   const size_t pix = (size_t)py * (size_t)W + (size_t)px;
   uint32_t nsamp = 0;
   if (active && (uint32_t)j < P.n_batches)
@@ -1056,20 +1080,24 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
       const uint32_t batch = P.first_batch + s;
       const uint32_t seed = (batch * (uint32_t)H + (uint32_t)py) * (uint32_t)W + (uint32_t)px;   // :435
       uint32_t rng = seed;
-      // randomGaussian x2 (:218-226, :445, :451)
-      float u1 = fmax_(1e-38f, rng_next(&rng));
-      float u2 = rng_next(&rng);
-      float r = sqrt_(-2.0f * log_(u1));
-      float th = (2.0f * 0x1.921fb6p+1f) * u2;
+      // randomGaussian x2 (:218-226, :445, :451): the four draws first, in
+      // the shader's order; a wave none of whose lanes needs its path (no
+      // lane in a tight rectangle, every radius draw at least P.cull_u0)
+      // goes straight to the fold with (0,0,0,1)
+      const float u1a = fmax_(1e-38f, rng_next(&rng));
+      const float u2a = rng_next(&rng);
+      const float u1j = fmax_(1e-38f, rng_next(&rng));
+      const float u2j = rng_next(&rng);
+      if (tight || u1a < P.cull_u0 || u1j < P.cull_u0) {
+      float r = sqrt_(-2.0f * log_(u1a));
+      float th = (2.0f * 0x1.921fb6p+1f) * u2a;
       float sn, cs;
       sincos_(th, &sn, &cs);
       const float ax = (r * cs) * 0.02f;
       const float ay = (r * sn) * 0.02f;
       const v3 origin = add(add(cpos, muls(right, ax)), muls(up, ay));   // :448
-      u1 = fmax_(1e-38f, rng_next(&rng));
-      u2 = rng_next(&rng);
-      r = sqrt_(-2.0f * log_(u1));
-      th = (2.0f * 0x1.921fb6p+1f) * u2;
+      r = sqrt_(-2.0f * log_(u1j));
+      th = (2.0f * 0x1.921fb6p+1f) * u2j;
       sincos_(th, &sn, &cs);
       const float jx = r * cs, jy = r * sn;
       const float ndcX = ndcX0 + (jx * 0.5f) / (float)W;                 // :453-454
@@ -1091,6 +1119,7 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
       else
         col = path_trace_fused<PT_REC_PF != 0, CNT>(P, origin, dir, seed, cand, c);
       col4 = make_float4(col.x, col.y, col.z, 1.0f);                      // vec4(color, 1.0)
+      }
      }
      if (PT_FOLD_DIRECT && spl == 1) {   // uniform: each lane folds its own sample, no hand-off (:467-469)
       if (active && live) {
@@ -1823,9 +1852,21 @@ __global__ __launch_bounds__(256) void wf_gen_kernel(RenderParams P, WfBuffers B
       F.up = mk(P.cam_upv[0], P.cam_upv[1], P.cam_upv[2]);
       F.tanFov = P.tan_fov;
       v3 col = mk(0.0f, 0.0f, 0.0f);
-      if (pixel_live(P, F.ndcX0, F.ndcY0)) {
+      S.s = (uint32_t)(g - pp * (long long)P.n_batches);
+      // render_kernel's per-sample skip (PT_OPT_CULL_TIGHT): outside the tight
+      // rectangles a sample whose two radius draws are at least P.cull_u0
+      // reaches nothing and is (0,0,0)
+      bool reach = pixel_live(P, F.ndcX0, F.ndcY0);
+      if (reach && !pixel_tight(P, F.ndcX0, F.ndcY0)) {
+        const uint32_t batch = P.first_batch + S.s;
+        uint32_t rng = (batch * (uint32_t)F.H + (uint32_t)F.py) * (uint32_t)F.W + (uint32_t)F.px;   // :435
+        const float u1a = fmax_(1e-38f, rng_next(&rng));
+        rng_next(&rng);
+        const float u1j = fmax_(1e-38f, rng_next(&rng));
+        reach = u1a < P.cull_u0 || u1j < P.cull_u0;
+      }
+      if (reach) {
         gen = true;
-        S.s = (uint32_t)(g - pp * (long long)P.n_batches);
         S.phase = PH_BEGIN;
         Ctr c = {0u, 0u, 0u, 0u, 0u};
         need = path_step<false>(P, F, S, T, c, &col);
@@ -2952,7 +2993,7 @@ hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipS
   if (lds > kMaxSceneLds) return hipErrorInvalidValue;
   void (*kern)(RenderParams);
   if (sweep)
-    kern = render_kernel<false, true, false, true>;
+    kern = p.sweep_hull ? render_kernel<false, true, false, 2> : render_kernel<false, true, false, 1>;
   else if (cnt)
     kern = lds_scene ? render_kernel<false, true, true> : render_kernel<false, false, true>;
   else
@@ -2986,7 +3027,7 @@ long long render_slots(size_t lds_bytes, bool sweep) {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &per_cu,
-          sweep ? render_kernel<false, true, false, true> : render_kernel<false, true>, 256, lds_bytes) != hipSuccess)
+          sweep ? render_kernel<false, true, false, 2> : render_kernel<false, true>, 256, lds_bytes) != hipSuccess)
     return 0;
   return (long long)cus * per_cu;
 }

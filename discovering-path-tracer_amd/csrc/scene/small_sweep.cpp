@@ -4,13 +4,14 @@
 
 namespace pt {
 
-std::vector<float> SmallSweep::pack() const {
+std::vector<float> SmallSweep::pack(bool hull_codes) const {
   const bool wide = n_boxes > 32;   // sweep_walk.h sweep_wide, sweep_need_words
   const size_t need_words = ((wide ? 2 : 1) * (size_t)n_leaves + 3) & ~(size_t)3;
   const size_t words = (size_t)8 * n_boxes + need_words + (size_t)n_leaves;
   std::vector<float> t((words + 3) / 4 * 4, 0.0f);
   if (n_boxes == 0) return t;
   memcpy(t.data(), boxes.data(), (size_t)8 * n_boxes * 4);
+  for (int b = 1; b < n_boxes && !hull_codes; ++b) t[8 * (size_t)b + 7] = 0.0f;
   for (int l = 0; l < n_leaves; ++l) {
     const uint32_t w[2] = {(uint32_t)need[l], (uint32_t)(need[l] >> 32)};
     memcpy(t.data() + 8 * (size_t)n_boxes + (wide ? 2 : 1) * (size_t)l, w, wide ? 8 : 4);
@@ -19,7 +20,8 @@ std::vector<float> SmallSweep::pack() const {
   return t;
 }
 
-bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, int max_boxes, int max_leaves) {
+bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, int max_boxes, int max_leaves,
+                       bool hull_codes) {
   *out = SmallSweep();
   if (n_kept == 0 || max_boxes > kSweepMaxBoxes || max_leaves > kSweepMaxLeaves) return false;
   auto skip_of = [&](size_t k) { int32_t s; memcpy(&s, collapsed + 8 * k + 3, 4); return (size_t)(s & 0x7fffffff); };
@@ -70,6 +72,23 @@ bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, i
     for (size_t k = 0; k < n_kept; ++k) box_id[k] = new_id[(size_t)box_id[k]];
     const uint32_t w = counts[1] | counts[2] << 8 | counts[3] << 16 | counts[4] << 24;
     memcpy(&s.boxes[7], &w, 4);
+  }
+  // hull faces: a flat box whose flat coordinate is bitwise the root's lo (code 1) or hi (code 2) on
+  // that axis and whose other four extents are bitwise the root's; the code in the record's last word
+  s.n_hull = 0;
+  for (int b = 1; b < s.n_boxes && hull_codes; ++b) {
+    float* r = &s.boxes[8 * (size_t)b];
+    const float* r0 = &s.boxes[0];
+    int flat = -1;
+    for (int a = 2; a >= 0; --a)
+      if (memcmp(r + a, r + 4 + a, 4) == 0) flat = a;   // the first flat axis, as cls above
+    if (flat < 0) continue;
+    bool same = true;
+    for (int a = 0; a < 3; ++a)
+      if (a != flat) same = same && memcmp(r + a, r0 + a, 4) == 0 && memcmp(r + 4 + a, r0 + 4 + a, 4) == 0;
+    const uint32_t code = !same ? 0u : memcmp(r + flat, r0 + flat, 4) == 0 ? 1u : memcmp(r + flat, r0 + 4 + flat, 4) == 0 ? 2u : 0u;
+    memcpy(r + 7, &code, 4);
+    s.n_hull += code != 0u;
   }
   // a is an ancestor of k iff a < k < skip(a) (a leaf's skip is a + 1)
   for (size_t k = 0; k < n_kept; ++k) {

@@ -21,21 +21,27 @@ constexpr int kSweepMaxLeaves = 32;
 struct SmallSweep {
   // 8 floats per distinct box: {lo.xyz, under's bits} {hi.xyz, 0}.  Box 0 is the root's; then the general
   // boxes, then those flat (lo == hi bitwise) in x, in y, in z, each by its first flat axis.  The root's
-  // last word holds the bits of: general | x-flat << 8 | y-flat << 16 | z-flat << 24 (counts, the root apart)
+  // last word holds the bits of: general | x-flat << 8 | y-flat << 16 | z-flat << 24 (counts, the root apart).
+  // A flat box's last word holds the bits of its hull code: 1 (2) when its flat coordinate is bitwise the
+  // root's lo (hi) on that axis and its other four extents are bitwise the root's (a face of the root box: its
+  // slab values are the root's own, sweep_walk.h sweep_slab_hull), else 0
   std::vector<float> boxes;
   std::vector<uint64_t> need;    // per leaf in kept-node (visit) order: the box bits of the leaf and its ancestors
   std::vector<uint32_t> under;   // per box: the leaves whose need holds its bit (box 0: every leaf)
   std::vector<int32_t> slot;     // per leaf: its triangle slot
   int n_boxes = 0, n_leaves = 0;
+  int n_hull = 0;                // boxes with a hull code
   // The device table (sweep_walk.h SweepTable): boxes, need[] (32-bit words
   // for up to 32 boxes, else 64-bit) padded to whole float4s, slot[].
-  std::vector<float> pack() const;
+  // hull_codes false: the same table with every hull code 0.
+  std::vector<float> pack(bool hull_codes = true) const;
 };
 
 // Builds the table from a collapsed threaded array (n_kept nodes, no padding
 // node).  false (and an empty table) when the scene has more than max_boxes
-// distinct boxes or max_leaves leaves.
+// distinct boxes or max_leaves leaves.  hull_codes false leaves every flat
+// box's code 0 (the walk then tests each with its own slab products).
 bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, int max_boxes = kSweepMaxBoxes,
-                       int max_leaves = kSweepMaxLeaves);
+                       int max_leaves = kSweepMaxLeaves, bool hull_codes = true);
 
 }  // namespace pt

@@ -22,6 +22,19 @@
 //     then the x-, y- and z-flat ones, and the sweep runs one loop per group;
 //     the flat loops (sweep_slab_flat) skip one subtract, multiply, min and
 //     max per box and answer as slab does, NaNs included.
+//   * A flat box that is a face of the root box -- its flat coordinate bitwise
+//     the root's lo or hi on that axis, its other four extents bitwise the
+//     root's: the cube's six -- is a hull face, marked by a code (1 lo, 2 hi)
+//     in its record's last word.  Each of the products (plane - o) * inv that
+//     sweep_slab_flat would form from its record has, operand for operand,
+//     the bits of one of the six the root's test formed, so it is that
+//     product bit for bit.  sweep_cands<true> keeps the root's six products
+//     and a hull face (sweep_slab_hull) takes the one of its code on the flat
+//     axis and the root's pairs on the other two, through the same fmin_ /
+//     fmax_ calls in the same order with the same operand order: same
+//     operands, same operations, same bits, NaNs included.  The branch on the
+//     code is scalar.  A table without hull faces is walked by
+//     sweep_cands<false>, which keeps nothing from the root's test.
 //   * sweep_mask / sweep_leaves state the same predicate from need[] in two
 //     passes (box bits, then (sb & need[l]) == need[l] per leaf).  The device
 //     does not call them: they are the restatement the tests hold sweep_cands
@@ -154,16 +167,77 @@ PT_FN bool sweep_slab_flat(v3 o, v3 inv, SweepBox r) {
   const float tmax = fmin_(fmin_(fx, fy), fz);
   return tmin <= tmax && tmax >= 0.0f;
 }
+// The root's slab values: the six products (plane - o) * inv of its record,
+// the operands of slab's per-axis min and max.  A hull face (below) reads them
+// instead of computing its own.
+struct SweepRootVals {
+  float t0x, t0y, t0z, t1x, t1y, t1z;
+};
+PT_FN SweepRootVals sweep_root_vals(v3 o, v3 inv, SweepBox r) {
+  SweepRootVals R;
+  R.t0x = (r[0] - o.x) * inv.x, R.t0y = (r[1] - o.y) * inv.y, R.t0z = (r[2] - o.z) * inv.z;
+  R.t1x = (r[4] - o.x) * inv.x, R.t1y = (r[5] - o.y) * inv.y, R.t1z = (r[6] - o.z) * inv.z;
+  return R;
+}
+// slab() of the root's record from its products: slab's own tail.
+PT_FN bool sweep_root_pass(const SweepRootVals& R) {
+  const float tmin = fmax_(fmax_(fmin_(R.t0x, R.t1x), fmin_(R.t0y, R.t1y)), fmin_(R.t0z, R.t1z));
+  const float tmax = fmin_(fmin_(fmax_(R.t0x, R.t1x), fmax_(R.t0y, R.t1y)), fmax_(R.t0z, R.t1z));
+  return tmin <= tmax && tmax >= 0.0f;
+}
+// On the device the six products stay in registers from the root's test to
+// the flat loops, but not the six min/max formed from them: the kernel has no
+// registers to spare (80, 6 waves), and forming the four a face needs again
+// costs less than spilling them.  An empty asm the compiler cannot see through
+// keeps it from reusing the root test's.  The values are untouched.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PT_SWEEP_OPAQUE(x) __asm__ volatile("" : "+v"(x))
+#else
+#define PT_SWEEP_OPAQUE(x) ((void)0)
+#endif
+PT_FN void sweep_root_detach(SweepRootVals* R) {
+  PT_SWEEP_OPAQUE(R->t0x); PT_SWEEP_OPAQUE(R->t0y); PT_SWEEP_OPAQUE(R->t0z);
+  PT_SWEEP_OPAQUE(R->t1x); PT_SWEEP_OPAQUE(R->t1y); PT_SWEEP_OPAQUE(R->t1z);
+}
+// A hull face: a box flat on AXIS whose flat coordinate is bitwise the root's
+// lo (code 1) or hi (code 2) there and whose extents on the other two axes are
+// bitwise the root's (scene/small_sweep.h marks them in the record's last
+// word).  Every product sweep_slab_flat<AXIS> would form from its record has
+// the operands of one of the root's, so it is that product bit for bit.  The
+// rest is sweep_slab_flat's: same calls, same order, same operand order.
+template <int AXIS>
+PT_FN bool sweep_slab_hull(const SweepRootVals& R, uint32_t code) {
+  const float t0x = AXIS == 0 && code != 1u ? R.t1x : R.t0x, t1x = R.t1x;
+  const float t0y = AXIS == 1 && code != 1u ? R.t1y : R.t0y, t1y = R.t1y;
+  const float t0z = AXIS == 2 && code != 1u ? R.t1z : R.t0z, t1z = R.t1z;
+  const float nx = AXIS == 0 ? t0x : fmin_(t0x, t1x), fx = AXIS == 0 ? t0x : fmax_(t0x, t1x);
+  const float ny = AXIS == 1 ? t0y : fmin_(t0y, t1y), fy = AXIS == 1 ? t0y : fmax_(t0y, t1y);
+  const float nz = AXIS == 2 ? t0z : fmin_(t0z, t1z), fz = AXIS == 2 ? t0z : fmax_(t0z, t1z);
+  const float tmin = fmax_(fmax_(nx, ny), nz);
+  const float tmax = fmin_(fmin_(fx, fy), fz);
+  return tmin <= tmax && tmax >= 0.0f;
+}
+// One flat box of the sweep: the record's last word is 0 (sweep_slab_flat) or
+// a hull code.  The word is the same for every lane: a scalar branch.
+template <int AXIS>
+PT_FN bool sweep_flat_pass(v3 o, v3 inv, const SweepRootVals& R, SweepBox r) {
+  const uint32_t code = f2u(r[7]);
+  if (code != 0u) return sweep_slab_hull<AXIS>(R, code);
+  return sweep_slab_flat<AXIS>(o, inv, r);
+}
 // Bit l set iff leaf l (in visit order) is a candidate of the ray: no box that
 // fails the slab test has l in its under mask (the record's fourth word).
 // Box 0 is the root's and guards every leaf: when no ray at hand passes it (no
 // lane of the wave on the device) the other boxes are not tested and *none is
 // set: the walk has no candidate.  Equal to sweep_leaves(sweep_mask(...)) and
-// its *none for every ray, NaNs of 0 * inf included: both go through slab.
+// its *none for every ray, NaNs of 0 * inf included: both go through slab's
+// operations.
 //
-// sweep_fold is the sweep past the root's test: `root` is this ray's answer,
-// false in a lane that rides along because another lane of its wave passed.
-PT_FN uint32_t sweep_fold(v3 o, v3 inv, const SweepTable& t, bool root) {
+// sweep_fold_vals is the sweep past the root's test: R the root's values for
+// this ray (HULL: the hull faces read them), `root` its answer, false in a
+// lane that rides along because another lane of its wave passed.
+template <bool HULL>
+PT_FN uint32_t sweep_fold_vals(v3 o, v3 inv, const SweepTable& t, const SweepRootVals& R, bool root) {
   const SweepBoxP B = sweep_boxes(t);
   const SweepBox r0 = B[0];
   const uint32_t all = f2u(r0[3]);
@@ -180,31 +254,46 @@ PT_FN uint32_t sweep_fold(v3 o, v3 inv, const SweepTable& t, bool root) {
 #pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_FLAT_UNROLL)
   for (; b < e; ++b) {
     const SweepBox r = B[b];
-    fail |= sweep_slab_flat<0>(o, inv, r) ? 0u : f2u(r[3]);
+    fail |= (HULL ? sweep_flat_pass<0>(o, inv, R, r) : sweep_slab_flat<0>(o, inv, r)) ? 0u : f2u(r[3]);
   }
   e += (int)(cnt >> 16 & 0xffu);
 #pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_FLAT_UNROLL)
   for (; b < e; ++b) {
     const SweepBox r = B[b];
-    fail |= sweep_slab_flat<1>(o, inv, r) ? 0u : f2u(r[3]);
+    fail |= (HULL ? sweep_flat_pass<1>(o, inv, R, r) : sweep_slab_flat<1>(o, inv, r)) ? 0u : f2u(r[3]);
   }
   e += (int)(cnt >> 24 & 0xffu);
 #pragma clang loop vectorize(disable) unroll_count(PT_SWEEP_FLAT_UNROLL)
   for (; b < e; ++b) {
     const SweepBox r = B[b];
-    fail |= sweep_slab_flat<2>(o, inv, r) ? 0u : f2u(r[3]);
+    fail |= (HULL ? sweep_flat_pass<2>(o, inv, R, r) : sweep_slab_flat<2>(o, inv, r)) ? 0u : f2u(r[3]);
   }
   return all & ~fail;
 }
+PT_FN uint32_t sweep_fold(v3 o, v3 inv, const SweepTable& t, bool root) {
+  return sweep_fold_vals<true>(o, inv, t, sweep_root_vals(o, inv, sweep_boxes(t)[0]), root);
+}
+// HULL false: the sweep for a table known to hold no hull code (or whose codes
+// are to be ignored): every flat box through sweep_slab_flat, nothing kept
+// from the root's test.  The same answer for any table.
+template <bool HULL = true>
 PT_FN uint32_t sweep_cands(v3 o, v3 inv, const SweepTable& t, bool* none) {
-  const bool root = sweep_slab(o, inv, sweep_boxes(t)[0]);
+  SweepRootVals R = {};
+  bool root;
+  if constexpr (HULL) {
+    R = sweep_root_vals(o, inv, sweep_boxes(t)[0]);
+    root = sweep_root_pass(R);
+  } else {
+    root = sweep_slab(o, inv, sweep_boxes(t)[0]);
+  }
 #if defined(__HIP_DEVICE_COMPILE__)
   *none = __builtin_amdgcn_ballot_w64(root) == 0;
 #else
   *none = !root;
 #endif
   if (*none) return 0u;
-  return sweep_fold(o, inv, t, root);
+  if constexpr (HULL) sweep_root_detach(&R);
+  return sweep_fold_vals<HULL>(o, inv, t, R, root);
 }
 
 // Closest hit over the leaf mask: leaves in visit order, triangle records by

@@ -41,6 +41,8 @@ PT_OPT_WF_REFILL = 21
 PT_OPT_MIXED_LANES = 22
 PT_OPT_DENOISE_LDS = 23
 PT_OPT_SMALL_SWEEP = 24
+PT_OPT_CULL_TIGHT = 25
+PT_OPT_SWEEP_HULL = 26
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -52,7 +54,7 @@ EXPORTS = [
     "pt_launch_times_ms", "pt_reset_launch_times", "pt_selftest_math", "pt_selftest_exhaustive",
     "pt_scene_load_obj", "pt_scene_parse_obj", "pt_scene_from_arrays", "pt_scene_build_bvh",
     "pt_scene_counts", "pt_scene_copy", "pt_scene_upload", "pt_scene_free", "pt_pack_light",
-    "pt_default_camera", "pt_primary_cull_rects", "pt_scene_save", "pt_scene_load_cache",
+    "pt_default_camera", "pt_primary_cull_rects", "pt_primary_cull_rects_r", "pt_scene_save", "pt_scene_load_cache",
     "pt_progressive_camera", "pt_progressive_advance", "pt_readback_begin", "pt_readback_end", "pt_write_image",
     "pt_items_live", "pt_items_pack", "pt_items_unpack_all", "pt_render_packed", "pt_launch_span_ms",
     "pt_set_partition_slots", "pt_get_traced", "pt_wide_info", "pt_partition_items",
@@ -141,6 +143,8 @@ def lib():
             "pt_scene_free": ([vp], i32), "pt_pack_light": ([vp, vp, vp, vp, vp], i32),
             "pt_default_camera": ([vp], i32),
             "pt_primary_cull_rects": ([vp, i32, i32, vp, vp, vp, i32, vp, i32, ctypes.POINTER(i32)], i32),
+            "pt_primary_cull_rects_r": ([vp, i32, i32, vp, vp, vp, i32, ctypes.c_double, vp, i32, ctypes.POINTER(i32),
+                                         ctypes.POINTER(ctypes.c_float)], i32),
             "pt_scene_save": ([vp, ctypes.c_char_p], i32),
             "pt_progressive_camera": ([vp, vp, ctypes.POINTER(i32)], i32),
             "pt_progressive_advance": ([vp, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
@@ -340,6 +344,25 @@ def primary_cull_rects(camera_ubo, width, height, root_min, root_max, lights16, 
                                        l.ctypes.data if l.size else None, l.size // 16, out.ctypes.data,
                                        max_rects, ctypes.byref(n)), "pt_primary_cull_rects")
     return None if n.value < 0 else out[:n.value].copy()
+
+
+def primary_cull_rects_r(camera_ubo, width, height, root_min, root_max, lights16, radius_bound=-1.0, max_rects=8):
+    """pt_primary_cull_rects_r: (rectangles or None, u0) -- the rectangles
+    outside which no primary ray whose two Box-Muller radii are at most
+    radius_bound (negative: the kernel's tight bound) reaches the root box or
+    a light, and the kernel's threshold on the radius draws."""
+    cam = np.ascontiguousarray(camera_ubo, np.float32).reshape(16)
+    lo = np.ascontiguousarray(root_min, np.float32).reshape(3)
+    hi = np.ascontiguousarray(root_max, np.float32).reshape(3)
+    l = np.ascontiguousarray(lights16, np.float32).reshape(-1)
+    out = np.zeros((max_rects, 4), np.float32)
+    n = ctypes.c_int(0)
+    u0 = ctypes.c_float(0.0)
+    _check(lib().pt_primary_cull_rects_r(cam.ctypes.data, width, height, lo.ctypes.data, hi.ctypes.data,
+                                         l.ctypes.data if l.size else None, l.size // 16, float(radius_bound),
+                                         out.ctypes.data, max_rects, ctypes.byref(n), ctypes.byref(u0)),
+           "pt_primary_cull_rects_r")
+    return (None if n.value < 0 else out[:n.value].copy()), float(u0.value)
 
 
 def write_image(path, rgba, width, height, fmt="png"):

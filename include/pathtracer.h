@@ -41,7 +41,9 @@ extern "C" {
  * (pt_denoise_params, pt_denoise_default_params, pt_guide_ray,
  * pt_render_guide, pt_guide_device_ptr, pt_read_guide, pt_denoise,
  * pt_read_denoised, pt_denoise_host, PT_OPT_DENOISE_LDS); the sweep walk of
- * tiny scenes (pt_sweep_info, PT_OPT_SMALL_SWEEP). */
+ * tiny scenes (pt_sweep_info, PT_OPT_SMALL_SWEEP); the tight cull rectangles
+ * and the sweep's hull faces (pt_primary_cull_rects_r, PT_OPT_CULL_TIGHT,
+ * PT_OPT_SWEEP_HULL). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -577,6 +579,26 @@ int pt_dist_finalize(pt_context* ctx);
  * PT_OPT_COUNT_TRACED run the threaded walk either way.  Output is
  * identical. */
 #define PT_OPT_SMALL_SWEEP 24
+/* PT_OPT_SWEEP_HULL: the sweep table marks each flat box that is a face of
+ * the root box (its flat coordinate bitwise the root's lo or hi on that axis,
+ * its other four extents bitwise the root's: box.obj's six), and the walk
+ * tests such a box with the slab products the root's test has just formed
+ * instead of computing them again -- the same operands through the same
+ * operations, so the same bits.  1 (default) = on; 0 = the
+ * walk reads a table without the marks.  Output is identical. */
+#define PT_OPT_SWEEP_HULL 26
+/* PT_OPT_CULL_TIGHT: beside the primary-culling rectangles, which hold for
+ * every Box-Muller radius (at most 13.23), the host derives a second set for
+ * radii of at most 4.25 (pt_primary_cull_rects_r).  A pixel inside the first
+ * set but outside the second -- the margin of aperture parallax and jitter
+ * around every object -- can reach the scene or a light only with a radius
+ * above 4.25, which a draw has with probability 1.2e-4.  render_kernel makes
+ * a sample's four draws first and traces it for such a pixel only if one of
+ * the two radius draws is below the threshold; otherwise the sample is
+ * (0,0,0), which is what the trace would return.  1 (default)
+ * = on; 0 = every sample of a live pixel is traced.  Needs
+ * PT_OPT_PRIMARY_CULL; stats mode never skips.  Output is identical. */
+#define PT_OPT_CULL_TIGHT 25
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
@@ -594,6 +616,18 @@ int pt_last_kernel(pt_context* ctx, int* kernel);
 int pt_primary_cull_rects(const float camera_ubo[16], int width, int height, const float root_min[3],
                           const float root_max[3], const pt_area_light* lights, int n_lights, float* rects,
                           int max_rects, int* n_rects);
+/* The same derivation for samples whose two Box-Muller radii are at most
+ * radius_bound (0 to 13.25; negative = the kernel's tight bound, 4.25): outside
+ * the rectangles no primary ray with such radii hits the root box or a light.
+ * The kernel derives this tight set beside the one above (PT_OPT_CULL_TIGHT)
+ * and, for a pixel inside the loose set but outside the tight one, traces a
+ * sample only if one of its two radius draws u1 is below *u0 -- the least
+ * float for which every float u in [*u0, 1] has the kernel's
+ * sqrt(-2 log(max(1e-38, u))) at most 4.25 (u0 may be null).  *n_rects = -1 as
+ * above.  Pure host function. */
+int pt_primary_cull_rects_r(const float camera_ubo[16], int width, int height, const float root_min[3],
+                            const float root_max[3], const pt_area_light* lights, int n_lights, double radius_bound,
+                            float* rects, int max_rects, int* n_rects, float* u0);
 
 /* ---- instrumentation --------------------------------------------------- */
 /* Stats mode runs the reference-exhaustive traversal with counters (output is

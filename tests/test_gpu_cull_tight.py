@@ -1,0 +1,139 @@
+"""GPU: the per-sample skip of the tight cull rectangles (PT_OPT_CULL_TIGHT,
+csrc/pt_cull.h): frames with the option on and off are bitwise equal and equal
+to the oracle's, and the counting kernel shows that samples were skipped.
+
+The frame is the box at 320x180, 4 spp: 98 of its 326 live 16x4 pixel blocks
+lie wholly between the loose and the tight rectangles
+(test_cull_tight.test_blocks_in_the_margin), so whole waves take the skip,
+others take it lane by lane.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import ptamd
+import scenes
+from test_gpu_sweep import _same
+
+pytestmark = pytest.mark.gpu
+
+W, H, DEPTH, SSS = 320, 180, 4, 3
+
+
+@functools.lru_cache(maxsize=None)
+def _box():
+    v, i, n, _, _ = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh().arrays()
+    return v, i, n
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(first, nb, nranks=1, rank=0):
+    v, i, n = _box()
+    ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, first_batch=0,
+                      n_batches=first + nb, max_depth=DEPTH, sss_bounces=SSS, nranks=nranks, rank=rank)
+    ref.setflags(write=False)
+    return ref
+
+
+def _renderer(tight, lanes=1, cam=scenes.DEFAULT_CAMERA, count=False):
+    v, i, n = _box()
+    r = ptamd.Renderer(0)
+    r.set_option(ptamd.PT_OPT_CULL_TIGHT, tight)
+    r.set_option(ptamd.PT_OPT_SAMPLE_LANES, lanes)
+    if count:
+        r.set_option(ptamd.PT_OPT_COUNT_TRACED, 1)
+    r.upload_scene(v, i, n)
+    r.upload_lights(scenes.REFERENCE_LIGHT)
+    r.set_camera(cam)
+    r.set_params(DEPTH, SSS)
+    return r
+
+
+@pytest.mark.parametrize("lanes", [1, 2, 4])
+def test_skip_on_and_off_equal_the_oracle(lanes):
+    """A fresh accumulator (batches 0-3), then batches 4-7 on top of it (a
+    non-zero accumulator), then -- with PT_OPT_FRESH_BATCH0 -- batches 0-3
+    again over the stale frame."""
+    frames = {}
+    for tight in (1, 0):
+        r = _renderer(tight, lanes)
+        r.resize_and_clear(W, H)
+        r.render(0, 4)
+        a = r.read_accum()
+        r.render(4, 4)
+        b = r.read_accum()
+        r.set_option(ptamd.PT_OPT_FRESH_BATCH0, 1)
+        r.render(0, 4)
+        c = r.read_accum()
+        r.close()
+        frames[tight] = (a, b, c)
+    for k, what in enumerate(("batches 0-3", "batches 4-7 on top", "batches 0-3 over a stale frame")):
+        _same(frames[0][k], frames[1][k], f"lanes={lanes} {what}: PT_OPT_CULL_TIGHT 0 against 1")
+    _same(frames[1][0], _oracle(0, 4), f"lanes={lanes} batches 0-3 against the oracle")
+    _same(frames[1][1], _oracle(4, 4), f"lanes={lanes} batches 0-7 against the oracle")
+    _same(frames[1][2], _oracle(0, 4), f"lanes={lanes} fresh restart against the oracle")
+
+
+@pytest.mark.parametrize("rank", [0, 1])
+def test_two_rank_share(rank):
+    frames = {}
+    for tight in (1, 0):
+        r = _renderer(tight)
+        r.set_partition(2, rank)
+        r.resize_and_clear(W, H)
+        r.render(0, 4)
+        frames[tight] = r.read_accum()
+        r.close()
+    _same(frames[0], frames[1], f"rank {rank} of 2: PT_OPT_CULL_TIGHT 0 against 1")
+    ref = _oracle(0, 4, 2, rank).reshape(-1, 4)
+    own = ref[:, 3] != 0   # the oracle leaves the other rank's pixels untouched (0)
+    assert own.any() and not own.all()
+    _same(frames[1].reshape(-1, 4)[own], ref[own], f"rank {rank} of 2 against the oracle")
+
+
+@pytest.mark.parametrize("kernel", [ptamd.KERNEL_RECURSIVE, ptamd.KERNEL_WAVEFRONT])
+def test_counting_mode_shows_skipped_primaries(kernel):
+    counts, frames = {}, {}
+    for tight in (1, 0):
+        r = _renderer(tight, count=True)
+        r.set_option(ptamd.PT_OPT_KERNEL, kernel)
+        r.resize_and_clear(W, H)
+        r.reset_stats()
+        r.render(0, 4)
+        frames[tight] = r.read_accum()
+        counts[tight] = r.traced()
+        assert r.last_kernel() == kernel
+        r.close()
+    _same(frames[0], frames[1], "counting mode: PT_OPT_CULL_TIGHT 0 against 1")
+    _same(frames[1], _oracle(0, 4), "counting mode against the oracle")
+    print(f"kernel {kernel}: primaries on {counts[1]['primaries']}, off {counts[0]['primaries']}")
+    assert 0 < counts[1]["primaries"] < counts[0]["primaries"] <= W * H * 4
+    assert counts[1]["closest_walks"] < counts[0]["closest_walks"]
+
+
+def test_no_guarantee_no_skip():
+    """A camera inside the box: neither derivation gives rectangles, both
+    settings trace every sample."""
+    cam = scenes.camera((0.0, 0.0, 0.5))
+    lo, hi = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
+    assert ptamd.primary_cull_rects(cam, W, H, lo, hi, scenes.REFERENCE_LIGHT) is None
+    assert ptamd.primary_cull_rects_r(cam, W, H, lo, hi, scenes.REFERENCE_LIGHT)[0] is None
+    frames = {}
+    for tight in (1, 0):
+        r = _renderer(tight, cam=cam, count=True)
+        r.resize_and_clear(W, H)
+        r.reset_stats()
+        r.render(0, 2)
+        frames[tight] = r.read_accum()
+        assert r.traced()["primaries"] == W * H * 2
+        r.close()
+    _same(frames[0], frames[1], "camera inside the box: PT_OPT_CULL_TIGHT 0 against 1")
+
+
+def test_option_range():
+    r = ptamd.Renderer(0)
+    with pytest.raises(ptamd.PTError, match="PT_OPT_CULL_TIGHT"):
+        r.set_option(ptamd.PT_OPT_CULL_TIGHT, 2)
+    r.close()
