@@ -408,6 +408,14 @@ struct pt_context {
   size_t denoised_cap = 0;
   int denoised_w = 0, denoised_h = 0;  // size of the image d_denoised holds (0: none yet)
   int opt_denoise_lds = 1;             // PT_OPT_DENOISE_LDS
+  // per-pixel luminance moments (PT_OPT_MOMENTS) and pt_denoise_var's variance planes:
+  int opt_moments = 0;
+  float2* d_moments = nullptr;         // W x H {m1, m2}
+  size_t moments_cap = 0;              // pixels d_moments holds
+  bool moments_valid = false;          // d_moments holds batches 0..moments_n-1 of the current frame
+  uint32_t moments_n = 0;
+  float* d_var[2] = {nullptr, nullptr};
+  size_t var_cap[2] = {0, 0};
   DistState* dist = nullptr;           // pt_dist_init
   pt_group* group = nullptr;           // pt_create_multi: every call goes to the group (pt_group.cpp)
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -1042,7 +1050,35 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
   if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
   if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
+  // PT_OPT_MOMENTS: the launches below fold the luminance moments too; the image counts as valid
+  // (batches 0..n-1, in order) when this render starts at 0 or continues at n
+  bool fold_moments = false, moments_cont = false;
+  if (c->opt_moments) {
+    if (pack_out) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with pt_render_packed or pt_dist_run");
+    if (c->nranks > 1) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not on a partition of more than one rank");
+    if (c->stats_mode) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not in stats mode");
+    if (c->opt_count) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with PT_OPT_COUNT_TRACED");
+    const size_t n = (size_t)c->width * c->height;
+    if (n_batches > 0) {
+      if (!c->d_moments || c->moments_cap < n) {
+        { const int rc_ = quiesce(c); if (rc_) return rc_; }
+        dev_free(c->d_moments);
+        c->moments_cap = 0;
+        c->moments_valid = false;
+        PT_HIP(hipSetDevice(c->device));
+        PT_HIP(hipMalloc((void**)&c->d_moments, n * sizeof(float2)));
+        c->moments_cap = n;
+        PT_HIP(hipMemsetAsync(c->d_moments, 0, n * sizeof(float2), c->stream));
+      }
+      fold_moments = true;
+      moments_cont = first_batch == 0 || (c->moments_valid && first_batch == c->moments_n);
+      c->moments_valid = false;   // until the launch is enqueued
+    }
+  } else if (n_batches > 0 && !pack_out) {
+    c->moments_valid = false;   // the accumulator moves on without them
+  }
   ptd::RenderParams p;
+  p.moments = fold_moments ? c->d_moments : nullptr;
   p.wide = nullptr;
   p.wide_tris = nullptr;
   p.wide_rank_of = nullptr;
@@ -1276,6 +1312,9 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
     const int ro = order_shared(c);
     if (ro) return ro;
   }
+  // a launch from batch 0 starts every pixel's moments at +0; the kernels write the live pixels only
+  if (fold_moments && first_batch == 0)
+    PT_HIP(hipMemsetAsync(c->d_moments, 0, (size_t)c->width * c->height * sizeof(float2), c->stream));
   if (wf) {
     const long long tiles = p.n_tiles;
     const long long items = p.items ? p.n_items : tiles * p.spl;
@@ -1337,6 +1376,10 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
     c->timed = true;
   }
   c->launch_n++;
+  if (fold_moments) {
+    c->moments_valid = moments_cont;
+    c->moments_n = moments_cont ? first_batch + n_batches : 0;
+  }
   // the state of the culled items after this launch (culled_state)
   if (culled_launch && !culled_skipped) {
     const bool same = c->culled_state == 2 && c->culled_buf == c->d_accum && c->culled_key == c->items_key;
@@ -1476,6 +1519,9 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_dn_scratch[0]);
   dev_free(c->d_dn_scratch[1]);
   dev_free(c->d_denoised);
+  dev_free(c->d_moments);
+  dev_free(c->d_var[0]);
+  dev_free(c->d_var[1]);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1711,6 +1757,15 @@ int pt_set_partition_slots(pt_context* c, int nranks, int rank, const int* slots
   return PT_OK;
 }
 
+// The moments image back to "no batches": zeros, on the context's stream.
+static int moments_zero(pt_context* c) {
+  c->moments_valid = false;
+  c->moments_n = 0;
+  const size_t n = (size_t)c->width * c->height;
+  if (c->d_moments && n > 0 && c->moments_cap >= n) PT_HIP(hipMemsetAsync(c->d_moments, 0, n * sizeof(float2), c->stream));
+  return PT_OK;
+}
+
 int pt_clear_accum(pt_context* c) {
   if (c && c->group) return ptg::clear_accum(c->group);
   if (!c) return fail(PT_ERR_INVALID, "null context");
@@ -1726,6 +1781,10 @@ int pt_clear_accum(pt_context* c) {
                            c->d_parts + (size_t)c->rank * ptd::kMaxSlots, c->stream));
   c->culled_state = 1;
   c->culled_buf = c->d_accum;
+  {
+    const int rz = moments_zero(c);
+    if (rz) return rz;
+  }
   return mark_shared(c);
 }
 
@@ -1762,7 +1821,7 @@ int pt_bind_accum(pt_context* c, void* ptr, int w, int h) {
   c->width = w;
   c->height = h;
   c->culled_state = 0;   // the caller's buffer: its content is not known
-  return PT_OK;
+  return moments_zero(c);
 }
 
 void* pt_accum_device_ptr(pt_context* c) {
@@ -1799,6 +1858,7 @@ int pt_render_packed(pt_context* c, uint32_t n_batches, void* packed, const void
   if (!c || !packed) return fail(PT_ERR_INVALID, "null argument");
   if (((uintptr_t)packed) & 15) return fail(PT_ERR_INVALID, "packed buffer must be 16-B aligned");
   if (c->stats_mode) return fail(PT_ERR_UNSUPPORTED, "stats mode renders into the accumulation buffer");
+  if (c->opt_moments) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with pt_render_packed");
   Assembly as;
   if (gathered) {
     if (!frame) return fail(PT_ERR_INVALID, "gathered slots without a frame");
@@ -2079,7 +2139,10 @@ int pt_denoise(pt_context* c, const pt_denoise_params* params, const void* src, 
     c->denoised_w = w;
     c->denoised_h = h;
   }
-  if (out == c->d_accum) c->culled_state = 0;   // the accumulation buffer given as the destination
+  if (out == c->d_accum) {   // the accumulation buffer given as the destination
+    c->culled_state = 0;
+    c->moments_valid = false;
+  }
   return mark_shared(c);
 }
 
@@ -2091,6 +2154,138 @@ int pt_read_denoised(pt_context* c, float* rgba, size_t n) {
   return read_image(c, c->d_denoised, c->denoised_w, c->denoised_h, rgba, n);
 }
 
+// ---- luminance moments and the variance-guided filter (pt_denoise.h) --------
+static bool moments_ready(const pt_context* c) {
+  return c->opt_moments && c->moments_valid && c->d_moments && c->moments_n >= 1;
+}
+
+void* pt_moments_device_ptr(pt_context* c) {
+  if (!c || c->group || !moments_ready(c)) return nullptr;
+  return (void*)c->d_moments;
+}
+
+int pt_read_moments(pt_context* c, float* out, size_t n, uint32_t* n_samples) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_moments: not on a multi-device context (pt_create_multi)");
+  if (!c || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (!c->opt_moments || !c->d_moments || c->moments_cap < (size_t)c->width * c->height)
+    return fail(PT_ERR_INVALID, "no moments image (PT_OPT_MOMENTS, then a render)");
+  const size_t need = (size_t)c->width * c->height * 2;
+  if (n < need) return fail(PT_ERR_INVALID, "output buffer too small: need " + std::to_string(need) + " floats");
+  PT_HIP(hipSetDevice(c->device));
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(hipMemcpyAsync(out, c->d_moments, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(hipStreamSynchronize(c->stream));
+  if (n_samples) *n_samples = moments_ready(c) ? c->moments_n : 0u;   // 0: not batches 0..n-1 in order
+  return PT_OK;
+}
+
+int pt_denoise_var_default_params(pt_denoise_var_params* out) {
+  if (!out) return fail(PT_ERR_INVALID, "null argument");
+  out->iterations = 4;
+  out->sigma_lum = 1.5f;
+  out->sigma_normal = 1.0f;
+  out->sigma_depth = 1.0f;
+  return PT_OK;
+}
+
+static int denoise_var_params(const pt_denoise_var_params* in, pt_denoise_var_params* p) {
+  if (in)
+    *p = *in;
+  else
+    (void)pt_denoise_var_default_params(p);
+  if (!ptdn::var_params_ok(p->iterations, p->sigma_lum, p->sigma_normal, p->sigma_depth))
+    return fail(PT_ERR_INVALID, "pt_denoise_var_params: iterations 1-6; sigmas finite, > 0 and with a finite non-zero square");
+  return PT_OK;
+}
+
+int pt_denoise_var_host(const float* rgba, const float* moments, uint32_t n_samples, const float* guide, int w, int h,
+                        const pt_denoise_var_params* params, float* out) {
+  if (!rgba || !moments || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
+  if (n_samples < 2) return fail(PT_ERR_INVALID, "pt_denoise_var: the variance of the mean needs at least 2 samples");
+  pt_denoise_var_params p;
+  const int rp = denoise_var_params(params, &p);
+  if (rp) return rp;
+  const size_t n = (size_t)w * (size_t)h;
+  std::vector<float4> g(n), a(n), b(n);
+  std::vector<float> va(n), vb(n);
+  memcpy(g.data(), guide, n * sizeof(float4));
+  memcpy(a.data(), rgba, n * sizeof(float4));
+  for (size_t i = 0; i < n; ++i) va[i] = ptdn::var_of_mean(moments[2 * i], moments[2 * i + 1], n_samples);
+  const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
+  for (int i = 0; i < p.iterations; ++i) {
+    const ptdn::VarImageFetch fetch = {a.data(), g.data(), va.data(), w};
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) {
+        const ptdn::VarOut o = ptdn::atrous_var_pixel(fetch, w, h, x, y, 1 << i, p.sigma_lum, sn2, sz2);
+        b[(size_t)y * w + x] = o.c;
+        vb[(size_t)y * w + x] = o.v;
+      }
+    a.swap(b);
+    va.swap(vb);
+  }
+  memcpy(out, a.data(), n * sizeof(float4));
+  return PT_OK;
+}
+
+int pt_denoise_var(pt_context* c, const pt_denoise_var_params* params, void* dst) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_var: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  pt_denoise_var_params p;
+  const int rp = denoise_var_params(params, &p);
+  if (rp) return rp;
+  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
+  if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
+  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
+  if (!moments_ready(c)) return fail(PT_ERR_INVALID, "pt_denoise_var: no valid moments (PT_OPT_MOMENTS, then a render from batch 0)");
+  if (c->moments_n < 2) return fail(PT_ERR_INVALID, "pt_denoise_var: the variance of the mean needs at least 2 samples");
+  if (((uintptr_t)dst) & 15) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
+  if (dst && (float4*)dst == c->d_accum) return fail(PT_ERR_INVALID, "pt_denoise_var: source and destination must differ");
+  PT_HIP(hipSetDevice(c->device));
+  if (!c->guide_valid) {
+    const int rg = pt_render_guide(c);
+    if (rg) return rg;
+  }
+  const int w = c->width, h = c->height;
+  const size_t n = (size_t)w * h;
+  for (int k = 0; k < 2 && k < p.iterations - 1; ++k) {
+    const int rs = grow_image(c, &c->d_dn_scratch[k], &c->dn_scratch_cap[k], n);
+    if (rs) return rs;
+  }
+  for (int k = 0; k < 2; ++k) {   // the variance planes: var0 in [0], pass i from [i & 1] to [(i + 1) & 1]
+    if (c->d_var[k] && c->var_cap[k] >= n) continue;
+    { const int rc_ = quiesce(c); if (rc_) return rc_; }
+    dev_free(c->d_var[k]);
+    c->var_cap[k] = 0;
+    PT_HIP(hipMalloc((void**)&c->d_var[k], n * sizeof(float)));
+    c->var_cap[k] = n;
+  }
+  float4* out = (float4*)dst;
+  if (!out) {
+    c->denoised_w = c->denoised_h = 0;
+    const int rd = grow_image(c, &c->d_denoised, &c->denoised_cap, n);
+    if (rd) return rd;
+    out = c->d_denoised;
+  }
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(ptd::launch_moments_var(c->d_moments, c->d_var[0], w, h, c->moments_n, c->stream));
+  const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
+  const float4* cur = c->d_accum;
+  for (int i = 0; i < p.iterations; ++i) {
+    float4* to = i == p.iterations - 1 ? out : c->d_dn_scratch[i & 1];
+    PT_HIP(ptd::launch_atrous_var(cur, c->d_var[i & 1], c->d_guide, to, c->d_var[(i + 1) & 1], w, h, 1 << i, p.sigma_lum,
+                                  sn2, sz2, c->opt_denoise_lds != 0 && i < 2, c->stream));
+    cur = to;
+  }
+  if (!dst) {
+    c->denoised_w = w;
+    c->denoised_h = h;
+  }
+  return mark_shared(c);
+}
+
 int pt_last_kernel(pt_context* c, int* kernel) {
   if (c && c->group) return ptg::last_kernel(c->group, kernel);
   if (!c || !kernel) return fail(PT_ERR_INVALID, "null argument");
@@ -2099,6 +2294,9 @@ int pt_last_kernel(pt_context* c, int* kernel) {
 }
 
 int pt_set_option(pt_context* c, int key, int value) {
+  if (c && c->group && key == PT_OPT_MOMENTS && value != 0)
+    return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not on a multi-device context (pt_create_multi)");
+  if (c && c->group && key == PT_OPT_MOMENTS) return PT_OK;
   if (c && c->group) return ptg::set_option(c->group, key, value);
   if (!c) return fail(PT_ERR_INVALID, "null context");
   switch (key) {
@@ -2198,6 +2396,11 @@ int pt_set_option(pt_context* c, int key, int value) {
     case PT_OPT_SWEEP_HULL:
       if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_SWEEP_HULL takes 0 or 1");
       c->opt_sweep_hull = value;
+      return PT_OK;
+    case PT_OPT_MOMENTS:
+      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_MOMENTS takes 0 or 1");
+      if (value != c->opt_moments) c->moments_valid = false;
+      c->opt_moments = value;
       return PT_OK;
     case PT_OPT_GROUP_EXCHANGE:
     case PT_OPT_GROUP_CHECK:
@@ -3051,6 +3254,7 @@ static void dist_mark_assembled(DistState* d, const void* frame, const std::vect
 int pt_dist_run(pt_context* c, uint32_t n_batches, int n_frames, int n_streams, void* frames, int n_frame_bufs) {
   if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_run: not on a multi-device context (pt_create_multi)");
   if (!c) return fail(PT_ERR_INVALID, "null context");
+  if (c->opt_moments) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with pt_dist_run");
   DistState* d = c->dist;
   if (!d || !d->ready) return fail(PT_ERR_INVALID, "pt_dist_run: no communicator (pt_dist_init)");
   if (n_frames < 0 || n_batches == 0) return fail(PT_ERR_INVALID, "pt_dist_run: bad frame or batch count");

@@ -1,5 +1,6 @@
 // pt_denoise.hip — the edge-avoiding a-trous filter's pass kernels
-// (pt_denoise); the filter's statement is pt_denoise.h, shared with the host.
+// (pt_denoise) and those of the variance-guided filter (pt_denoise_var, below);
+// the filters' statements are pt_denoise.h, shared with the host.
 //
 // One pixel per lane, 16x16 pixels per workgroup, a wave a 16x4 strip: the
 // lanes of a tile row read 256 consecutive bytes of each image per tap.
@@ -62,7 +63,101 @@ __global__ __launch_bounds__(256) void atrous_staged_kernel(const float4* __rest
   dst[(size_t)y * (size_t)W + (size_t)x] = atrous_pixel(fetch, W, H, x, y, STEP, s);
 }
 
+// ---- the variance-guided filter (pt_denoise_var, pt_denoise.h) --------------
+// The same two shapes with a float variance plane beside the colour; the 3x3
+// prefilter of the variance is part of the pass (nine 4-B taps around the
+// pixel, inside the halo the staged kernel holds anyway).
+__global__ __launch_bounds__(256) void moments_var_kernel(const float2* __restrict__ moments, float* __restrict__ var,
+                                                          size_t n, uint32_t n_samples) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float2 m = moments[i];
+  var[i] = var_of_mean(m.x, m.y, n_samples);
+}
+
+__global__ __launch_bounds__(256) void atrous_var_kernel(const float4* __restrict__ src, const float* __restrict__ vsrc,
+                                                         const float4* __restrict__ guide, float4* __restrict__ dst,
+                                                         float* __restrict__ vdst, int W, int H, int step,
+                                                         float sigma_lum, float sn2, float sz2) {
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const VarImageFetch fetch = {src, guide, vsrc, W};
+  const VarOut o = atrous_var_pixel(fetch, W, H, x, y, step, sigma_lum, sn2, sz2);
+  const size_t i = (size_t)y * (size_t)W + (size_t)x;
+  dst[i] = o.c;
+  vdst[i] = o.v;
+}
+
+template <int STEP>
+struct VarTileFetch {
+  static constexpr int kSide = 16 + 4 * STEP;
+  const float4* color;   // LDS, as TileFetch
+  const float4* guide;
+  const float* variance;
+  int x0, y0;
+  __device__ inline void operator()(int qx, int qy, float4* c, float4* g, float* v) const {
+    const int i = (qy - y0) * kSide + (qx - x0);
+    *c = color[i];
+    *g = guide[i];
+    *v = variance[i];
+  }
+  __device__ inline float var(int qx, int qy) const { return variance[(qy - y0) * kSide + (qx - x0)]; }
+};
+
+template <int STEP>
+__global__ __launch_bounds__(256) void atrous_var_staged_kernel(const float4* __restrict__ src,
+                                                                const float* __restrict__ vsrc,
+                                                                const float4* __restrict__ guide,
+                                                                float4* __restrict__ dst, float* __restrict__ vdst,
+                                                                int W, int H, float sigma_lum, float sn2, float sz2) {
+  constexpr int kSide = VarTileFetch<STEP>::kSide;
+  __shared__ float4 tc[kSide * kSide], tg[kSide * kSide];
+  __shared__ float tv[kSide * kSide];
+  const int x0 = (int)blockIdx.x * 16 - 2 * STEP, y0 = (int)blockIdx.y * 16 - 2 * STEP;
+  for (int i = (int)threadIdx.x; i < kSide * kSide; i += 256) {
+    const int gx = x0 + i % kSide, gy = y0 + i / kSide;
+    if (gx >= 0 && gx < W && gy >= 0 && gy < H) {   // atrous_var_pixel never fetches the others
+      const size_t g = (size_t)gy * (size_t)W + (size_t)gx;
+      tc[i] = src[g];
+      tg[i] = guide[g];
+      tv[i] = vsrc[g];
+    }
+  }
+  __syncthreads();
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const VarTileFetch<STEP> fetch = {tc, tg, tv, x0, y0};
+  const VarOut o = atrous_var_pixel(fetch, W, H, x, y, STEP, sigma_lum, sn2, sz2);
+  const size_t i = (size_t)y * (size_t)W + (size_t)x;
+  dst[i] = o.c;
+  vdst[i] = o.v;
+}
+
 }  // namespace
+
+hipError_t launch_moments_var(const float2* moments, float* var, int width, int height, uint32_t n_samples,
+                              hipStream_t stream) {
+  if (width <= 0 || height <= 0 || n_samples < 2) return hipErrorInvalidValue;
+  const size_t n = (size_t)width * (size_t)height;
+  moments_var_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(moments, var, n, n_samples);
+  return hipGetLastError();
+}
+
+hipError_t launch_atrous_var(const float4* src, const float* vsrc, const float4* guide, float4* dst, float* vdst,
+                             int width, int height, int step, float sigma_lum, float sn2, float sz2, bool staged,
+                             hipStream_t stream) {
+  if (width <= 0 || height <= 0 || step < 1) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+  if (staged && step == 1)
+    atrous_var_staged_kernel<1><<<grid, 256, 0, stream>>>(src, vsrc, guide, dst, vdst, width, height, sigma_lum, sn2, sz2);
+  else if (staged && step == 2)
+    atrous_var_staged_kernel<2><<<grid, 256, 0, stream>>>(src, vsrc, guide, dst, vdst, width, height, sigma_lum, sn2, sz2);
+  else
+    atrous_var_kernel<<<grid, 256, 0, stream>>>(src, vsrc, guide, dst, vdst, width, height, step, sigma_lum, sn2, sz2);
+  return hipGetLastError();
+}
 
 hipError_t launch_atrous(const float4* src, const float4* guide, float4* dst, int width, int height, int step,
                          float sc2, float sn2, float sz2, bool staged, hipStream_t stream) {

@@ -163,6 +163,11 @@ struct RenderParams {
   // per 16x4 part of the frame (y / 4 * blocks_x + x / 16): the summed wave
   // durations of the launch's live workgroups in GPU wall-clock ticks, or null
   unsigned* cost_out = nullptr;
+  // luminance moments (PT_OPT_MOMENTS): float2 {m1, m2} per pixel of the frame, folded beside the colour
+  // by the MOMENTS instantiations (launch_render / launch_wavefront pick them when this is set); the live
+  // pixels only -- the host zeroes the image before a launch from batch 0, and a culled pixel's fold of
+  // L = +0 into +0 is +0.  Last member: the layout the other instantiations read does not move
+  float2* moments = nullptr;
 };
 constexpr int kMixShift = 24;
 constexpr int kMaxCullRects = 8;
@@ -239,6 +244,14 @@ hipError_t launch_guide(const RenderParams& p, float4* guide, bool lds_scene, hi
 // staged: the tile and its halo go through LDS (steps 1 and 2 only).
 hipError_t launch_atrous(const float4* src, const float4* guide, float4* dst, int width, int height, int step,
                          float sc2, float sn2, float sz2, bool staged, hipStream_t stream);
+// The variance-guided filter (pt_denoise.h atrous_var_pixel): var0 from the
+// moments of n_samples >= 2 samples, then one pass from (src, vsrc) to (dst,
+// vdst), all four distinct; staged as above.
+hipError_t launch_moments_var(const float2* moments, float* var, int width, int height, uint32_t n_samples,
+                              hipStream_t stream);
+hipError_t launch_atrous_var(const float4* src, const float* vsrc, const float4* guide, float4* dst, float* vdst,
+                             int width, int height, int step, float sigma_lum, float sn2, float sz2, bool staged,
+                             hipStream_t stream);
 // lanes of the wide walk's persistent grid on this device (overflow areas to allocate)
 long long wide_trace_lanes();
 // workgroups of the LDS-staged render kernel resident on this device at once

@@ -919,7 +919,10 @@ __device__ unsigned long long g_wg_trace[kWgTraceCap][4];
 // has hull faces (P.sweep_hull) and the walk reuses the root's slab products
 // for them; a table without any runs SWEEP 1, the walk that keeps nothing
 // from the root's test.
-template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0>
+// MOMENTS (PT_OPT_MOMENTS; never with STATS or CNT): the lane that folds a
+// pixel's red also folds the sample luminances L and L * L into P.moments, in
+// batch order with the colour's own step (fold_one).
+template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0, bool MOMENTS = false>
 #ifndef PT_RENDER_MIN_BLOCKS
 #define PT_RENDER_MIN_BLOCKS 5
 #endif
@@ -983,7 +986,9 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
   // the colour hand-off (4 floats) -- never both at once
   static_assert(!SWEEP || (LDS && !STATS && !CNT), "the sweep walk is the plain LDS kernel's");
   constexpr int kQueue = SWEEP ? 0 : kCand;   // the sweep walk queues nothing
-  __shared__ int cand_buf[4][kQueue + (kPark > 4 ? kPark : 4)][64];
+  static_assert(!MOMENTS || (!STATS && !CNT), "moments: the plain kernels only");
+  constexpr int kHand = MOMENTS ? 5 : 4;              // floats handed off per sample: the colour, then L
+  __shared__ int cand_buf[4][kQueue + (kPark > kHand ? kPark : kHand)][64];
   int* cand = &cand_buf[wave][0][lane];
   float* colw = (float*)&cand_buf[wave][kQueue][0];   // colour hand-off, [channel][lane]
   const int q = wave * (64 / spl) + lane / spl;       // pixel within the workgroup
@@ -1042,6 +1047,15 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
   // A culled pixel's colours are all (0,0,0,1): its lanes fold them without
   // the colour hand-off (fold_constant), the live pixels' lanes below.
   if (!live && active) fold_constant(P, acc, spl, j);
+  // the pixel's moments, on its first lane: a launch from batch 0 starts from +0 (m * 0 + L = L)
+  float mom1 = 0.0f, mom2 = 0.0f;
+  if constexpr (MOMENTS) {
+    if (active && live && j == 0 && P.first_batch != 0) {
+      const float2 m = P.moments[pix];
+      mom1 = m.x;
+      mom2 = m.y;
+    }
+  }
   if (!wg_live) {   // uniform per workgroup; stats mode never culls
     emit_lane(P, active, pix, q, acc, spl, j);
     return;
@@ -1128,6 +1142,11 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
         acc[1] = fold_one(acc[1], col4.y, batch);
         acc[2] = fold_one(acc[2], col4.z, batch);
         acc[3] = fold_one(acc[3], col4.w, batch);
+        if constexpr (MOMENTS) {
+          const float L = ptdn::lum(col4.x, col4.y, col4.z);
+          mom1 = fold_one(mom1, L, batch);
+          mom2 = fold_one(mom2, L * L, batch);
+        }
       }
       continue;
      }
@@ -1136,6 +1155,7 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
      colw[64 + lane] = col4.y;
      colw[128 + lane] = col4.z;
      colw[192 + lane] = col4.w;
+     if constexpr (MOMENTS) colw[256 + lane] = ptdn::lum(col4.x, col4.y, col4.z);
      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
      __builtin_amdgcn_wave_barrier();
      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1148,6 +1168,13 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch)
           if (ch % spl == j) acc[ch] = fold_one(acc[ch], cc[ch * 64], batch);
+        if constexpr (MOMENTS) {
+          if (j == 0) {
+            const float L = cc[256];
+            mom1 = fold_one(mom1, L, batch);
+            mom2 = fold_one(mom2, L * L, batch);
+          }
+        }
       }
      }
      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1156,6 +1183,9 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
     }
   }
   emit_lane(P, active, pix, q, acc, spl, j);
+  if constexpr (MOMENTS) {
+    if (active && live && j == 0) P.moments[pix] = make_float2(mom1, mom2);
+  }
   if (!STATS && P.cost_out && lane == 0) {
     // the wave's pixels lie in one 16x4 part: its first pixel row / 4
     const int part_row = (gy0 + wave * (64 / spl) / 16) >> 2;
@@ -2796,6 +2826,7 @@ __global__ __launch_bounds__(256, PT_WF_TAIL_MIN_BLOCKS) void wf_tail_kernel(Ren
 }
 
 // Running mean (:467-469) of each pixel's samples, in batch order.
+template <bool MOMENTS>
 __global__ __launch_bounds__(256) void wf_fold_kernel(RenderParams P, WfBuffers B, long long n_pix, long long pp0) {
   const long long pp = pp0 + (long long)blockIdx.x * 256 + threadIdx.x;   // pixels [pp0, pp0 + n_pix)
   if (pp - pp0 >= n_pix) return;
@@ -2807,6 +2838,16 @@ __global__ __launch_bounds__(256) void wf_fold_kernel(RenderParams P, WfBuffers 
     const float4 a = *dst;
     acc[0] = a.x; acc[1] = a.y; acc[2] = a.z; acc[3] = a.w;
   }
+  float mom1 = 0.0f, mom2 = 0.0f;   // MOMENTS: the luminance moments, the same step (render_kernel)
+  float2* mdst = nullptr;
+  if constexpr (MOMENTS) {
+    mdst = P.moments + (size_t)py * (size_t)P.width + (size_t)px;
+    if (P.first_batch != 0) {
+      const float2 m = *mdst;
+      mom1 = m.x;
+      mom2 = m.y;
+    }
+  }
   const float4* col = B.colors + (size_t)pp * P.n_batches;
   for (uint32_t s = 0; s < P.n_batches; ++s) {
     const float4 c = col[s];
@@ -2816,7 +2857,13 @@ __global__ __launch_bounds__(256) void wf_fold_kernel(RenderParams P, WfBuffers 
     acc[1] = (acc[1] * fb + c.y) / fb1;
     acc[2] = (acc[2] * fb + c.z) / fb1;
     acc[3] = (acc[3] * fb + 1.0f) / fb1;
+    if constexpr (MOMENTS) {
+      const float L = ptdn::lum(c.x, c.y, c.z);
+      mom1 = (mom1 * fb + L) / fb1;
+      mom2 = (mom2 * fb + L * L) / fb1;
+    }
   }
+  if constexpr (MOMENTS) *mdst = make_float2(mom1, mom2);
   *dst = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
@@ -2991,8 +3038,12 @@ hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipS
     return hipErrorInvalidValue;
   const size_t lds = sweep ? sweep_lds_bytes(p) : lds_scene ? scene_lds_bytes(p) : 0;
   if (lds > kMaxSceneLds) return hipErrorInvalidValue;
+  if (p.moments && (stats || cnt || p.pack_out)) return hipErrorInvalidValue;
   void (*kern)(RenderParams);
-  if (sweep)
+  if (p.moments)   // PT_OPT_MOMENTS: the same choice among the MOMENTS instantiations
+    kern = sweep ? (p.sweep_hull ? render_kernel<false, true, false, 2, true> : render_kernel<false, true, false, 1, true>)
+                 : (lds_scene ? render_kernel<false, true, false, 0, true> : render_kernel<false, false, false, 0, true>);
+  else if (sweep)
     kern = p.sweep_hull ? render_kernel<false, true, false, 2> : render_kernel<false, true, false, 1>;
   else if (cnt)
     kern = lds_scene ? render_kernel<false, true, true> : render_kernel<false, false, true>;
@@ -3047,6 +3098,7 @@ long long wide_trace_lanes() {
 
 hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds_scene, hipStream_t stream, bool cnt,
                             hipStream_t stream2, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  if (p0.moments && cnt) return hipErrorInvalidValue;
   if (p0.spl != 1 && p0.spl != 2 && p0.spl != 4 && p0.spl != 8) return hipErrorInvalidValue;
   if (p0.n_batches == 0) return hipSuccess;
   const int per = 256 / p0.spl;
@@ -3162,7 +3214,10 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
       cur ^= 1;
     }
     for (int h = 0; h < H; ++h)
-      wf_fold_kernel<<<(unsigned)((pxn[h] + 255) / 256), 256, 0, sh[h]>>>(ph[h], bh[h], pxn[h], px0[h]);
+      if (p.moments)
+        wf_fold_kernel<true><<<(unsigned)((pxn[h] + 255) / 256), 256, 0, sh[h]>>>(ph[h], bh[h], pxn[h], px0[h]);
+      else
+        wf_fold_kernel<false><<<(unsigned)((pxn[h] + 255) / 256), 256, 0, sh[h]>>>(ph[h], bh[h], pxn[h], px0[h]);
     if (split) {
       e = hipEventRecord(ev_join, stream2);
       if (e == hipSuccess) e = hipStreamWaitEvent(stream, ev_join, 0);

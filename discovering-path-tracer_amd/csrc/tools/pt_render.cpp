@@ -6,7 +6,7 @@
 //   pt_render scene.obj [-w 1920] [-h 1080] [-spp 8] [-depth 4] [-sss 3]
 //             [-fused] [-o out.pfm] [-png out.png] [-device 0 | -devices 0,1,..]
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
-//             [-denoise] [-guide normals.pfm]
+//             [-denoise | -denoise-var] [-guide normals.pfm]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -18,7 +18,10 @@
 // every other call is unchanged.
 // -denoise filters the final image on the device (pt_denoise, default
 // parameters) before -o / -png are written; -guide writes the first-hit
-// normals of the guide image as a PFM.  Both need a single-device context.
+// normals of the guide image as a PFM.  -denoise-var turns PT_OPT_MOMENTS on
+// before rendering and filters with the variance-guided filter
+// (pt_denoise_var, default parameters; at least 2 spp).  All three need a
+// single-device context.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -42,7 +45,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr,
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
-            "       [-denoise] [-guide normals.pfm] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
+            "       [-denoise | -denoise-var] [-guide normals.pfm] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
             "       [-progressive N [-chunk K] [-orbit-at B]]\n",
             argv[0]);
     return 2;
@@ -53,7 +56,7 @@ int main(int argc, char** argv) {
   bool fused = false;
   int progressive = 0, chunk = 8, orbit_at = -1;
   std::string cache_path, png_path, guide_path;
-  bool denoise = false;
+  bool denoise = false, denoise_var = false;
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -75,6 +78,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "-cache")) cache_path = next();
     else if (!strcmp(argv[i], "-png")) png_path = next();
     else if (!strcmp(argv[i], "-denoise")) denoise = true;
+    else if (!strcmp(argv[i], "-denoise-var")) denoise_var = true;
     else if (!strcmp(argv[i], "-guide")) guide_path = next();
     else if (!strcmp(argv[i], "-progressive")) progressive = atoi(next());
     else if (!strcmp(argv[i], "-chunk")) chunk = atoi(next());
@@ -105,6 +109,7 @@ int main(int argc, char** argv) {
     check(pt_group_info(ctx, nullptr, nullptr, 0, &peer), "group_info");
     printf("devices: %zu (%s)\n", devices.size(), peer ? "peer stores into the first device's frame" : "packed tile copies");
   }
+  if (denoise_var) check(pt_set_option(ctx, PT_OPT_MOMENTS, 1), "moments");
   check(pt_scene_upload(ctx, scene), "upload scene");
   const float pos[3] = {0.0f, 2.0f, 0.0f}, nrm[3] = {0.0f, -1.0f, 0.0f}, inten[3] = {10.0f, 10.0f, 10.0f},
               size[2] = {2.5f, 2.5f};   // VulkanRayTracer.cpp:149-162
@@ -169,7 +174,10 @@ int main(int argc, char** argv) {
     printf("rendered %dx%d x %d spp in %.3f ms\n", W, H, spp, std::chrono::duration<double, std::milli>(r1 - r0).count());
   if (!out_path.empty() || !png_path.empty()) {
     std::vector<float> rgba((size_t)W * H * 4);
-    if (denoise) {
+    if (denoise_var) {
+      check(pt_denoise_var(ctx, nullptr, nullptr), "denoise-var");
+      check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+    } else if (denoise) {
       check(pt_denoise(ctx, nullptr, nullptr, nullptr), "denoise");
       check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
     } else {

@@ -43,6 +43,7 @@ PT_OPT_DENOISE_LDS = 23
 PT_OPT_SMALL_SWEEP = 24
 PT_OPT_CULL_TIGHT = 25
 PT_OPT_SWEEP_HULL = 26
+PT_OPT_MOMENTS = 27
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -63,6 +64,8 @@ EXPORTS = [
     "pt_group_check", "pt_dist_info", "pt_mixed_info", "pt_sweep_info",
     "pt_denoise_default_params", "pt_guide_ray", "pt_render_guide", "pt_guide_device_ptr", "pt_read_guide",
     "pt_denoise", "pt_read_denoised", "pt_denoise_host",
+    "pt_moments_device_ptr", "pt_read_moments", "pt_denoise_var_default_params", "pt_denoise_var",
+    "pt_denoise_var_host",
 ]
 
 
@@ -86,6 +89,11 @@ class Traced(ctypes.Structure):
 
 class DenoiseParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float)]
+
+
+class DenoiseVarParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("sigma_lum", ctypes.c_float), ("sigma_normal", ctypes.c_float),
                 ("sigma_depth", ctypes.c_float)]
 
 
@@ -163,6 +171,11 @@ def lib():
             "pt_denoise": ([vp, ctypes.POINTER(DenoiseParams), vp, vp], i32),
             "pt_read_denoised": ([vp, vp, sz], i32),
             "pt_denoise_host": ([vp, vp, i32, i32, ctypes.POINTER(DenoiseParams), vp], i32),
+            "pt_moments_device_ptr": ([vp], vp),
+            "pt_read_moments": ([vp, vp, sz, ctypes.POINTER(u32)], i32),
+            "pt_denoise_var_default_params": ([ctypes.POINTER(DenoiseVarParams)], i32),
+            "pt_denoise_var": ([vp, ctypes.POINTER(DenoiseVarParams), vp], i32),
+            "pt_denoise_var_host": ([vp, vp, u32, vp, i32, i32, ctypes.POINTER(DenoiseVarParams), vp], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -418,6 +431,39 @@ def denoise_host(rgba, guide, width, height, params=None):
     return out.reshape(height, width, 4)
 
 
+def denoise_var_default_params():
+    """pt_denoise_var_default_params as a DenoiseVarParams."""
+    p = DenoiseVarParams()
+    _check(lib().pt_denoise_var_default_params(ctypes.byref(p)), "pt_denoise_var_default_params")
+    return p
+
+
+def _denoise_var_params(params):
+    """None (the library's defaults), a DenoiseVarParams, or (iterations,
+    sigma_lum, sigma_normal, sigma_depth) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, DenoiseVarParams):
+        return ctypes.byref(params)
+    it, sl, sn, sz = params
+    return ctypes.byref(DenoiseVarParams(int(it), float(sl), float(sn), float(sz)))
+
+
+def denoise_var_host(rgba, moments, n_samples, guide, width, height, params=None):
+    """pt_denoise_var_host: the variance-guided filter on the host, (H, W, 4)
+    float32 from the colours, the moments {m1, m2} of n_samples samples and
+    the guide."""
+    a = np.ascontiguousarray(rgba, np.float32).reshape(-1)
+    m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+    g = np.ascontiguousarray(guide, np.float32).reshape(-1)
+    if a.size != width * height * 4 or g.size != a.size or m.size != width * height * 2:
+        raise PTError("rgba and guide must hold width*height*4 floats, moments width*height*2")
+    out = np.empty(a.size, np.float32)
+    _check(lib().pt_denoise_var_host(a.ctypes.data, m.ctypes.data, int(n_samples), g.ctypes.data, width, height,
+                                     _denoise_var_params(params), out.ctypes.data), "pt_denoise_var_host")
+    return out.reshape(height, width, 4)
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -595,6 +641,28 @@ class Renderer:
         with dst_ptr None the library-owned result is read back and returned
         as (H, W, 4) float32."""
         _check(lib().pt_denoise(self._c, _denoise_params(params), src_ptr, dst_ptr), "pt_denoise")
+        if dst_ptr is not None:
+            return None
+        out = np.empty(self.width * self.height * 4, np.float32)
+        _check(lib().pt_read_denoised(self._c, out.ctypes.data, out.size), "pt_read_denoised")
+        return out.reshape(self.height, self.width, 4)
+
+    def moments_ptr(self):
+        """pt_moments_device_ptr: None when the moments are off or invalid."""
+        return lib().pt_moments_device_ptr(self._c)
+
+    def read_moments(self):
+        """pt_read_moments: ((H, W, 2) float32 {m1, m2}, n_samples) (PT_OPT_MOMENTS)."""
+        out = np.empty(self.width * self.height * 2, np.float32)
+        n = ctypes.c_uint32(0)
+        _check(lib().pt_read_moments(self._c, out.ctypes.data, out.size, ctypes.byref(n)), "pt_read_moments")
+        return out.reshape(self.height, self.width, 2), int(n.value)
+
+    def denoise_var(self, params=None, dst_ptr=None):
+        """pt_denoise_var: the variance-guided filter of the accumulation image
+        and its moments; with dst_ptr None the library-owned result is read
+        back and returned as (H, W, 4) float32."""
+        _check(lib().pt_denoise_var(self._c, _denoise_var_params(params), dst_ptr), "pt_denoise_var")
         if dst_ptr is not None:
             return None
         out = np.empty(self.width * self.height * 4, np.float32)

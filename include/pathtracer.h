@@ -43,7 +43,10 @@ extern "C" {
  * pt_read_denoised, pt_denoise_host, PT_OPT_DENOISE_LDS); the sweep walk of
  * tiny scenes (pt_sweep_info, PT_OPT_SMALL_SWEEP); the tight cull rectangles
  * and the sweep's hull faces (pt_primary_cull_rects_r, PT_OPT_CULL_TIGHT,
- * PT_OPT_SWEEP_HULL). */
+ * PT_OPT_SWEEP_HULL); the per-pixel luminance moments and the
+ * variance-guided filter (PT_OPT_MOMENTS, pt_moments_device_ptr,
+ * pt_read_moments, pt_denoise_var_params, pt_denoise_var_default_params,
+ * pt_denoise_var, pt_denoise_var_host). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -301,6 +304,69 @@ int pt_read_denoised(pt_context* ctx, float* rgba, size_t n_floats);
  * host function; bit-identical to pt_denoise. */
 int pt_denoise_host(const float* rgba, const float* guide, int width, int height, const pt_denoise_params* params,
                     float* out);
+
+/* ---- per-pixel luminance moments and the variance-guided filter --------
+ * With PT_OPT_MOMENTS 1 every pt_dispatch, pt_render and
+ * pt_progressive_advance also folds, per pixel, into a library-owned W x H
+ * image of float2 {m1, m2}:
+ *   L  = (0.2126f * r + 0.7152f * g) + 0.0722f * b   rgb of the sample's colour
+ *   m1 = (m1 * float(batch) + L)       / float(batch + 1)
+ *   m2 = (m2 * float(batch) + (L * L)) / float(batch + 1)
+ * the accumulator's own fold, in batch order, IEEE division, nothing fused.
+ * A culled pixel and a sample PT_OPT_CULL_TIGHT skips have L = +0.  After a
+ * render that starts at batch 0 every pixel of the frame holds the value of
+ * this definition.  pt_clear_accum, pt_resize_and_clear and pt_bind_accum
+ * zero the image.  The context tracks the consecutive batches 0..n-1 the image
+ * holds: a render with moments on whose first_batch is neither 0 nor n, and a
+ * render with moments off that changes the accumulator, make the moments
+ * invalid until the next render from batch 0 with moments on.
+ * PT_ERR_UNSUPPORTED with the option on: multi-device contexts, a partition of
+ * more than one rank, pt_render_packed, pt_dist_run, stats mode,
+ * PT_OPT_COUNT_TRACED. */
+/* The moments image in device memory; null when off or invalid. */
+void* pt_moments_device_ptr(pt_context* ctx);
+/* Waits for the moments and copies W*H*2 floats; *n_samples (may be null)
+ * receives n, or 0 when the image is invalid (its content is then whatever
+ * the renders since the last clear folded).  PT_ERR_INVALID with the option
+ * off or before the first render with it. */
+int pt_read_moments(pt_context* ctx, float* out, size_t n_floats, uint32_t* n_samples);
+/* The a-trous filter above with its colour edge-stop driven by each pixel's
+ * variance of the mean (SVGF): strong where the estimate is noisy, fading out
+ * as the render converges.  From the accumulation image c, its moments of n
+ * samples and the guide (n.xyz, t), lum() being the L above:
+ *   var0_p = fmax(0, m2_p - m1_p * m1_p) / float(n - 1)
+ *   pass i = 0 .. iterations-1, s = 1 << i, on colour c and variance v (v = var0 in pass 0):
+ *     gv_p  = (sum of (g[|dx|] * g[|dy|]) * v_q) / (sum of g[|dx|] * g[|dy|])
+ *             over q = p + (dx, dy), dy = -1..1 outer, dx = -1..1 inner, spacing 1,
+ *             taps outside the frame skipped, g = {1/2, 1/4}
+ *     den_p = sigma_lum * sqrt(gv_p) + 1e-6f
+ *     over the 25 taps q = p + s * (dx, dy), dy outer, dx inner, outside skipped
+ *     (h, d2n, dz, sn2, sz2 as in pt_denoise):
+ *       w      = h * exp(-((fabs(lum(c_p) - lum(c_q)) / den_p + d2n / sn2) + (dz * dz) / sz2))
+ *       sum_c += w * c_q.rgb;   sum_v += (w * w) * v_q;   sum_w += w
+ *     out.rgb = sum_c / sum_w,  out.a = c_p.a,  v_out = sum_v / (sum_w * sum_w)
+ * One rounding per written operation; sigma_lum is not scaled per pass.
+ * Defaults (pt_denoise_var_default_params): 4 iterations, sigma_lum 1.5,
+ * sigma_normal 1, sigma_depth 1: the best point of a grid scored on 8- and
+ * 32-spp frames of two scenes against 256 spp. */
+typedef struct pt_denoise_var_params {
+  int iterations;      /* 1 to 6 */
+  float sigma_lum;     /* all three finite and > 0, their squares finite and */
+  float sigma_normal;  /* non-zero */
+  float sigma_depth;
+} pt_denoise_var_params;
+int pt_denoise_var_default_params(pt_denoise_var_params* out);
+/* Enqueues the filter of the accumulation image with its moments, after
+ * rendering the guide if there is none.  dst_device null: the library-owned
+ * image pt_read_denoised reads; else W*H float4, 16-B aligned, not the
+ * accumulation image.  PT_ERR_INVALID without valid moments, with n < 2, with
+ * bad parameters, without a scene, a camera or a frame.  PT_OPT_DENOISE_LDS
+ * picks the staged kernels for spacings 1 and 2 as for pt_denoise (same bits). */
+int pt_denoise_var(pt_context* ctx, const pt_denoise_var_params* params, void* dst_device);
+/* The same filter on the host: rgba, guide and out W*H*4 floats, moments
+ * W*H*2, n_samples >= 2.  Pure host function; bit-identical to pt_denoise_var. */
+int pt_denoise_var_host(const float* rgba, const float* moments, uint32_t n_samples, const float* guide, int width,
+                        int height, const pt_denoise_var_params* params, float* out);
 
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile
@@ -587,6 +653,11 @@ int pt_dist_finalize(pt_context* ctx);
  * operations, so the same bits.  1 (default) = on; 0 = the
  * walk reads a table without the marks.  Output is identical. */
 #define PT_OPT_SWEEP_HULL 26
+/* PT_OPT_MOMENTS: 1 = renders also fold the per-pixel luminance moments
+ * (above) with the MOMENTS instantiations of the render and fold kernels; 0
+ * (default) = off, the kernels and frames of before.  The accumulator is the
+ * same bits either way. */
+#define PT_OPT_MOMENTS 27
 /* PT_OPT_CULL_TIGHT: beside the primary-culling rectangles, which hold for
  * every Box-Muller radius (at most 13.23), the host derives a second set for
  * radii of at most 4.25 (pt_primary_cull_rects_r).  A pixel inside the first
