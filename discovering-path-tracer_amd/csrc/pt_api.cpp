@@ -248,8 +248,6 @@ struct pt_context {
   float4* d_wide_leafbox = nullptr;  // the reference's leaf boxes by rank (64-B walk)
   float4* d_wide_tris = nullptr;
   int* d_wide_rank_of = nullptr;
-  // the 8-wide layout (PT_OPT_WIDE_NODE 80): nodes, triangle records and
-  // leaf boxes by leaf position, position -> rank, slot -> position
   int2* d_wide_ovf = nullptr;
   long long wide_ovf_lanes = 0;
   int wide_ovf_stack = 0;   // the stack bound d_wide_ovf was sized for
@@ -428,14 +426,6 @@ struct pt_scene {
   uint32_t flags = 0;
 };
 
-// The items (owned tile x sample-lane part) the render kernel would launch,
-// split by the same float test its workgroups apply (render_kernel wg_live):
-// those whose pixel rectangle can touch a cull rectangle go to the render
-// kernel, the rest to fill_culled_kernel.  A culled workgroup still costs a
-// workgroup launch (a fully culled 1080p frame took 0.10 ms at 4 sample
-// lanes), so only live ones are launched.
-// Pixels of columns [g0, g0+n) (or rows) whose NDC origin (the kernel's
-// ndc = 2*p/res - 1) lies in [lo, hi].
 // Before a launch that writes context-owned buffers: wait for the previous
 // such launch if it ran on another stream.
 static int order_shared(pt_context* c) {
@@ -478,6 +468,8 @@ static int quiesce(pt_context* c) {
   return PT_OK;
 }
 
+// Pixels of columns [g0, g0+n) (or rows) whose NDC origin (the kernel's
+// ndc = 2*p/res - 1) lies in [lo, hi].
 static int pixels_in(int g0, int n, int res, float lo, float hi) {
   int k = 0;
   for (int i = 0; i < n; ++i) {
@@ -562,6 +554,12 @@ static int sync_parts(pt_context* c) {
   return PT_OK;
 }
 
+// The items (owned tile x sample-lane part) the render kernel would launch,
+// split by the same float test its workgroups apply (render_kernel wg_live):
+// those whose pixel rectangle can touch a cull rectangle go to the render
+// kernel, the rest to fill_culled_kernel.  A culled workgroup still costs a
+// workgroup launch (a fully culled 1080p frame took 0.10 ms at 4 sample
+// lanes), so only live ones are launched.
 static void item_lists(const ptd::RenderParams& p, const ptd::Part& part, std::vector<int>* live,
                        std::vector<int>* culled) {
   const int W = p.width, H = p.height, spl = p.spl, rows = 16 / spl;

@@ -64,49 +64,21 @@ struct Hit {
 // in a wave whose lanes pass different leaves the triangle test then runs
 // max-over-lanes times instead of once per leaf any lane passed.  Candidates
 // are tested in visit order with the same strict '<', so the hit is the same.
-#ifndef PT_WF_PF
-#define PT_WF_PF 0
-#endif
-#ifndef PT_REC_PF
-#define PT_REC_PF 0
-#endif
 #ifndef PT_KCAND
 #define PT_KCAND 8
 #endif
-#ifndef PT_WF_WAVEFLUSH
-#define PT_WF_WAVEFLUSH 1   // wf_trace_kernel: wave-wide candidate flush (see there)
-#endif
-#ifndef PT_WF_SORT
-#define PT_WF_SORT 1   // wf_shade_kernel: bin each workgroup's next rays (see there)
-#endif
-#ifndef PT_WF_SORT_PHASE
-#define PT_WF_SORT_PHASE 1   // ... by the phase the path waits in (0: by ray kind and octant)
-#endif
-#ifndef PT_WF_SHADOW_QUEUE
-#define PT_WF_SHADOW_QUEUE 1   // wf_trace_kernel: shadow rays queue their leaves too (see there)
-#endif
-// queued shadow leaves are only ever flushed by the wave-wide flush
-static_assert(PT_WF_WAVEFLUSH || !PT_WF_SHADOW_QUEUE, "PT_WF_SHADOW_QUEUE needs PT_WF_WAVEFLUSH");
 constexpr int kCand = PT_KCAND;
 
-// The running mean's step (:467-469): (acc * b + c) / (b + 1).  PT_FOLD_FAST:
-// where b + 1 is a power of two the quotient is a product with its exact
-// reciprocal (bitwise the IEEE quotient: both round the same exact value),
-// and a running value of 1 folding a colour of 1 stays 1 ((b + 1) / (b + 1),
-// b + 1 < 2^24 exact) -- the alpha channel of every live pixel.
-#ifndef PT_FOLD_FAST
-#define PT_FOLD_FAST 1
-#endif
-// PT_FOLD_DIRECT: with one lane per pixel each lane folds its own sample
-// (no colour hand-off through LDS).  PT_SKIP_DEAD: the last SSS step's next
-// direction and the last bounce's direction, never traced, are not computed
-// (their draws still advance the stream).
-#ifndef PT_FOLD_DIRECT
-#define PT_FOLD_DIRECT 1   // box 1080p8, driver command: with PT_SKIP_DEAD and PT_FOLD_FAST 0.2131 -> 0.2114 ms (profiles/r05b/ab_box.log)
-#endif
-#ifndef PT_SKIP_DEAD
-#define PT_SKIP_DEAD 1
-#endif
+// The running mean's step (:467-469): (acc * b + c) / (b + 1).  Where b + 1
+// is a power of two the quotient is a product with its exact reciprocal
+// (bitwise the IEEE quotient: both round the same exact value), and a running
+// value of 1 folding a colour of 1 stays 1 ((b + 1) / (b + 1), b + 1 < 2^24
+// exact) -- the alpha channel of every live pixel.
+// With one lane per pixel each lane folds its own sample (no colour hand-off
+// through LDS).  The last SSS step's next direction and the last bounce's
+// direction, never traced, are not computed (their draws still advance the
+// stream).  Box 1080p8, driver command: the three together 0.2131 -> 0.2114 ms
+// (profiles/r05b/ab_box.log).
 
 // PF (prefetch): load node k+1 while node k is being tested — it is the next
 // visit whenever k is a hit internal node or a leaf (the node arrays carry one
@@ -114,7 +86,9 @@ constexpr int kCand = PT_KCAND;
 // 1M-triangle scene in the first kernel; re-measured after the candidate queue,
 // paired walks and null shadow rays it costs more than it hides: wavefront 1M
 // cloud 400 -> 337 ms and 10M cloud 662 -> 616 ms without it, sphere 452 ->
-// 423, recursive 5K sphere -2.5 %.  Off by default (PT_WF_PF, PT_REC_PF); an
+// 423, recursive 5K sphere -2.5 %.  The wavefront and fused walks no longer
+// carry it; only the reference-exhaustive stats walk from device memory
+// (trace_closest, occluded, path_trace with PF) still prefetches.  An
 // LDS-staged walk never used it.
 
 __device__ __forceinline__ void test_candidates(const RenderParams& P, v3 o, v3 d, const int* cand, int nc,
@@ -130,7 +104,7 @@ __device__ __forceinline__ void test_candidates(const RenderParams& P, v3 o, v3 
   }
 }
 
-// Shadow-ray candidates (PT_WF_SHADOW_QUEUE): the queued triangles in visit
+// Shadow-ray candidates (wf_trace_kernel): the queued triangles in visit
 // order until the first one occluded() would stop at; true if any.
 __device__ __forceinline__ bool test_shadow_candidates(const RenderParams& P, v3 o, v3 d, float limit,
                                                        const int* cand, int nc) {
@@ -437,28 +411,19 @@ __device__ __forceinline__ void add_ctr(Ctr& a, const Ctr& b) {
   a.prim += b.prim;
 }
 
-// LDS-staged scenes park path state in LDS during walks (PT_PARK) and run 6
-// waves per SIMD (80 VGPRs, 2 spilled) instead of 5 (96): box 1080p8 -3.8 %.
+// LDS-staged scenes park path state in LDS during walks and run 6 waves per
+// SIMD (80 VGPRs, 2 spilled) instead of 5 (96): box 1080p8 -3.8 %.
 // 7 waves spill 19 VGPRs and gain nothing; parking at 5 waves costs +1.7 %.
-#ifndef PT_PARK
-#define PT_PARK 1
-#endif
 // Parking in the paired walks of device-memory scenes (25 instead of 35
 // spilled VGPRs, at 5 waves/SIMD): sphere 5K tris -1.0 %, 20K cloud -2.0 %
 // (neutral while the k+1 prefetch held 8 more registers).  4 waves without
 // spills: +12 %.
-#ifndef PT_PARK_FUSED
-#define PT_PARK_FUSED 1
-#endif
-// ... and with the sweep walk (PT_OPT_SMALL_SWEEP), measured on its own with
-// PT_RENDER_MIN_BLOCKS_SWEEP (box 1080p8, 200 frames, four runs each,
-// profiles/sweep/ab_occupancy.log): parked at 5 / 6 / 7 blocks 0.1721-0.1724 /
-// 0.1601-0.1625 / 0.1662-0.1734 ms, not parked 0.1706-0.1718 / 0.1636-0.1661 /
-// 0.1675-0.1719: parked at 6 blocks, as the threaded walk.
-#ifndef PT_PARK_SWEEP
-#define PT_PARK_SWEEP PT_PARK
-#endif
-constexpr int kPark = (PT_PARK || PT_PARK_FUSED || PT_PARK_SWEEP) ? 12 : 0;   // floats of path state parked in LDS around a walk
+// ... and with the sweep walk (PT_OPT_SMALL_SWEEP), measured on its own (box
+// 1080p8, 200 frames, four runs each, profiles/sweep/ab_occupancy.log):
+// parked at 5 / 6 / 7 blocks 0.1721-0.1724 / 0.1601-0.1625 / 0.1662-0.1734 ms,
+// not parked 0.1706-0.1718 / 0.1636-0.1661 / 0.1675-0.1719: parked at 6
+// blocks, as the threaded walk.
+constexpr int kPark = 12;   // floats of path state parked in LDS around a walk
 __device__ __forceinline__ void park3(float* pk, int i, v3 v) {
   pk[i * 64] = v.x;
   pk[(i + 1) * 64] = v.y;
@@ -495,7 +460,7 @@ __device__ __forceinline__ v3 unpark3(const float* pk, int i) {
 // starts at cand); 2: of a table with hull faces (sweep_walk.h sweep_slab_hull).
 template <bool STATS, bool PF, bool CNT = false, int SWEEP = 0>
 __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr& c, int* cand) {
-  constexpr bool PARK = (SWEEP ? PT_PARK_SWEEP : PT_PARK) && !STATS && !PF;
+  constexpr bool PARK = !STATS && !PF;
   float* pk = (float*)(cand + (SWEEP ? 0 : kCand) * 64);
   auto closest = [&](v3 o, v3 d, Ctr& cc) {
     if constexpr (SWEEP)
@@ -602,7 +567,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
       sss_thr = mul(sss_thr, muls(sss_albedo, exp_(-travel / (sss_radius * 1.5f))));
       // the last step's next direction (:406-407) is never traced: its two
       // draws only advance the stream (the same state as sample_sphere's)
-      if (STATS || !PT_SKIP_DEAD || k + 1 < P.sss_bounces) {
+      if (STATS || k + 1 < P.sss_bounces) {
         so = sub(cp, muls(sn, OFFSET));
         sd = sample_sphere(&rng);
       } else {
@@ -612,7 +577,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
 
     // the last bounce's direction (:411-414) is never traced and the stream
     // is not read again: the path ends here
-    if (PT_SKIP_DEAD && !STATS && depth + 1 >= P.max_depth) break;
+    if (!STATS && depth + 1 >= P.max_depth) break;
     const v3 bd = sample_hemisphere(hn, &rng);          // :411-414
     thr = mul(thr, muls(albedo, dot(hn, bd)));
     ro = add(hp, muls(hn, OFFSET));
@@ -628,9 +593,8 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
 // SSS step's last shadow ray with the next SSS ray.  The RNG draws, the float
 // operations and their order are path_trace's: a shadow result is only used
 // after the pair returns, to finish the same sums in the same order.
-template <bool PF, bool CNT = false>
+template <bool CNT = false>
 __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, int* cand, Ctr& c) {
-  constexpr bool PARK = PT_PARK_FUSED != 0;
   float* pk = (float*)(cand + kCand * 64);
   const float OFFSET = 0.001f;
   v3 thr = mk(1.0f, 1.0f, 1.0f);
@@ -648,7 +612,7 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
     float tl;
     if (intersect_area_light(ro, rd, L, &tl)) {
       if (!have_h0) {
-        h0 = trace_closest<false, PF, true, CNT>(P, ro, rd, c, cand);
+        h0 = trace_closest<false, false, true, CNT>(P, ro, rd, c, cand);
         have_h0 = true;
       }
       if (h0.tri < 0 || h0.t > tl) return mk(L.inten[0], L.inten[1], L.inten[2]);
@@ -662,12 +626,12 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
     Hit h;
     if (depth == 0) {
       if (!have_h0) {
-        h0 = trace_closest<false, PF, true, CNT>(P, ro, rd, c, cand);
+        h0 = trace_closest<false, false, true, CNT>(P, ro, rd, c, cand);
         have_h0 = true;
       }
       h = h0;
     } else {
-      PT_WALK2(PARK, h = (trace_closest<false, PF, true, CNT>(P, ro, rd, c, cand)));
+      PT_WALK2(true, h = (trace_closest<false, false, true, CNT>(P, ro, rd, c, cand)));
     }
     if (h.tri < 0) {
       rad = add(rad, mul(thr, mk(0.0f, 0.0f, 0.0f)));  // background (:336)
@@ -690,7 +654,7 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
       const float d2 = dist * dist;
       const v3 contrib = mul(albedo, muls(muls(mk(L.inten[0], L.inten[1], L.inten[2]), diff), rcp_(fmax_(d2, 0.01f))));
       if (i + 1 < NL) {
-        if (!shadow_needed(L, diff) || !occluded<false, PF, CNT>(P, add(hp, muls(hn, OFFSET)), ld, dist - OFFSET, c))
+        if (!shadow_needed(L, diff) || !occluded<false, false, CNT>(P, add(hp, muls(hn, OFFSET)), ld, dist - OFFSET, c))
           direct = add(direct, contrib);
       } else {
         s_need = shadow_needed(L, diff);
@@ -705,7 +669,7 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
     v3 sd = sample_sphere(&rng);
     Hit sh;
     bool occ = false;
-    PT_WALK4(PARK, walk_pair<CNT>(P, NL > 0 && s_need, s_o, s_d, s_lim, &occ, P.sss_bounces > 0, so, sd, cand, &sh, c));
+    PT_WALK4(true, walk_pair<CNT>(P, NL > 0 && s_need, s_o, s_d, s_lim, &occ, P.sss_bounces > 0, so, sd, cand, &sh, c));
     if (NL > 0 && !occ) direct = add(direct, s_c);
     rad = add(rad, mul(thr, direct));
 
@@ -725,7 +689,7 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
         const v3 term = muls(mul(muls(sss_albedo, ediff), mk(L.inten[0], L.inten[1], L.inten[2])),
                              rcp_(fmax_(d2, 0.01f)));
         if (i + 1 < NL) {
-          if (!shadow_needed(L, ediff) || !occluded<false, PF, CNT>(P, add(cp, muls(sn, OFFSET)), ed, edist - OFFSET, c))
+          if (!shadow_needed(L, ediff) || !occluded<false, false, CNT>(P, add(cp, muls(sn, OFFSET)), ed, edist - OFFSET, c))
             sl = add(sl, term);
         } else {
           s_need = shadow_needed(L, ediff);
@@ -739,7 +703,7 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
       sss_thr = mul(sss_thr, muls(sss_albedo, exp_(-travel / (sss_radius * 1.5f))));
       so = sub(cp, muls(sn, OFFSET));
       sd = sample_sphere(&rng);
-      PT_WALK4(PARK, walk_pair<CNT>(P, NL > 0 && s_need, s_o, s_d, s_lim, &occ, k + 1 < P.sss_bounces, so, sd, cand, &sh, c));
+      PT_WALK4(true, walk_pair<CNT>(P, NL > 0 && s_need, s_o, s_d, s_lim, &occ, k + 1 < P.sss_bounces, so, sd, cand, &sh, c));
       if (NL > 0 && !occ) sl = add(sl, s_c);
       rad = add(rad, muls(mul(thr_k, sl), 1.0f + sss_radius * 0.5f));
     }
@@ -897,12 +861,12 @@ __device__ __forceinline__ void unpack_block(const RenderParams& P, int block) {
   }
 }
 
-// One step of the running mean (:467-469); PT_FOLD_FAST above.
+// One step of the running mean (:467-469); its two exact shortcuts are explained above.
 __device__ __forceinline__ float fold_one(float a, float c, uint32_t batch) {
   const float fb = (float)batch, fb1 = (float)(batch + 1u);
-  if (PT_FOLD_FAST && a == 1.0f && c == 1.0f && batch < (1u << 24)) return 1.0f;
+  if (a == 1.0f && c == 1.0f && batch < (1u << 24)) return 1.0f;
   const float x = a * fb + c;
-  if (PT_FOLD_FAST && ((batch + 1u) & batch) == 0u && batch + 1u != 0u) return x * (1.0f / fb1);
+  if (((batch + 1u) & batch) == 0u && batch + 1u != 0u) return x * (1.0f / fb1);
   return x / fb1;
 }
 
@@ -926,15 +890,8 @@ template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0, bool MOMENTS = 
 #ifndef PT_RENDER_MIN_BLOCKS
 #define PT_RENDER_MIN_BLOCKS 5
 #endif
-#ifndef PT_RENDER_MIN_BLOCKS_LDS
-#define PT_RENDER_MIN_BLOCKS_LDS (PT_PARK ? 6 : PT_RENDER_MIN_BLOCKS)
-#endif
-#ifndef PT_RENDER_MIN_BLOCKS_SWEEP
-#define PT_RENDER_MIN_BLOCKS_SWEEP PT_RENDER_MIN_BLOCKS_LDS
-#endif
-__global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
-                                  : LDS && !STATS ? PT_RENDER_MIN_BLOCKS_LDS : PT_RENDER_MIN_BLOCKS) void render_kernel(
-    RenderParams P) {
+// the parked walks (sweep, and LDS without stats) run 6 blocks per CU (kPark above)
+__global__ __launch_bounds__(256, SWEEP || (LDS && !STATS) ? 6 : PT_RENDER_MIN_BLOCKS) void render_kernel(RenderParams P) {
   const int tid = (int)threadIdx.x;
   // Work mapping.  A 16x16 pixel tile (the partition unit) is split into
   // SPL workgroups; lane l of wave w handles pixel q = w*(64/SPL) + l/SPL of
@@ -988,7 +945,8 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
   constexpr int kQueue = SWEEP ? 0 : kCand;   // the sweep walk queues nothing
   static_assert(!MOMENTS || (!STATS && !CNT), "moments: the plain kernels only");
   constexpr int kHand = MOMENTS ? 5 : 4;              // floats handed off per sample: the colour, then L
-  __shared__ int cand_buf[4][kQueue + (kPark > kHand ? kPark : kHand)][64];
+  static_assert(kPark >= kHand, "the hand-off shares the parked state's area");
+  __shared__ int cand_buf[4][kQueue + kPark][64];
   int* cand = &cand_buf[wave][0][lane];
   float* colw = (float*)&cand_buf[wave][kQueue][0];   // colour hand-off, [channel][lane]
   const int q = wave * (64 / spl) + lane / spl;       // pixel within the workgroup
@@ -1119,9 +1077,9 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
       const v3 bdir = normalize(sub(add(cdir, muls(neg(right), (ndcX * tanFov) * aspect)), muls(up, ndcY * tanFov)));
       const v3 focal = add(cpos, muls(bdir, 3.0f));                       // :459
       const v3 dir = normalize(sub(focal, origin));                       // :460
-      // PF (prefetch node k+1) for walks from device memory; on an LDS-staged
-      // scene it measured slower at every tile share (1080p box: +7 % on a
-      // whole frame, +12 % on a 1/8 share: registers)
+      // PF (prefetch node k+1) for the stats walk from device memory; on an
+      // LDS-staged scene it measured slower at every tile share (1080p box:
+      // +7 % on a whole frame, +12 % on a 1/8 share: registers)
       // Scenes walked from device memory pair each shadow ray with the next
       // closest-hit ray (path_trace_fused: two node round trips in flight,
       // sphere 20K tris -9 %); on an LDS-staged scene the round trip is short
@@ -1131,11 +1089,11 @@ __global__ __launch_bounds__(256, SWEEP ? PT_RENDER_MIN_BLOCKS_SWEEP
       if (STATS || LDS)
         col = path_trace<STATS, !LDS, CNT, SWEEP>(P, origin, dir, seed, c, cand);
       else
-        col = path_trace_fused<PT_REC_PF != 0, CNT>(P, origin, dir, seed, cand, c);
+        col = path_trace_fused<CNT>(P, origin, dir, seed, cand, c);
       col4 = make_float4(col.x, col.y, col.z, 1.0f);                      // vec4(color, 1.0)
       }
      }
-     if (PT_FOLD_DIRECT && spl == 1) {   // uniform: each lane folds its own sample, no hand-off (:467-469)
+     if (spl == 1) {   // uniform: each lane folds its own sample, no hand-off (:467-469)
       if (active && live) {
         const uint32_t batch = P.first_batch + base;   // wave-uniform
         acc[0] = fold_one(acc[0], col4.x, batch);
@@ -1424,7 +1382,7 @@ __device__ __forceinline__ void trav_start(Trav& T, v3 o, v3 d, bool shadow, flo
 // it starts finished, unoccluded: no node is visited.  Skipping it inside
 // path_step instead measured +3 % on the displaced sphere (paths drift apart)
 // with the exhaustive walks; with the culled wide walk the shading kernel
-// answers it itself (PT_WF_NULL_INLINE, wf_shade_kernel).
+// answers it itself (wf_shade_kernel).
 __device__ __forceinline__ void trav_null(const RenderParams& P, Trav& T) {
   T.k = P.n_nodes;
   T.shadow = 2;
@@ -1857,9 +1815,6 @@ __device__ __forceinline__ bool pixel_live(const RenderParams& P, float ndcX0, f
   return live;
 }
 
-#ifndef PT_WF_GEN_BLOCK_SLOTS
-#define PT_WF_GEN_BLOCK_SLOTS 1
-#endif
 // Ray generation + shading up to the primary trace (path_step from PH_BEGIN).
 template <bool CNT>
 __global__ __launch_bounds__(256) void wf_gen_kernel(RenderParams P, WfBuffers B, long long n, long long g0) {
@@ -1904,36 +1859,32 @@ __global__ __launch_bounds__(256) void wf_gen_kernel(RenderParams P, WfBuffers B
       if (!need) B.colors[g] = make_float4(col.x, col.y, col.z, 1.0f);
     }
   }
-  // list slots: one atomic per workgroup (PT_WF_GEN_BLOCK_SLOTS) instead of
-  // one per wave -- the generation is otherwise short, and every wave of the
-  // launch adding to the same counter queued on that one address
-  int slot;
-  if (PT_WF_GEN_BLOCK_SLOTS) {
-    __shared__ int wave_n[4], wave_base[4];
-    const unsigned long long m = __ballot(need);
-    const int w = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-    if (lane == 0) wave_n[w] = (int)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int tot = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-      const int base = tot ? atomicAdd(&B.counters[0], tot) : 0;
-      wave_base[0] = base;
-      wave_base[1] = base + wave_n[0];
-      wave_base[2] = base + wave_n[0] + wave_n[1];
-      wave_base[3] = base + wave_n[0] + wave_n[1] + wave_n[2];
-    }
-    __syncthreads();
-    slot = wave_base[w] + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  } else {
-    slot = wave_slot(&B.counters[0], need);
+  // list slots: one atomic per workgroup instead of one per wave -- the
+  // generation is otherwise short, and every wave of the launch adding to the
+  // same counter queued on that one address
+  __shared__ int wave_n[4], wave_base[4];
+  const unsigned long long m = __ballot(need);
+  const int w = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  if (lane == 0) wave_n[w] = (int)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int tot = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    const int base = tot ? atomicAdd(&B.counters[0], tot) : 0;
+    wave_base[0] = base;
+    wave_base[1] = base + wave_n[0];
+    wave_base[2] = base + wave_n[0] + wave_n[1];
+    wave_base[3] = base + wave_n[0] + wave_n[1] + wave_n[2];
   }
+  __syncthreads();
+  const int slot =
+      wave_base[w] + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
   if (need) {
     wf_push(B, 0, slot, (int)g, T, fuse_bits(P, S, T), S.rng);
     wf_store_state(B, 0, slot, S);
   }
   if (CNT) {
-    const unsigned long long m = __ballot(gen);
-    if (__lane_id() == 0 && m) atomicAdd(&P.stats[8], (unsigned long long)__popcll(m));
+    const unsigned long long mg = __ballot(gen);
+    if (__lane_id() == 0 && mg) atomicAdd(&P.stats[8], (unsigned long long)__popcll(mg));
   }
 }
 
@@ -1972,51 +1923,27 @@ __device__ __forceinline__ void wf_lane_start(const RenderParams& P, float4 r0, 
 
 // One node of trace_closest / occluded (same visit order and tests); true
 // when the ray is finished (L.lim / L.res hold the result).
-template <bool PF, bool CNT = false>
+template <bool CNT = false>
 __device__ __forceinline__ bool wf_lane_step(const RenderParams& P, WfLane& L, int* cand, Ctr& c) {
   if (L.k >= P.n_nodes) {
     if (!L.shadow)
       test_candidates(P, L.o, L.d, cand, L.nc, &L.lim, &L.res);
-    else if (PT_WF_SHADOW_QUEUE && L.nc > 0)
+    else if (L.nc > 0)
       L.res = test_shadow_candidates(P, L.o, L.d, L.lim, cand, L.nc) ? 1 : L.res;
     return true;
   }
   if (CNT) c.nodes++;
-  float4 na, nb;
-  if (PF) {
-    na = P.nodes[2 * L.k + 2];
-    nb = P.nodes[2 * L.k + 3];
-  }
   const int raw = __float_as_int(L.a.w);
   const bool h = slab(L.o, L.inv, L.a, L.b) || (raw < 0);
   const int tri = __float_as_int(L.b.w);
   const bool leaf_hit = h && tri >= 0;
   if (CNT) c.leaves += leaf_hit ? 1u : 0u;
-  if (L.shadow && !PT_WF_SHADOW_QUEUE) {
-    if (leaf_hit) {
-      const float4* T = P.tris + 3 * tri;
-      float t;
-      if (tri_test(L.o, L.d, T[0], T[1], T[2], &t) && t < 1e30f && !(t >= L.lim)) {
-        L.res = 1;
-        return true;
-      }
-    }
-  } else {
-    cand[L.nc * 64] = tri;
-    L.nc += leaf_hit ? 1 : 0;
-    if (!PT_WF_WAVEFLUSH && !L.shadow && L.nc == kCand) {
-      test_candidates(P, L.o, L.d, cand, L.nc, &L.lim, &L.res);
-      L.nc = 0;
-    }
-  }
+  // closest-hit and shadow rays alike queue the leaf; the kernel's wave-wide flush tests it
+  cand[L.nc * 64] = tri;
+  L.nc += leaf_hit ? 1 : 0;
   const int next = (h && tri < 0) ? L.k + 1 : (raw & 0x7fffffff);
-  if (PF && next == L.k + 1) {
-    L.a = na;
-    L.b = nb;
-  } else {
-    L.a = P.nodes[2 * next];
-    L.b = P.nodes[2 * next + 1];
-  }
+  L.a = P.nodes[2 * next];
+  L.b = P.nodes[2 * next + 1];
   L.k = next;
   return false;
 }
@@ -2024,14 +1951,14 @@ __device__ __forceinline__ bool wf_lane_step(const RenderParams& P, WfLane& L, i
 // Persistent traversal over list `cur`: lanes pull list slots (one atomic per
 // wave) and refill once at least PT_WF_REFILL lanes are idle.
 //
-// PT_WF_WAVEFLUSH: closest-hit candidates are tested wave-wide -- as soon as
+// Closest-hit candidates are tested wave-wide -- as soon as
 // one lane's queue is full, every lane with queued candidates tests them in
 // the same loop -- instead of by each full lane alone while the other lanes
 // of the wave wait (round-1 counters on the sphere: ~10 of 64 lanes active
 // per VALU instruction in wf_trace_kernel).  Same candidates, same visit
 // order, same strict '<': the same hit.  1080p8 displaced sphere 378 -> 289
 // ms, 1M cloud +0.5 %.
-// PT_WF_SHADOW_QUEUE: shadow rays queue their hit leaves as well instead of
+// Shadow rays queue their hit leaves as well instead of
 // testing each at once in a branch the other lanes wait on; the wave-wide
 // flush tests them in visit order and ends the walk at the first occluder.
 // The answer ("some accepted triangle has !(t >= limit)") is the same; the
@@ -2124,11 +2051,11 @@ __global__ __launch_bounds__(256, PT_WF_MIN_BLOCKS) void wf_trace_kernel(RenderP
     }
     if (!more && __ballot(p >= 0) == 0ull) break;
     for (int it = 0; it < PT_WF_STEPS; ++it) {
-      if (p >= 0 && wf_lane_step<PT_WF_PF && !LDS, CNT>(P, L, cand, c)) {
+      if (p >= 0 && wf_lane_step<CNT>(P, L, cand, c)) {
         B.hits[p] = make_float2(L.lim, __int_as_float(L.res));
         p = -1;
       }
-      if (PT_WF_WAVEFLUSH && __ballot(p >= 0 && L.nc == kCand)) {   // wave-uniform
+      if (__ballot(p >= 0 && L.nc == kCand)) {   // wave-uniform
         if (p >= 0 && L.nc > 0) {
           if (!L.shadow) {
             test_candidates(P, L.o, L.d, cand, L.nc, &L.lim, &L.res);
@@ -2165,11 +2092,8 @@ __global__ __launch_bounds__(256, PT_WF_MIN_BLOCKS) void wf_trace_kernel(RenderP
 // triangles, 4 above): sphere 78.0 -> 75.1 ms, 10M cloud 237 -> 206 ms;
 // the refill threshold is P.wide_refill (PT_OPT_WF_REFILL; PT_WIDE_REFILL for
 // the tail kernel).
-#ifndef PT_WIDE_G
-#define PT_WIDE_G 1
-#endif
 // refill threshold of the wide walk: 16 idle lanes.  Before the finished
-// walks were batched at the refill check (PT_WIDE_DEFER_DONE), 24 measured
+// walks were batched at the refill check (wf_trace_wide_kernel), 24 measured
 // best (sphere -0.9 %, 10M cloud -0.35 % against 32; 16 then +3 %); with
 // them batched, 16 against 24: sphere -2 %, 10M cloud -1.5 % (DESIGN item
 // 36); 12: +0.2 % / +4 %, 8: +7 % / +31 %.
@@ -2181,10 +2105,7 @@ __global__ __launch_bounds__(256, PT_WF_MIN_BLOCKS) void wf_trace_kernel(RenderP
 #ifndef PT_WIDE_STEPS
 #define PT_WIDE_STEPS 12
 #endif
-constexpr int kWideG = PT_WIDE_G;
-#ifndef PT_WIDE_DEFER_DONE
-#define PT_WIDE_DEFER_DONE 1
-#endif
+// finished walks waiting on their leaf queue that make the wave flush
 #ifndef PT_WIDE_FLUSH_T
 #define PT_WIDE_FLUSH_T 1
 #endif
@@ -2225,7 +2146,7 @@ __device__ __forceinline__ int fused_shadow_ray(const RenderParams& P, v3 o, v3 
 }
 constexpr int kFuseWalk = 16;   // lane state: walking the fused shadow ray
 
-// PT_WIDE_FLUSH_WAVE: the wave's queued leaf candidates tested one per lane.
+// The wave's queued leaf candidates tested one per lane.
 // wide_flush runs a lane's queue in its own lane, so a flush takes as many
 // loop trips as the longest queue while the others idle: a probe of the trace
 // kernel (tools/flush_probe.py) measured 67 candidates per flush on the
@@ -2244,12 +2165,6 @@ constexpr int kFuseWalk = 16;   // lane state: walking the fused shadow ray
 // rank, the reference's visit order): the same hits as wide_flush.  Call with
 // every lane of the wave active; keys: the wave's 64 LDS words; returns true
 // for a shadow ray found occluded.
-#ifndef PT_WIDE_FLUSH_WAVE
-#define PT_WIDE_FLUSH_WAVE 1
-#endif
-#ifndef PT_WIDE_OWNER3
-#define PT_WIDE_OWNER3 0
-#endif
 // Inclusive prefix sum over the wave's 64 lanes (every lane active) by DPP
 // row shifts within each row of 16 and row broadcasts across rows: six VALU
 // steps, where __shfl_up made six dependent LDS-crossbar round trips.
@@ -2275,33 +2190,14 @@ __device__ __forceinline__ bool wide_flush_wave(WideRay& R, bool mine, const flo
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const int* qbase = cand - lane;   // the wave's queue: [k][lane]
-#if PT_WIDE_OWNER3
-  // the inclusive sums at the ends of the wave's four 16-lane blocks (the
-  // last is `total`): wave-uniform, read once per flush
-  const int e15 = __builtin_amdgcn_readlane(incl, 15), e31 = __builtin_amdgcn_readlane(incl, 31),
-            e47 = __builtin_amdgcn_readlane(incl, 47);
-#endif
   for (int base = 0; base < total; base += 64) {
     const int target = base + lane;
     int L = 0;   // the owner: lanes whose inclusive sum is <= target
-#if PT_WIDE_OWNER3
-    // The same count in two dependent LDS round trips instead of six (the
-    // sums never decrease): whole 16-lane blocks by the uniform block ends,
-    // then whole 4-lane groups inside the block, then lanes inside the group
-    L = (e15 <= target ? 16 : 0) + (e31 <= target ? 16 : 0) + (e47 <= target ? 16 : 0);
-    {
-      const int a0 = __shfl(incl, L + 3), a1 = __shfl(incl, L + 7), a2 = __shfl(incl, L + 11);
-      L += (a0 <= target ? 4 : 0) + (a1 <= target ? 4 : 0) + (a2 <= target ? 4 : 0);
-      const int b0 = __shfl(incl, L), b1 = __shfl(incl, L + 1), b2 = __shfl(incl, L + 2);
-      L += (b0 <= target ? 1 : 0) + (b1 <= target ? 1 : 0) + (b2 <= target ? 1 : 0);
-    }
-#else
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) {
       const int v = __shfl(incl, L + s - 1);
       if (v <= target) L += s;
     }
-#endif
     L = min(L, 63);
     const int offL = __shfl(off, L);
     const v3 o = mk(__shfl(R.o.x, L), __shfl(R.o.y, L), __shfl(R.o.z, L));
@@ -2344,7 +2240,7 @@ __device__ __forceinline__ bool wide_flush_wave(WideRay& R, bool mine, const flo
 }
 
 // LAYOUT: 0 128-B 4-wide nodes, 1 64-B 4-wide nodes (QN)
-template <int G, bool CNT = false, int LAYOUT = 1>
+template <bool CNT = false, int LAYOUT = 1>
 __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(RenderParams P, WfBuffers B,
                                                                                 int cur) {
   constexpr bool QN = LAYOUT >= 1;
@@ -2355,10 +2251,9 @@ __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(
   const int wave = tid >> 6, lane = tid & 63;
   __shared__ int2 stk[4][kWideLds][64];
   int2* lds = &stk[wave][0][lane];
-  __shared__ int cq[PT_WIDE_QUEUE ? 4 : 1][PT_WIDE_QUEUE ? kWideQ : 1][64];
-  int* cand = PT_WIDE_QUEUE ? &cq[wave][0][lane] : nullptr;
-  constexpr bool FW = PT_WIDE_FLUSH_WAVE && PT_WIDE_QUEUE;
-  __shared__ unsigned long long fkeys[FW ? 4 : 1][64];
+  __shared__ int cq[4][kWideQ][64];   // the lanes' leaf queues (wide_walk.h)
+  int* cand = &cq[wave][0][lane];
+  __shared__ unsigned long long fkeys[4][64];
   bool fin = false;
   const long long os = (long long)gridDim.x * 256;
   int2* ovf = P.wide_ovf + ((long long)blockIdx.x * 256 + tid);
@@ -2414,26 +2309,21 @@ __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(
     }
   };
   for (;;) {
-    // PT_WIDE_DEFER_DONE: the lanes whose walks ended since the last check
-    // finish here together, not in the step their walk ended in (where the
-    // wave ran the finishing code -- the fused shadow ray's light sample,
-    // normalisations and start -- for one or two lanes at a time)
-    if (PT_WIDE_DEFER_DONE && p >= 0 && fin && R.nc == 0) finish();
+    // The lanes whose walks ended since the last check finish here together,
+    // not in the step their walk ended in (where the wave ran the finishing
+    // code -- the fused shadow ray's light sample, normalisations and start --
+    // for one or two lanes at a time)
+    if (p >= 0 && fin && R.nc == 0) finish();
+    // every idle lane refills on its own (no refill groups: see above)
     const unsigned long long idle = __ballot(p < 0);
-    unsigned long long gm = idle;
-#pragma unroll
-    for (int sh = 1; sh < G; sh <<= 1) gm &= gm >> sh;
-    gm &= group_lead<G>();
-    const int ng = (int)__popcll(gm);
-    if (more && ng * G >= P.wide_refill) {
-      const int need = ng * G;
+    const int need = (int)__popcll(idle);
+    if (more && need >= P.wide_refill) {
       int base = 0;
       if (lane == 0) base = atomicAdd(&B.counters[2], need);
       base = __shfl(base, 0);
       if (base + need >= count) more = false;
-      const int lead = lane & ~(G - 1);
-      if ((gm >> lead) & 1ull) {
-        const int slot = base + (int)__popcll(gm & ((1ull << lead) - 1ull)) * G + (lane - lead);
+      if ((idle >> lane) & 1ull) {
+        const int slot = base + (int)__popcll(idle & ((1ull << lane) - 1ull));
         if (slot < count) {
           float4 r0, r1;
           wf_load_ray(rays, B.cap, slot, &r0, &r1);
@@ -2456,81 +2346,65 @@ __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(
     if (!more && __ballot(p >= 0) == 0ull) break;
     for (int it = 0; it < PT_WIDE_STEPS; ++it) {
       bool exact = false;
-      if (!PT_WIDE_QUEUE) {
-        if (p >= 0 && wide_step<CNT, false, QN>(R, P.wide, P.wide_tris, lds, 64, ovf, os, P.wide_stack, &exact,
-                                                &c.nodes, &c.leaves, nullptr, P.wide_leafbox)) {
-          int res;
-          if (exact) res = R.shadow ? kNeedExactShadow : kNeedExactClosest;
-          else if (R.shadow) res = R.best;
-          else res = R.best;   // the rank (hit_tris = wide_tris)
-          B.hits[p] = make_float2(R.lim, __int_as_float(res));
-          p = -1;
-        }
-      } else {
-        // fin: the walk has no node left (its queue may still hold candidates)
-        if (p >= 0 && !fin)
-          fin = wide_step<CNT, true, QN>(R, P.wide, P.wide_tris, lds, 64, ovf, os, P.wide_stack, &exact, &c.nodes,
-                                         &c.leaves, cand, P.wide_leafbox);
-        if (exact) {
-          R.nc = 0;
-          // a fused shadow ray the walk cannot take goes to the shading's next round
-          B.hits[p] = (fz & kFuseWalk) ? make_float2(__uint_as_float(aux), __int_as_float(cr))
-                                       : make_float2(R.lim, __int_as_float(R.shadow ? kNeedExactShadow
-                                                                                    : kNeedExactClosest));
-          p = -1;
-          fin = false;
-          fz = 0;
-        }
-        // wave-uniform flush: a queue that cannot take another node's four
-        // leaves, or PT_WIDE_FLUSH_T finished walks waiting on their queue,
-        // or nothing left walking
-        const unsigned long long waiting = __ballot(p >= 0 && fin && R.nc > 0);
+      // fin: the walk has no node left (its queue may still hold candidates)
+      if (p >= 0 && !fin)
+        fin = wide_step<CNT, true, QN>(R, P.wide, P.wide_tris, lds, 64, ovf, os, P.wide_stack, &exact, &c.nodes,
+                                       &c.leaves, cand, P.wide_leafbox);
+      if (exact) {
+        R.nc = 0;
+        // a fused shadow ray the walk cannot take goes to the shading's next round
+        B.hits[p] = (fz & kFuseWalk) ? make_float2(__uint_as_float(aux), __int_as_float(cr))
+                                     : make_float2(R.lim, __int_as_float(R.shadow ? kNeedExactShadow
+                                                                                  : kNeedExactClosest));
+        p = -1;
+        fin = false;
+        fz = 0;
+      }
+      // wave-uniform flush: a queue that cannot take another node's four
+      // leaves, or PT_WIDE_FLUSH_T finished walks waiting on their queue,
+      // or nothing left walking
+      const unsigned long long waiting = __ballot(p >= 0 && fin && R.nc > 0);
 #ifdef PT_WIDE_PROBE_FLUSH
-        if (lane == 0) atomicAdd(&P.stats[7], 1ull);
-        if (lane == 0) atomicAdd(&P.stats[8], (unsigned long long)__popcll(__ballot(p >= 0 && !fin)));
+      if (lane == 0) atomicAdd(&P.stats[7], 1ull);
+      if (lane == 0) atomicAdd(&P.stats[8], (unsigned long long)__popcll(__ballot(p >= 0 && !fin)));
 #endif
 #ifdef PT_WIDE_PROBE   // lane-state census per step (traced counters 0-4: walking, idle with rays left
-                       // in the list, idle in the drain, steps, waiting on the leaf queue)
-        {
-          const unsigned long long walking = __ballot(p >= 0 && !fin), idle_l = __ballot(p < 0);
-          if (lane == 0) {
-            atomicAdd(&P.stats[4], (unsigned long long)__popcll(walking));
-            atomicAdd(&P.stats[more ? 5 : 6], (unsigned long long)__popcll(idle_l));
-            atomicAdd(&P.stats[7], 1ull);
-            atomicAdd(&P.stats[8], (unsigned long long)__popcll(waiting));
-          }
+                     // in the list, idle in the drain, steps, waiting on the leaf queue)
+      {
+        const unsigned long long walking = __ballot(p >= 0 && !fin), idle_l = __ballot(p < 0);
+        if (lane == 0) {
+          atomicAdd(&P.stats[4], (unsigned long long)__popcll(walking));
+          atomicAdd(&P.stats[more ? 5 : 6], (unsigned long long)__popcll(idle_l));
+          atomicAdd(&P.stats[7], 1ull);
+          atomicAdd(&P.stats[8], (unsigned long long)__popcll(waiting));
         }
-#endif
-        if (__ballot(p >= 0 && R.nc > kWideQ - 4) || (int)__popcll(waiting) >= PT_WIDE_FLUSH_T ||
-            (waiting && __ballot(p >= 0 && !fin) == 0ull)) {
-#ifdef PT_WIDE_PROBE_FLUSH   // flush loop use: [4] flushes, [5] sum of candidates, [6] sum of the largest queue, [7] steps
-          {
-            int mx = p >= 0 ? R.nc : 0, sm = mx;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-              mx = max(mx, __shfl_xor(mx, o));
-              sm += __shfl_xor(sm, o);
-            }
-            if (lane == 0) {
-              atomicAdd(&P.stats[4], 1ull);
-              atomicAdd(&P.stats[5], (unsigned long long)sm);
-              atomicAdd(&P.stats[6], (unsigned long long)mx);
-            }
-          }
-#endif
-          if (FW ? wide_flush_wave<CNT, QN>(R, p >= 0, P.wide_tris, cand, fkeys[FW ? wave : 0], lane, &c.leaves,
-                                            P.wide_leafbox)
-                 : (p >= 0 && R.nc > 0 &&
-                    wide_flush<CNT, QN>(R, P.wide_tris, cand, &c.leaves, P.wide_leafbox))) {
-            fin = true;   // occluded
-            R.sp = 0;
-            R.cur = -1;
-          }
-        }
-        if (!PT_WIDE_DEFER_DONE && p >= 0 && fin && R.nc == 0) finish();
-        // every lane idle or done (PT_WIDE_DEFER_DONE): back to the refill check
-        if (PT_WIDE_DEFER_DONE && __ballot(p >= 0 && !(fin && R.nc == 0)) == 0ull) break;
       }
+#endif
+      if (__ballot(p >= 0 && R.nc > kWideQ - 4) || (int)__popcll(waiting) >= PT_WIDE_FLUSH_T ||
+          (waiting && __ballot(p >= 0 && !fin) == 0ull)) {
+#ifdef PT_WIDE_PROBE_FLUSH   // flush loop use: [4] flushes, [5] sum of candidates, [6] sum of the largest queue, [7] steps
+        {
+          int mx = p >= 0 ? R.nc : 0, sm = mx;
+#pragma unroll
+          for (int o = 32; o >= 1; o >>= 1) {
+            mx = max(mx, __shfl_xor(mx, o));
+            sm += __shfl_xor(sm, o);
+          }
+          if (lane == 0) {
+            atomicAdd(&P.stats[4], 1ull);
+            atomicAdd(&P.stats[5], (unsigned long long)sm);
+            atomicAdd(&P.stats[6], (unsigned long long)mx);
+          }
+        }
+#endif
+        if (wide_flush_wave<CNT, QN>(R, p >= 0, P.wide_tris, cand, fkeys[wave], lane, &c.leaves, P.wide_leafbox)) {
+          fin = true;   // occluded
+          R.sp = 0;
+          R.cur = -1;
+        }
+      }
+      // every lane idle or done: back to the refill check (where the done ones finish)
+      if (__ballot(p >= 0 && !(fin && R.nc == 0)) == 0ull) break;
     }
   }
   if (CNT) flush_traced(P, c, lane);
@@ -2539,22 +2413,18 @@ __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(
 // Shading of every path in list `cur` (path_step on the returned hit);
 // paths that need another ray go to list cur^1, finished ones store colour.
 //
-// PT_WF_SORT: a workgroup appends its next rays binned -- one atomic per
-// workgroup, a counting sort in LDS -- by the phase the path waits in
-// (PT_WF_SORT_PHASE; closest-hit and shadow rays apart, and the next shading
-// pass runs one case of path_step per wave instead of several), or by ray
-// kind and direction octant.  A ray's result does not depend on where it
-// sits in the list, so the image is unchanged.  Measured at 1080p 8 spp with
-// the wide walk (G = 1, null queries inline): sphere 70.7 -> 65.0 ms, 10M
-// cloud 181.5 -> 158.0 ms by phase; by kind and octant 65.7 / 158.3; by
-// phase and octant 65.7 / 159.1.  (With the exhaustive walks and refill
-// groups of round 2's first half, kind and octant had measured sphere -0.5 %,
-// 10M cloud +3.5 %; the exhaustive walk keeps the unsorted lists.)
-[[maybe_unused]] __device__ __forceinline__ int ray_bin(const Trav& T) {
-  const int oct = (T.d.x < 0.0f ? 1 : 0) | (T.d.y < 0.0f ? 2 : 0) | (T.d.z < 0.0f ? 4 : 0);
-  return (T.shadow ? 8 : 0) | oct;
-}
-// PT_WF_NULL_INLINE: a null shadow query (trav_null: its answer cannot change
+// With the wide walk a workgroup appends its next rays binned -- one atomic
+// per workgroup, a counting sort in LDS -- by the phase the path waits in
+// (closest-hit and shadow rays apart, and the next shading pass runs one case
+// of path_step per wave instead of several).  A ray's result does not depend
+// on where it sits in the list, so the image is unchanged.  Measured at 1080p
+// 8 spp with the wide walk (single-lane refill, null queries inline): sphere
+// 70.7 -> 65.0 ms, 10M cloud 181.5 -> 158.0 ms by phase; binned by ray kind
+// and direction octant instead 65.7 / 158.3; by phase and octant 65.7 /
+// 159.1.  (With the exhaustive walks and refill groups of round 2's first
+// half, kind and octant had measured sphere -0.5 %, 10M cloud +3.5 %; the
+// exhaustive walk keeps the unsorted lists.)
+// A null shadow query (trav_null: its answer cannot change
 // the image) is answered by the shading kernel itself, with the wide walk --
 // path_step runs on with "unoccluded" -- instead of taking a list slot, a refill and a lane of
 // the next traversal launch (where it started finished and left its lane
@@ -2564,9 +2434,6 @@ __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(
 // 206 -> 181 ms; with the exhaustive threaded walk (PT_OPT_WIDE 0) the 10M
 // cloud measured 2799 -> 2980 ms (paths drift out of phase), so it keeps the
 // null rays in its lists.
-#ifndef PT_WF_NULL_INLINE
-#define PT_WF_NULL_INLINE 1
-#endif
 #ifndef PT_WF_SHADE_MIN_BLOCKS
 #define PT_WF_SHADE_MIN_BLOCKS 4
 #endif
@@ -2624,23 +2491,17 @@ __global__ __launch_bounds__(256, PT_WF_SHADE_MIN_BLOCKS) void wf_shade_kernel(R
           col = mk(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
         }
       }
-#if PT_WF_NULL_INLINE
       while (P.wide && need && T.shadow == 2) {   // a null shadow query (trav_null): unoccluded, answered here
         T.res = 0;
         need = path_step<false>(P, F, S, T, c, &col);
       }
-#endif
       if (!need) B.colors[p] = make_float4(col.x, col.y, col.z, 1.0f);
     }
-    if (PT_WF_SORT && P.wide) {   // uniform: every thread of the workgroup runs each iteration
+    if (P.wide) {   // uniform: every thread of the workgroup runs each iteration
       const int tid = (int)threadIdx.x;
       if (tid < kWfBins) bin_cnt[tid] = 0;
       __syncthreads();
-#if PT_WF_SORT_PHASE
       const int bin = need ? (S.phase & 7) : 0;   // the phase the path waits in
-#else
-      const int bin = need ? ray_bin(T) : 0;
-#endif
       const int rank = need ? atomicAdd(&bin_cnt[bin], 1) : 0;
       __syncthreads();
       if (tid == 0) {
@@ -2703,7 +2564,7 @@ __global__ __launch_bounds__(256, PT_WF_TAIL_MIN_BLOCKS) void wf_tail_kernel(Ren
   // leaf queue; an exact walk's candidates (the queue is empty then)
   __shared__ int cq[4][kWideQ > kCand ? kWideQ : kCand][64];
   int* cand = &cq[wave][0][lane];
-  __shared__ unsigned long long fkeys[PT_WIDE_FLUSH_WAVE ? 4 : 1][64];
+  __shared__ unsigned long long fkeys[4][64];
   const long long os = (long long)gridDim.x * 256;
   int2* ovf = P.wide_ovf + ((long long)blockIdx.x * 256 + tid);
   const float4* __restrict__ rays = B.rays[cur];
@@ -2811,9 +2672,7 @@ __global__ __launch_bounds__(256, PT_WF_TAIL_MIN_BLOCKS) void wf_tail_kernel(Ren
       const unsigned long long waiting = __ballot(p >= 0 && fin && R.nc > 0);
       if (__ballot(p >= 0 && R.nc > kWideQ - 4) || (int)__popcll(waiting) >= PT_WIDE_FLUSH_T ||
           (waiting && __ballot(p >= 0 && !fin) == 0ull)) {
-        if (PT_WIDE_FLUSH_WAVE ? wide_flush_wave<CNT, QN>(R, p >= 0, P.wide_tris, cand, fkeys[PT_WIDE_FLUSH_WAVE ? wave : 0],
-                                                        lane, &c.leaves, P.wide_leafbox)
-                               : (p >= 0 && R.nc > 0 && wide_flush<CNT, QN>(R, P.wide_tris, cand, &c.leaves, P.wide_leafbox))) {
+        if (wide_flush_wave<CNT, QN>(R, p >= 0, P.wide_tris, cand, fkeys[wave], lane, &c.leaves, P.wide_leafbox)) {
           fin = true;   // occluded
           R.sp = 0;
           R.cur = -1;
@@ -3088,8 +2947,8 @@ long long wide_trace_lanes() {
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   int most = 0;
-  for (auto k : {wf_trace_wide_kernel<kWideG, false, 1>, wf_trace_wide_kernel<kWideG, true, 1>,
-                 wf_trace_wide_kernel<kWideG, false, 0>, wf_trace_wide_kernel<kWideG, true, 0>}) {
+  for (auto k : {wf_trace_wide_kernel<false, 1>, wf_trace_wide_kernel<true, 1>,
+                 wf_trace_wide_kernel<false, 0>, wf_trace_wide_kernel<true, 0>}) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0) != hipSuccess) return 0;
     most = std::max(most, per_cu);
   }
@@ -3116,11 +2975,7 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
   int dev = 0, cus = 0, per_cu_t = 0, per_cu_s = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-#ifdef PT_WF_FORCE_G
-  const bool g2 = PT_WF_FORCE_G == 2;
-#else
   const bool g2 = p0.n_tris < kWfGroup4Tris;
-#endif
   void (*trace)(RenderParams, WfBuffers, int) =
       cnt ? (lds_scene ? (g2 ? wf_trace_kernel<true, 2, true> : wf_trace_kernel<true, 4, true>)
                        : (g2 ? wf_trace_kernel<false, 2, true> : wf_trace_kernel<false, 4, true>))
@@ -3128,8 +2983,8 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
                        : (g2 ? wf_trace_kernel<false, 2> : wf_trace_kernel<false, 4>));
   const bool wide = p0.wide && !lds_scene;
   if (wide)   // culled wide walk (PT_OPT_WIDE, default)
-    trace = p0.wide_qn ? (cnt ? wf_trace_wide_kernel<kWideG, true, 1> : wf_trace_wide_kernel<kWideG, false, 1>)
-                       : (cnt ? wf_trace_wide_kernel<kWideG, true, 0> : wf_trace_wide_kernel<kWideG, false, 0>);
+    trace = p0.wide_qn ? (cnt ? wf_trace_wide_kernel<true, 1> : wf_trace_wide_kernel<false, 1>)
+                       : (cnt ? wf_trace_wide_kernel<true, 0> : wf_trace_wide_kernel<false, 0>);
   const size_t lds_t = wide ? 0 : lds;
   if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_t, trace, 256, lds_t);
   if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, wf_shade_kernel, 256, 0);
@@ -3203,14 +3058,6 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
       if (tail)
         for (int h = 0; h < H; ++h) hipLaunchKernelGGL(tailk, dim3(grid_x), dim3(256), 0, sh[h], ph[h], bh[h], cur);
       for (int h = 0; h < H; ++h) wf_shade_kernel<<<grid_s, 256, 0, sh[h]>>>(ph[h], bh[h], cur);
-#ifdef PT_WF_ROUND_LOG   // A/B builds only: rays per round (synchronous)
-      {
-        int cnt2[2] = {0, 0};
-        if (hipStreamSynchronize(sh[0]) == hipSuccess &&
-            hipMemcpy(cnt2, bh[0].counters, 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
-          fprintf(stderr, "wf_round %d traced %d next %d\n", it, cnt2[cur], cnt2[cur ^ 1]);
-      }
-#endif
       cur ^= 1;
     }
     for (int h = 0; h < H; ++h)

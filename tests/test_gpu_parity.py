@@ -881,7 +881,7 @@ def test_count_traced_mode(scene):
             assert c[k] == first[k], (name, k, c, first)
     if "lds" in counts:   # the two path-recursive kernels do the same node visits and tests
         assert counts["lds"] == counts["dev"]
-    # the wavefront kernel queues shadow leaves (PT_WF_SHADOW_QUEUE): a shadow
+    # the wavefront kernel queues shadow leaves (wf_lane_step): a shadow
     # walk may run a few nodes past its occluder before the queue is tested
     assert counts["wf"]["nodes"] >= counts["dev"]["nodes"]
     assert counts["wf"]["tri_tests"] >= counts["dev"]["tri_tests"]

@@ -69,7 +69,7 @@ WIDE_FROM_REFERENCE, WIDE_SAH = 0, 1
 # (grouping, node bytes, queued leaf tests): the kernel's default is (SAH, 64,
 # 2: queued, flushed wave-wide); 64-B nodes hold boxes rounded outward onto an 8-bit grid and test a
 # leaf's exact box before its hit counts (wide_walk.h); queued: leaf hits are
-# tested in flushes, as one lane of the trace kernel does (PT_WIDE_QUEUE)
+# tested in flushes, as one lane of the trace kernel does (wide_step's QUEUE form)
 BUILDS = pytest.mark.parametrize(
     "build", [(WIDE_SAH, 64, 1), (WIDE_SAH, 64, 0), (WIDE_SAH, 128, 1), (WIDE_SAH, 128, 0),
               (WIDE_FROM_REFERENCE, 64, 1), (WIDE_FROM_REFERENCE, 128, 0), (WIDE_SAH, 64, 2), (WIDE_SAH, 128, 2),
