@@ -24,6 +24,69 @@ def camera(pos, up=(0, 1, 0), fov=60.0):
     return ubo
 
 
+def transformed(v, scale, offset):
+    """Vertices `v * scale + offset`, computed in float64 and rounded to float32."""
+    p = np.asarray(v, np.float64).reshape(-1, 3) * float(scale) + np.asarray(offset, np.float64)
+    return p.astype(np.float32).reshape(-1)
+
+
+def transformed_camera(ubo, scale, offset):
+    """The camera UBO that sees `transformed(v, scale, offset)` from where `ubo`
+    sees `v`: the position moves, direction, up and fov stay (the shader's
+    aperture 0.02 and focal distance 3 do not scale, so only the blur differs)."""
+    out = np.array(ubo, np.float32)
+    out[0:3] = (np.asarray(ubo[0:3], np.float64) * float(scale) + np.asarray(offset, np.float64)).astype(np.float32)
+    return out
+
+
+def transformed_light(light16, scale, offset):
+    """The packed light moved with the scene: position moved, size times scale,
+    intensity times scale^2 (the irradiance at the moved surface stays)."""
+    out = np.array(light16, np.float32)
+    out[0:3] = (np.asarray(light16[0:3], np.float64) * float(scale) + np.asarray(offset, np.float64)).astype(np.float32)
+    out[8:11] = (np.asarray(light16[8:11], np.float64) * float(scale) ** 2).astype(np.float32)
+    out[12:14] = (np.asarray(light16[12:14], np.float64) * float(scale)).astype(np.float32)
+    return out
+
+
+def coincident_copies(v, i, copies):
+    """The index list `copies` times over the same vertices, odd copies with
+    flipped winding: every ray that hits ties in t across `copies` triangles,
+    and the winner's normal depends on the visit order."""
+    t = np.asarray(i, np.uint32).reshape(-1, 3)
+    parts = [t if c % 2 == 0 else t[:, [0, 2, 1]] for c in range(copies)]
+    return np.asarray(v, np.float32).reshape(-1).copy(), np.concatenate(parts).astype(np.uint32).reshape(-1)
+
+
+def floor_and_cloud():
+    """5,000 small triangles over a two-triangle floor 40 units across (y = -0.6,
+    geometric normal +y): triangle sizes three orders of magnitude apart in one
+    tree.  The floor's coefficients exceed the cull bound, so every wide node
+    above it gives up culling while its siblings still cull."""
+    v, i = random_triangles(5000, seed=3, spread=0.5, size=0.01)
+    quad = np.array([(-20, -0.6, -20), (-20, -0.6, 20), (20, -0.6, 20), (20, -0.6, -20)], np.float32)
+    base = v.size // 3
+    qi = np.array([0, 1, 2, 0, 2, 3], np.uint32) + np.uint32(base)
+    return np.concatenate([v, quad.reshape(-1)]).astype(np.float32), np.concatenate([i, qi]).astype(np.uint32)
+
+
+def with_degenerates(v, i):
+    """Every 5th triangle with two equal vertices (a segment), every 7th
+    collapsed to a point: zero-extent leaf boxes and det = 0."""
+    t = np.array(i, np.uint32).reshape(-1, 3)
+    k = np.arange(len(t))
+    t[k % 5 == 0, 1] = t[k % 5 == 0, 0]
+    t[k % 7 == 0, 1] = t[k % 7 == 0, 0]
+    t[k % 7 == 0, 2] = t[k % 7 == 0, 0]
+    return np.asarray(v, np.float32).reshape(-1).copy(), t.reshape(-1)
+
+
+def flat_quad():
+    """Two triangles in z = 0 (geometric normal +z): the root box has zero thickness."""
+    v = np.array([(-1, -1, 0), (1, -1, 0), (1, 1, 0), (-1, 1, 0)], np.float32)
+    return v.reshape(-1), np.array([0, 1, 2, 0, 2, 3], np.uint32)
+
+
 def random_triangles(n, seed=42, spread=1.0, size=0.01):
     """SURVEY.md §8d config 5 generator: centroids ~U[-1,1]^3, vertex offsets
     ~U[-size,size]^3, unshared vertices."""

@@ -153,6 +153,22 @@ def test_cull_disabled_when_object_reaches_camera_plane():
     assert ptamd.primary_cull_rects(scenes.DEFAULT_CAMERA, 64, 64, lo, hi, many) is None
 
 
+def ring_lights(n):
+    """n small lights on a ring above the box, facing down."""
+    return np.concatenate([ptamd.pack_light([1.5 * np.cos(k * 0.785), 2, 1.5 * np.sin(k * 0.785)], [0, -1, 0], [3, 2, 1],
+                                            [0.6, 0.6]) for k in range(n)])
+
+
+def test_seven_lights_fill_the_rectangle_table_and_eight_switch_culling_off():
+    """The table holds 8 rectangles (kMaxCullRects): the root box and 7 lights."""
+    lo, hi = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
+    rects = ptamd.primary_cull_rects(scenes.DEFAULT_CAMERA, 64, 48, lo, hi, ring_lights(7))
+    assert rects is not None and len(rects) == 8
+    assert _culled_mask(rects, 64, 48).any()
+    for n in (8, 9):
+        assert ptamd.primary_cull_rects(scenes.DEFAULT_CAMERA, 64, 48, lo, hi, ring_lights(n)) is None
+
+
 @pytest.mark.parametrize("name,cam,W,H,lights", CASES[:4], ids=[c[0] for c in CASES[:4]])
 def test_oracle_renders_culled_pixels_as_background(box, name, cam, W, H, lights):
     v, idx, nodes = box

@@ -96,6 +96,64 @@ def _margin(loose, tight, W, H):
     return ~test_cull._culled_mask(loose, W, H) & test_cull._culled_mask(tight, W, H)
 
 
+def rng_draws(seeds, n):
+    """The shader's RNG (raytrace_comp.comp:207-216) in numpy: the first n
+    draws of every seed, (len(seeds), n) float32."""
+    s = np.asarray(seeds, np.uint64) & np.uint64(0xFFFFFFFF)
+    m32 = np.uint64(0xFFFFFFFF)
+    out = np.empty((s.size, n), np.float32)
+    for k in range(n):
+        s = (s * np.uint64(747796405) + np.uint64(2891336453)) & m32
+        r = (((s >> ((s >> np.uint64(28)) + np.uint64(4))) ^ s) * np.uint64(277803737)) & m32
+        r = (r >> np.uint64(22)) ^ r
+        out[:, k] = r.astype(np.uint32).astype(np.float32) / np.float32(4294967296.0)
+    return out
+
+
+def test_rng_restatement_equals_the_oracle():
+    rnd = np.random.default_rng(5)
+    seeds = np.concatenate([np.arange(0, 64), 2 ** 32 - 1 - np.arange(0, 64), 2 ** 31 + np.arange(-32, 32),
+                            rnd.integers(0, 2 ** 32, 4000)]).astype(np.uint64)
+    got = rng_draws(seeds, 4)
+    want = np.stack([oracle_lib.rng(int(s), 4) for s in seeds])
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert len(np.unique(got)) > 0.99 * got.size
+
+
+def skip_counts(cam, W, H, lights, first_batch, n_batches, lo=(-1, -1, -1), hi=(1, 1, 1)):
+    """What include/pathtracer.h defines for PT_OPT_CULL_TIGHT, counted on the
+    host: (live pixels, margin samples the kernel must skip, margin samples it
+    must trace) over the batches.  A margin pixel lies inside a loose
+    rectangle and outside every tight one; its sample of a batch is skipped
+    when draws 0 and 2 of seed (batch * H + y) * W + x, after fmax(1e-38, .),
+    are both at least u0."""
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    loose = ptamd.primary_cull_rects(cam, W, H, lo, hi, lights)
+    tight, u0 = ptamd.primary_cull_rects_r(cam, W, H, lo, hi, lights)
+    assert loose is not None and tight is not None and len(loose) == len(tight)
+    u0 = np.float32(u0)
+    live = ~test_cull._culled_mask(loose, W, H)
+    ys, xs = np.nonzero(_margin(loose, tight, W, H))
+    skipped = traced = 0
+    for batch in range(first_batch, first_batch + n_batches):
+        seeds = (np.uint64(batch) * np.uint64(H) + ys.astype(np.uint64)) * np.uint64(W) + xs.astype(np.uint64)
+        u = np.maximum(np.float32(1e-38), rng_draws(seeds, 3))
+        skip = (u[:, 0] >= u0) & (u[:, 2] >= u0)
+        skipped += int(skip.sum())
+        traced += int((~skip).sum())
+    return int(live.sum()), skipped, traced
+
+
+def test_skip_counts_of_the_gpu_test_frame():
+    """The box at 320x180, default camera: 5,369 margin pixels; batches 0-7
+    hold 12 margin samples with a radius draw below u0 (the kernel must trace
+    them), batches 0-599 hold 767."""
+    live, skipped, traced = skip_counts(scenes.DEFAULT_CAMERA, 320, 180, scenes.REFERENCE_LIGHT, 0, 8)
+    assert skipped + traced == 5369 * 8 and traced == 12 and live > 5369
+    _, skipped, traced = skip_counts(scenes.DEFAULT_CAMERA, 320, 180, scenes.REFERENCE_LIGHT, 0, 600)
+    assert skipped + traced == 5369 * 600 and traced == 767
+
+
 @pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=[c[0] for c in CASES])
 def test_margin_pixels_reach_nothing_with_radii_at_the_bound(name, cam, W, H, lights):
     """Aperture and jitter radii both at the bound, both angles scanned (the

@@ -1,6 +1,8 @@
 """GPU: the per-sample skip of the tight cull rectangles (PT_OPT_CULL_TIGHT,
 csrc/pt_cull.h): frames with the option on and off are bitwise equal and equal
-to the oracle's, and the counting kernel shows that samples were skipped.
+to the oracle's, and the counting kernel skips exactly the samples the
+header's definition says (the image cannot show the predicate: the margin
+samples the kernel must trace are black in the oracle too).
 
 The frame is the box at 320x180, 4 spp: 98 of its 326 live 16x4 pixel blocks
 lie wholly between the loose and the tight rectangles
@@ -15,6 +17,7 @@ import pytest
 import oracle_lib as O
 import ptamd
 import scenes
+from test_cull_tight import skip_counts
 from test_gpu_sweep import _same
 
 pytestmark = pytest.mark.gpu
@@ -110,6 +113,42 @@ def test_counting_mode_shows_skipped_primaries(kernel):
     _same(frames[1], _oracle(0, 4), "counting mode against the oracle")
     print(f"kernel {kernel}: primaries on {counts[1]['primaries']}, off {counts[0]['primaries']}")
     assert 0 < counts[1]["primaries"] < counts[0]["primaries"] <= W * H * 4
+    assert counts[1]["closest_walks"] < counts[0]["closest_walks"]
+
+
+@pytest.mark.parametrize("kernel,lanes", [(ptamd.KERNEL_RECURSIVE, 1), (ptamd.KERNEL_WAVEFRONT, 1),
+                                          (ptamd.KERNEL_RECURSIVE, 4)])
+def test_skip_counts_are_exact(kernel, lanes):
+    """The image cannot show whether the kernel evaluates the skip predicate:
+    every margin sample it must trace (a radius draw below kCullTightU0) is
+    (0,0,0) in the oracle too (767 of 767 over batches 0-599), so a kernel that
+    skipped every margin sample would render the same frame.  The counters
+    can: with the option off every sample of a live pixel generates its
+    primary ray, with it on exactly the margin samples whose two radius draws
+    are at least u0 do not (test_cull_tight.skip_counts, from the header's
+    definition).  At 4 lanes the samples of one pixel sit in neighbouring
+    lanes."""
+    nb = 8
+    live, skipped, traced = skip_counts(scenes.DEFAULT_CAMERA, W, H, scenes.REFERENCE_LIGHT, 0, nb)
+    assert traced >= 5 and skipped > 1000, "the batches exercise both sides of the predicate"
+    counts, frames = {}, {}
+    for tight in (1, 0):
+        r = _renderer(tight, lanes, count=True)
+        r.set_option(ptamd.PT_OPT_KERNEL, kernel)
+        r.resize_and_clear(W, H)
+        r.reset_stats()
+        r.render(0, nb)
+        frames[tight] = r.read_accum()
+        counts[tight] = r.traced()
+        assert r.last_kernel() == kernel
+        r.close()
+    print(f"kernel {kernel} lanes {lanes}: primaries on {counts[1]['primaries']}, off {counts[0]['primaries']}; "
+          f"expected off {live * nb}, skipped {skipped}, margin samples traced {traced}")
+    _same(frames[0], frames[1], "counting mode: PT_OPT_CULL_TIGHT 0 against 1")
+    _same(frames[1], _oracle(4, 4), "counting mode against the oracle")
+    assert counts[0]["primaries"] == live * nb
+    assert counts[0]["primaries"] - counts[1]["primaries"] == skipped
+    assert 0 < counts[1]["primaries"] < counts[0]["primaries"] <= W * H * nb
     assert counts[1]["closest_walks"] < counts[0]["closest_walks"]
 
 

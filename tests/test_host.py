@@ -48,9 +48,19 @@ def _product(v, i, int_bits=False, threads=0):
     return pi, pn
 
 
-@pytest.mark.parametrize("name", ["box", "random1", "random2", "random3", "random1000", "grid", "sphere"])
+@pytest.mark.parametrize("name", ["box", "random1", "random2", "random3", "random1000", "grid", "sphere",
+                                  "coincident", "degenerates", "translated"])
 def test_bvh_byte_identical_to_oracle(name):
-    if name == "box":
+    """coincident: six copies of every triangle, so every centroid key ties six
+    ways -- the worst case for the builder's restatement of the unstable sort."""
+    if name == "coincident":
+        v, i = scenes.coincident_copies(*scenes.displaced_sphere(2), 6)
+    elif name == "degenerates":
+        v, i = scenes.with_degenerates(*scenes.random_triangles(3000, seed=8, spread=0.5, size=0.02))
+    elif name == "translated":
+        v, i = scenes.random_triangles(1000, seed=5)
+        v = scenes.transformed(v, 1.0, (1000, -500, 2000))
+    elif name == "box":
         v, i, _ = O.obj_parse(open(scenes.BOX_OBJ, "rb").read())
     elif name.startswith("random"):
         v, i = scenes.random_triangles(int(name[6:]), seed=5)

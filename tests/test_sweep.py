@@ -90,7 +90,8 @@ def make_rays(v, idx, n, seed):
     P = V[idx.reshape(-1, 3)]
     t = rng.integers(0, len(P), k)
     b = rng.dirichlet([1, 1, 1], k).astype(np.float32)
-    o = np.tile(np.float32([0.3, 0.2, 3.0]), (k, 1))
+    # (placed by the scene's bounds: (0.3, 0.2, 3.0) for the box's [-1, 1]^3)
+    o = np.tile(((lo + hi) / 2 + ext.max() * np.float32([0.15, 0.1, 1.5])).astype(np.float32), (k, 1))
     fam.append((o, _unit((P[t] * b[:, :, None]).sum(1) - o)))
     # 4. one or two zero direction components, origins anywhere (half of them inside)
     o = rng.uniform(lo - ext * 0.5, hi + ext * 0.5, (k, 3))
@@ -133,14 +134,37 @@ def check(v, idx, nodes, rays):
     return rc == 0, st
 
 
+def _box_mesh():
+    with open(scenes.BOX_OBJ, "rb") as f:
+        v, i, _ = oracle_lib.obj_parse(f.read())
+    return v, i
+
+
+# Tiny scenes away from the origin-centred, unit-sized, non-degenerate ones:
+# name -> (vertices, indices) before the BVH build (shared with the GPU tests).
+HOSTILE = {
+    "box@300": lambda: (scenes.transformed(_box_mesh()[0], 1.0, (300, 300, -300)), _box_mesh()[1]),
+    "box*50": lambda: (scenes.transformed(_box_mesh()[0], 50.0, (0, 0, 0)), _box_mesh()[1]),
+    "box*0.01": lambda: (scenes.transformed(_box_mesh()[0], 0.01, (0, 0, 0)), _box_mesh()[1]),
+    "box:copies2": lambda: scenes.coincident_copies(*_box_mesh(), 2),
+    "tri4:copies8": lambda: scenes.coincident_copies(*scenes.random_triangles(4), 8),
+    "flat_quad": scenes.flat_quad,
+    "tri8:degenerate": lambda: scenes.with_degenerates(*scenes.random_triangles(8)),
+}
+# (distinct boxes, leaves) of the tables where the scene fixes them
+HOSTILE_TABLES = {"box:copies2": (7, 24), "tri4:copies8": (7, 32), "flat_quad": (1, 2), "tri8:degenerate": (15, 8)}
+
+
 def _scene(name):
     if name == "box":
         return _box()
+    if name in HOSTILE:
+        return _built(*HOSTILE[name]())
     kind, n = name.split(":")
     return _built(*(scenes.grid_mesh(int(n)) if kind == "grid" else scenes.random_triangles(int(n))))
 
 
-SCENES = ["box", "grid:2", "grid:3", "grid:4", "tri:1", "tri:2", "tri:3", "tri:7", "tri:16", "tri:32"]
+SCENES = ["box", "grid:2", "grid:3", "grid:4", "tri:1", "tri:2", "tri:3", "tri:7", "tri:16", "tri:32"] + sorted(HOSTILE)
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -153,6 +177,8 @@ def test_sweep_equals_threaded_walk(name):
     # up to 32 distinct boxes the box mask is 32 bits wide, else 64 (tri:32 has 63)
     assert inf[1] == idx.size // 3 and 1 <= inf[0] <= min(64, inf[3])
     assert inf[2] == 0, "every need mask holds the root's bit"
+    if name in HOSTILE_TABLES:
+        assert (int(inf[0]), int(inf[1])) == HOSTILE_TABLES[name]
     assert (int(st[0]), int(st[1]), int(st[2])) == (0, 0, 0), \
         f"{name}: leaf sequence / closest / shadow mismatches {st[:3]}, first bad ray {int(st[3])}: {rays[int(st[3]) % len(rays)]}"
     # the rays do reach the geometry

@@ -103,7 +103,10 @@ def scene(name):
     return test_sweep._scene(name)
 
 
-SCENES = ["box", "cuboid", "grid:2", "tri:4"]
+# the test_sweep.HOSTILE names: the box moved and scaled keeps its six hull faces
+# (the codes compare bits, not values near the origin); the flat quad's only box is the root
+MOVED_BOXES = ["box@300", "box*50", "box*0.01", "box:copies2"]
+SCENES = ["box", "cuboid", "grid:2", "tri:4"] + MOVED_BOXES + ["flat_quad", "tri4:copies8"]
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -120,8 +123,10 @@ def test_hull_faces_equal_slab(name):
     assert int(st[2]) == 0, f"the table without codes differs from sweep_leaves(sweep_mask): {st[2]}; {where}"
     assert int(st[3]) == 0, f"the sweep past the root differs from the two passes without the early exit: {st[3]}; {where}"
     assert int(st[4]) == 0, f"sweep_slab_hull differs from slab on {int(st[4])} (ray, box) pairs; {where}"
-    if name == "box":
+    if name == "box" or name in MOVED_BOXES:
         assert (boxes, flat, coded) == (7, 6, 6), "the box's six face boxes are hull faces"
+    if name == "flat_quad":
+        assert (boxes, leaves, coded) == (1, 2, 0), "the root alone: nothing to share its products with"
     if name == "cuboid":
         assert coded >= 2, "the cuboid has hull faces"
     if name.startswith("tri"):

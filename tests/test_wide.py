@@ -94,13 +94,24 @@ def check(v, idx, nodes, rays, build=(WIDE_SAH, 64, 1)):
 
 def _unit(a):
     a = np.asarray(a, np.float32)
-    return (a / np.sqrt((a * a).sum(-1, keepdims=True))).astype(np.float32)
+    with np.errstate(invalid="ignore"):   # a degenerate triangle's normal is 0/0: its rays are NaN, and must agree too
+        return (a / np.sqrt((a * a).sum(-1, keepdims=True))).astype(np.float32)
 
 
-def make_rays(v, idx, n, seed, lo=-1.2, hi=1.2):
-    """A mix of ray families (see the module docstring); n x 8 float32."""
+AIMED = (1, 2, 3, 5)   # make_rays families (0-based) that aim at the scene's triangles or from them
+
+
+def make_rays(v, idx, n, seed):
+    """A mix of ray families (see the module docstring); n x 8 float32.  The
+    families sit relative to the scene's bounds (centre c, largest half extent
+    h): origins in c +- 1.2 h, the camera-like point at c + h (0.3, 0.2, 3);
+    for a scene in [-1, 1]^3 these are the ranges the walk was first tested on."""
     rng = np.random.default_rng(seed)
     V = v.reshape(-1, 3)
+    blo, bhi = V.min(0).astype(np.float64), V.max(0).astype(np.float64)
+    c = (blo + bhi) / 2
+    h = float(np.max(bhi - blo)) / 2
+    lo, hi = c - 1.2 * h, c + 1.2 * h
     T = idx.reshape(-1, 3)
     P = V[T]                                 # triangles x 3 x 3
     e1, e2 = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
@@ -108,10 +119,10 @@ def make_rays(v, idx, n, seed, lo=-1.2, hi=1.2):
     out = []
     k = n // 6
     # 1. random origins in / around the scene, random directions
-    o = rng.uniform(lo * 1.5, hi * 1.5, (k, 3)).astype(np.float32)
+    o = rng.uniform(c - 1.8 * h, c + 1.8 * h, (k, 3)).astype(np.float32)
     out.append((o, _unit(rng.normal(size=(k, 3)))))
     # 2. from a camera-like point outside towards random scene points
-    o = np.tile(np.float32([0.3, 0.2, 3.0]), (k, 1))
+    o = np.tile((c + h * np.array([0.3, 0.2, 3.0])).astype(np.float32), (k, 1))
     tgt = rng.uniform(lo, hi, (k, 3)).astype(np.float32)
     out.append((o, _unit(tgt - o)))
     # 3. from surface points (offset +-1e-3 along the normal, :355, :370) in random directions
@@ -148,11 +159,23 @@ def make_rays(v, idx, n, seed, lo=-1.2, hi=1.2):
     return rays
 
 
-def run_scene(v, i, n_rays, seed, build=(WIDE_SAH, 64, 1)):
+def run_scene(v, i, n_rays, seed, build=(WIDE_SAH, 64, 1), rays=None):
+    """make_rays' mix (or the given rays(v, idx)) as closest-hit and as shadow queries."""
     v, idx, nodes = _scene(v, i)
-    rays = make_rays(v, idx, n_rays, seed)
+    mixed = rays is None
+    rays = make_rays(v, idx, n_rays, seed) if mixed else rays(v, idx)
     out, st = check(v, idx, nodes, rays, build)     # closest
     assert st[0] == 0, f"closest-hit mismatches: {int(st[0])} (first ray {int(st[7])}: {rays[int(st[7])]})"
+    if mixed:
+        # the rays reach the scene: hits in every family that aims at it, and
+        # axis-parallel rays handed back to the exact walk
+        k = n_rays // 6
+        for fam in AIMED:
+            assert np.count_nonzero(out[fam * k:(fam + 1) * k if fam < 5 else n_rays, 3] > 0) > 0, \
+                f"family {fam + 1} hits nothing"
+        assert st[2] > 0
+    else:
+        assert np.count_nonzero(out[:, 3] > 0) > len(rays) // 2
     # shadow queries with limits around the closest hit (and far / negative / NaN ones)
     rng = np.random.default_rng(seed + 1)
     sh = rays.copy()
@@ -233,6 +256,71 @@ def test_wide_walk_dense_tiny_cloud(build):
     # (queued tests cull against a best hit that lags by up to a queue's worth;
     # an 8-wide node queues up to eight leaves at once)
     assert st[4] < (0.8 if not build[2] else 0.97 if build[1] == 80 else 0.95) * st[6], (int(st[4]), int(st[6]))
+
+
+# Scenes away from the [-1, 1]^3 the cases above live in.  The cull bound's
+# terms grow with |o - v0|, with the edge lengths and with the largest
+# coefficients below a node (wide_bvh.cpp: wide_tri_coeffs, node_cull_consts),
+# and the 64-byte nodes' 8-bit grid is rounded outward from each node's own
+# origin and scale.
+HOSTILE = {
+    "cloud_far": lambda: (scenes.transformed(scenes.random_triangles(20000, seed=7)[0], 1.0, (1000, -500, 2000)),
+                          scenes.random_triangles(20000, seed=7)[1]),
+    "sphere_at_300": lambda: (scenes.transformed(scenes.displaced_sphere(3)[0], 1.0, (300, 300, -300)),
+                              scenes.displaced_sphere(3)[1]),
+    "sphere_x50": lambda: (scenes.transformed(scenes.displaced_sphere(3)[0], 50.0, (0, 0, 0)),
+                           scenes.displaced_sphere(3)[1]),
+    "sphere_x0.05": lambda: (scenes.transformed(scenes.displaced_sphere(3)[0], 0.05, (0, 0, 0)),
+                             scenes.displaced_sphere(3)[1]),
+    "floor_and_cloud": scenes.floor_and_cloud,
+    "coincident_x6": lambda: scenes.coincident_copies(*scenes.displaced_sphere(2), 6),
+    "degenerates": lambda: scenes.with_degenerates(*scenes.random_triangles(3000, seed=8, spread=0.5, size=0.02)),
+}
+
+
+@BUILDS
+@pytest.mark.parametrize("name", sorted(HOSTILE))
+def test_wide_walk_hostile_geometry(name, build):
+    """Translated, scaled, mixed-scale, all-ties and degenerate scenes: the
+    culled walk's closest hits and shadow answers are still the oracle's."""
+    v, i = HOSTILE[name]()
+    st, _ = run_scene(v, i, 30000, seed=21 + sorted(HOSTILE).index(name), build=build)
+    if name == "floor_and_cloud":
+        # the floor's coefficients exceed the bound (c1 = 0): the nodes above it
+        # do not cull, their siblings still do
+        assert st[3] < st[5] / 2, (int(st[3]), int(st[5]))
+
+
+def far_rays(v, idx, n, seed, dmin=1.0, dmax=1e5):
+    """Rays aimed at points of the triangles from dmin to dmax away
+    (log-uniform), tilted 1e-3 to 1 out of the triangle's plane: S = |o - v0|,
+    which the cull bound's eps0 + eps1 S and k2 S terms multiply, is up to
+    five orders of magnitude above the scene's size, on tests whose |det| is
+    small."""
+    rng = np.random.default_rng(seed)
+    P = v.reshape(-1, 3)[idx.reshape(-1, 3)]
+    nrm = _unit(np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]))
+    t = rng.integers(0, len(P), n)
+    b = rng.dirichlet([1, 1, 1], n).astype(np.float32)
+    tp = (P[t] * b[:, :, None]).sum(1)
+    inplane = _unit(np.cross(nrm[t], rng.normal(size=(n, 3))))
+    tilt = (10.0 ** rng.uniform(-3, 0, n)).astype(np.float32)[:, None] * np.where(rng.random((n, 1)) < .5, 1, -1)
+    d = _unit(inplane + nrm[t] * tilt)
+    dist = (10.0 ** rng.uniform(np.log10(dmin), np.log10(dmax), (n, 1))).astype(np.float32)
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0:3] = (tp - d * dist).astype(np.float32)
+    rays[:, 3:6] = d
+    return rays
+
+
+@BUILDS
+def test_wide_walk_far_origins(build):
+    """The hostile scenes move the origins with the geometry; here the origins
+    alone move away, from a dense cloud whose triangles hide each other, so a
+    child culled wrongly would lose the hit."""
+    v, i = scenes.random_triangles(30000, seed=9, spread=0.2, size=0.004)
+    st, _ = run_scene(v, i, 0, seed=31, build=build, rays=lambda v, idx: far_rays(v, idx, 40000, 32))
+    assert st[3] < st[5] / 3, (int(st[3]), int(st[5]))   # and it still culls
 
 
 def test_wide_info_and_refusals():
