@@ -26,6 +26,7 @@
 #include "pt_device.h"
 #include "pt_group.h"
 #include "pt_cull.h"
+#include "pt_isect.h"
 #include "pt_math.h"
 #include "scene/bvh.h"
 #include "scene/camera.h"
@@ -295,6 +296,7 @@ struct pt_context {
   int opt_count = 0;          // PT_OPT_COUNT_TRACED
   int opt_small_sweep = -1;   // PT_OPT_SMALL_SWEEP: -1 auto (kSweepAutoBoxes), 0 off, 1 whenever the scene has a table
   int opt_sweep_hull = 1;     // PT_OPT_SWEEP_HULL
+  int opt_exit_skip = 1;      // PT_OPT_EXIT_SKIP
   int opt_wide_build = 1;     // PT_OPT_WIDE_BUILD (pt::WideBuild; read at upload)
   int opt_wf_streams = 1;     // PT_OPT_WF_STREAMS (2 measured slower: 10M cloud +9 %, sphere -0.8 %)
   hipStream_t wf_stream2 = nullptr;           // the wavefront pipeline's second half (created on first use)
@@ -351,6 +353,7 @@ struct pt_context {
   std::vector<float> key_scratch, items_scratch;   // per-launch keys, built without reallocating
   float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};   // root AABB of the uploaded tree
   std::vector<pt_area_light> lights_host;
+  bool exit_normals = false;   // some triangle's stored normal is axis-pure (pt_isect.h exit_normal)
   // wavefront pipeline buffers (PT_OPT_KERNEL 3), grown on demand
   ptd::WfBuffers wf{};
   void* wf_block = nullptr;
@@ -1108,6 +1111,13 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   p.n_batches = n_batches;
   p.max_depth = c->params.max_depth;
   p.sss_bounces = c->params.sss_bounces;
+  // the exit skip (PT_OPT_EXIT_SKIP): only where it can fire and rad is finite
+  p.exit_skip = c->opt_exit_skip && c->exit_normals && !c->stats_mode ? 1 : 0;
+  for (int i = 0; i < c->n_lights && p.exit_skip; ++i)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(c->lights_host[(size_t)i].intensity[k])) p.exit_skip = 0;
+  memcpy(p.root_lo, c->root_lo, sizeof p.root_lo);
+  memcpy(p.root_hi, c->root_hi, sizeof p.root_hi);
   camera_params(c->cam, &p);
   p.blocks_x = (c->width + 15) / 16;
   p.blocks_total = p.blocks_x * ((c->height + 15) / 16);
@@ -1591,6 +1601,17 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
       pt::build_wide_bvh((const float*)nodes, n_nodes, (flags & PT_NODES_INT_BITS) != 0, vertices, n_vertex_floats,
                          indices, n_indices / 3, &wide, c->opt_wide_build);
   float lo[3] = {threaded[0].x, threaded[0].y, threaded[0].z};   // node 0 is the root
+  // the exit skip (PT_OPT_EXIT_SKIP) can fire only on an axis-pure stored normal: look for one with the
+  // ops of setup_tris_kernel (a cross product with two zero components first: normalize keeps a zero)
+  bool exit_normals = false;
+  for (size_t t = 0; t < n_indices / 3 && !exit_normals; ++t) {
+    const float* a = vertices + 3 * (size_t)indices[3 * t];
+    const float* b = vertices + 3 * (size_t)indices[3 * t + 1];
+    const float* d = vertices + 3 * (size_t)indices[3 * t + 2];
+    const ptm::v3 v0 = ptm::mk(a[0], a[1], a[2]);
+    const ptm::v3 cr = ptm::cross(ptm::sub(ptm::mk(b[0], b[1], b[2]), v0), ptm::sub(ptm::mk(d[0], d[1], d[2]), v0));
+    if ((cr.x == 0.0f) + (cr.y == 0.0f) + (cr.z == 0.0f) >= 2) exit_normals = ptd::exit_normal(ptm::normalize(cr));
+  }
   float hi[3] = {threaded[1].x, threaded[1].y, threaded[1].z};
   PT_HIP(hipSetDevice(c->device));
   { const int rc_ = quiesce(c); if (rc_) return rc_; }
@@ -1678,6 +1699,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->sweep_hull = has_sweep ? sweep.n_hull : 0;
   memcpy(c->root_lo, lo, sizeof lo);
   memcpy(c->root_hi, hi, sizeof hi);
+  c->exit_normals = exit_normals;
   c->has_scene = true;
   c->scene_serial++;
   return PT_OK;
@@ -2394,6 +2416,10 @@ int pt_set_option(pt_context* c, int key, int value) {
     case PT_OPT_SWEEP_HULL:
       if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_SWEEP_HULL takes 0 or 1");
       c->opt_sweep_hull = value;
+      return PT_OK;
+    case PT_OPT_EXIT_SKIP:
+      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_EXIT_SKIP takes 0 or 1");
+      c->opt_exit_skip = value;
       return PT_OK;
     case PT_OPT_MOMENTS:
       if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_MOMENTS takes 0 or 1");

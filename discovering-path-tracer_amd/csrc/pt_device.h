@@ -166,8 +166,16 @@ struct RenderParams {
   // luminance moments (PT_OPT_MOMENTS): float2 {m1, m2} per pixel of the frame, folded beside the colour
   // by the MOMENTS instantiations (launch_render / launch_wavefront pick them when this is set); the live
   // pixels only -- the host zeroes the image before a launch from batch 0, and a culled pixel's fold of
-  // L = +0 into +0 is +0.  Last member: the layout the other instantiations read does not move
+  // L = +0 into +0 is +0.  After every older member: the layout the other instantiations read does not move
   float2* moments = nullptr;
+  // the exit skip (PT_OPT_EXIT_SKIP, pt_isect.h exit_skip): set by the host when the option is on, some
+  // triangle's stored normal is axis-pure (exit_normal) and every light is finite; the fast path tracers
+  // then end a path whose bounce ray provably leaves through a face of the root box [root_lo, root_hi]
+  // (node 0 of the reference's tree, bitwise).  Clear: no kernel evaluates the predicate -- the LDS-staged
+  // render kernels branch on it, the others are the instantiations without it (launch_render,
+  // launch_wavefront), which read nothing past `moments`
+  int exit_skip = 0;
+  float root_lo[3] = {}, root_hi[3] = {};
 };
 constexpr int kMixShift = 24;
 constexpr int kMaxCullRects = 8;

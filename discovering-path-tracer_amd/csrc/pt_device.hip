@@ -382,20 +382,15 @@ __device__ __forceinline__ v3 sample_sphere(uint32_t* rng) {
   return mk(r * cs, r * sn, z);
 }
 
-// sampleHemisphere (:229-243)
-__device__ __forceinline__ v3 sample_hemisphere(v3 n, uint32_t* rng) {
-  const float r1 = rng_next(rng);
+// sampleHemisphere (:229-243): pt_isect.h hemisphere_dir on its two draws
+// (r1: the first, already made -- the exit skip reads it before the rest)
+__device__ __forceinline__ v3 sample_hemisphere_r1(v3 n, float r1, uint32_t* rng) {
   const float r2 = rng_next(rng);
-  const float th = acos_(sqrt_(1.0f - r1));
-  const float ph = (2.0f * 0x1.921fb6p+1f) * r2;
-  float st, ct, sp, cp;
-  sincos_(th, &st, &ct);
-  sincos_(ph, &sp, &cp);
-  const v3 l = mk(st * cp, st * sp, ct);
-  const v3 upv = fabs_(n.z) < 0.999f ? mk(0.0f, 0.0f, 1.0f) : mk(1.0f, 0.0f, 0.0f);
-  const v3 t = normalize(cross(upv, n));
-  const v3 b = cross(n, t);
-  return add(add(muls(t, l.x), muls(b, l.y)), muls(n, l.z));
+  return hemisphere_dir(n, r1, r2);
+}
+// The exit skip (pt_isect.h exit_skip) on the kernel's values.
+__device__ __forceinline__ bool exit_skipped(const RenderParams& P, v3 hn, v3 ro, float r1) {
+  return exit_skip(hn, ro, r1, mk(P.root_lo[0], P.root_lo[1], P.root_lo[2]), mk(P.root_hi[0], P.root_hi[1], P.root_hi[2]));
 }
 
 __device__ __forceinline__ v3 tri_normal(const RenderParams& P, int tri) {
@@ -564,10 +559,11 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
         }
       }
       rad = add(rad, muls(mul(mul(thr, sss_thr), sl), 1.0f + sss_radius * 0.5f));
-      sss_thr = mul(sss_thr, muls(sss_albedo, exp_(-travel / (sss_radius * 1.5f))));
-      // the last step's next direction (:406-407) is never traced: its two
-      // draws only advance the stream (the same state as sample_sphere's)
+      // the last step's throughput is never read and its next direction
+      // (:406-407) never traced: its two draws only advance the stream (the
+      // same state as sample_sphere's)
       if (STATS || k + 1 < P.sss_bounces) {
+        sss_thr = mul(sss_thr, muls(sss_albedo, exp_(-travel / (sss_radius * 1.5f))));
         so = sub(cp, muls(sn, OFFSET));
         sd = sample_sphere(&rng);
       } else {
@@ -578,9 +574,12 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
     // the last bounce's direction (:411-414) is never traced and the stream
     // is not read again: the path ends here
     if (!STATS && depth + 1 >= P.max_depth) break;
-    const v3 bd = sample_hemisphere(hn, &rng);          // :411-414
-    thr = mul(thr, muls(albedo, dot(hn, bd)));
     ro = add(hp, muls(hn, OFFSET));
+    const float r1 = rng_next(&rng);
+    // the bounce ray provably misses the root box (exit_skip): rad stays
+    if (!STATS && P.exit_skip && exit_skipped(P, hn, ro, r1)) break;
+    const v3 bd = sample_hemisphere_r1(hn, r1, &rng);   // :411-414
+    thr = mul(thr, muls(albedo, dot(hn, bd)));
     rd = bd;
   }
   return rad;
@@ -593,7 +592,9 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
 // SSS step's last shadow ray with the next SSS ray.  The RNG draws, the float
 // operations and their order are path_trace's: a shadow result is only used
 // after the pair returns, to finish the same sums in the same order.
-template <bool CNT = false>
+// EXIT: the instantiation the host picks when P.exit_skip is set (this kernel's
+// registers are tight: a branch on the flag costs the others 10-17 spilled VGPRs).
+template <bool CNT = false, bool EXIT = false>
 __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, int* cand, Ctr& c) {
   float* pk = (float*)(cand + kCand * 64);
   const float OFFSET = 0.001f;
@@ -708,7 +709,12 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
       rad = add(rad, muls(mul(thr_k, sl), 1.0f + sss_radius * 0.5f));
     }
 
-    const v3 bd = sample_hemisphere(hn, &rng);          // :411-414
+    const float r1 = rng_next(&rng);
+    if constexpr (EXIT) {
+      // the bounce ray provably misses the root box (exit_skip): rad stays
+      if (depth + 1 >= P.max_depth || exit_skipped(P, hn, add(hp, muls(hn, OFFSET)), r1)) break;
+    }
+    const v3 bd = sample_hemisphere_r1(hn, r1, &rng);   // :411-414
     thr = mul(thr, muls(albedo, dot(hn, bd)));
     ro = add(hp, muls(hn, OFFSET));
     rd = bd;
@@ -886,7 +892,9 @@ __device__ unsigned long long g_wg_trace[kWgTraceCap][4];
 // MOMENTS (PT_OPT_MOMENTS; never with STATS or CNT): the lane that folds a
 // pixel's red also folds the sample luminances L and L * L into P.moments, in
 // batch order with the colour's own step (fold_one).
-template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0, bool MOMENTS = false>
+// EXIT (device-memory scenes, never with STATS): path_trace_fused's instantiation
+// with the exit skip; the LDS-staged kernels branch on P.exit_skip instead.
+template <bool STATS, bool LDS, bool CNT = false, int SWEEP = 0, bool MOMENTS = false, bool EXIT = false>
 #ifndef PT_RENDER_MIN_BLOCKS
 #define PT_RENDER_MIN_BLOCKS 5
 #endif
@@ -1089,7 +1097,7 @@ __global__ __launch_bounds__(256, SWEEP || (LDS && !STATS) ? 6 : PT_RENDER_MIN_B
       if (STATS || LDS)
         col = path_trace<STATS, !LDS, CNT, SWEEP>(P, origin, dir, seed, c, cand);
       else
-        col = path_trace_fused<CNT>(P, origin, dir, seed, cand, c);
+        col = path_trace_fused<CNT, EXIT>(P, origin, dir, seed, cand, c);
       col4 = make_float4(col.x, col.y, col.z, 1.0f);                      // vec4(color, 1.0)
       }
      }
@@ -1470,7 +1478,9 @@ __device__ __forceinline__ void camera_ray(const CamFrame& F, uint32_t seed, v3*
 // caller traces it and calls again with T.lim/T.res holding the result) or
 // the sample is complete (returns false, *out = its radiance).  Shared by the
 // wavefront pipeline's generation, shading and tail kernels.
-template <bool STATS>
+// EXIT: with the exit skip (the shading and tail kernels' instantiations that
+// launch_wavefront picks when P.exit_skip is set; the others are the code of before).
+template <bool STATS, bool EXIT = false>
 __device__ bool path_step(const RenderParams& P, const CamFrame& F, PathSt& S, Trav& T, Ctr& c, v3* out) {
   const float OFFSET = 0.001f;
   const v3 albedo = mk(0.8f, 0.8f, 0.8f);
@@ -1631,7 +1641,15 @@ __device__ bool path_step(const RenderParams& P, const CamFrame& F, PathSt& S, T
     }
     if (!finished && S.phase == -1) {
       // indirect bounce (:411-414)
-      const v3 bd = sample_hemisphere(S.hn, &S.rng);
+      const float r1 = rng_next(&S.rng);
+      if constexpr (EXIT) {
+        // the ray provably misses the root box (exit_skip): the path ends with the radiance it has
+        if (exit_skipped(P, S.hn, add(S.hp, muls(S.hn, OFFSET)), r1)) {
+          *out = S.rad;
+          return false;
+        }
+      }
+      const v3 bd = sample_hemisphere_r1(S.hn, r1, &S.rng);
       S.thr = mul(S.thr, muls(albedo, dot(S.hn, bd)));
       const v3 ro = add(S.hp, muls(S.hn, OFFSET));
       S.depth++;
@@ -2438,6 +2456,7 @@ __global__ __launch_bounds__(256, PT_WIDE_MIN_BLOCKS) void wf_trace_wide_kernel(
 #define PT_WF_SHADE_MIN_BLOCKS 4
 #endif
 constexpr int kWfBins = 16;
+template <bool EXIT = false>
 __global__ __launch_bounds__(256, PT_WF_SHADE_MIN_BLOCKS) void wf_shade_kernel(RenderParams P, WfBuffers B, int cur) {
   if (blockIdx.x == 0 && threadIdx.x == 0) B.counters[2] = 0;   // the next traversal's cursor
   const int count = B.counters[cur];
@@ -2479,13 +2498,13 @@ __global__ __launch_bounds__(256, PT_WF_SHADE_MIN_BLOCKS) void wf_shade_kernel(R
         T.res = occluded<false, false>(P, T.o, T.d, T.lim, c) ? 1 : 0;
       }
       v3 col;
-      need = path_step<false>(P, F, S, T, c, &col);
+      need = path_step<false, EXIT>(P, F, S, T, c, &col);
       if (fused) {
         // the shading just derived the shadow ray the trace kernel walked
         // (same hit, same draws, same ops): take its answer
         if (need && T.shadow != 0) {
           T.res = T.shadow == 2 ? 0 : fused - 1;
-          need = path_step<false>(P, F, S, T, c, &col);
+          need = path_step<false, EXIT>(P, F, S, T, c, &col);
         } else {   // cannot happen; fail loudly rather than shade wrongly
           need = false;
           col = mk(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
@@ -2493,7 +2512,7 @@ __global__ __launch_bounds__(256, PT_WF_SHADE_MIN_BLOCKS) void wf_shade_kernel(R
       }
       while (P.wide && need && T.shadow == 2) {   // a null shadow query (trav_null): unoccluded, answered here
         T.res = 0;
-        need = path_step<false>(P, F, S, T, c, &col);
+        need = path_step<false, EXIT>(P, F, S, T, c, &col);
       }
       if (!need) B.colors[p] = make_float4(col.x, col.y, col.z, 1.0f);
     }
@@ -2553,7 +2572,7 @@ __global__ __launch_bounds__(256, PT_WF_SHADE_MIN_BLOCKS) void wf_shade_kernel(R
 #ifndef PT_WF_TAIL_MIN_BLOCKS
 #define PT_WF_TAIL_MIN_BLOCKS 4
 #endif
-template <bool CNT, bool QN>
+template <bool CNT, bool QN, bool EXIT = false>
 __global__ __launch_bounds__(256, PT_WF_TAIL_MIN_BLOCKS) void wf_tail_kernel(RenderParams P, WfBuffers B, int cur) {
   const int count = B.counters[cur];
   if (count == 0 || count >= P.wf_tail) return;
@@ -2628,10 +2647,10 @@ __global__ __launch_bounds__(256, PT_WF_TAIL_MIN_BLOCKS) void wf_tail_kernel(Ren
       PathSt S;
       wf_load_state(B, cur, p, R.o, R.d, &S);   // PH_SSS: the walk ray is S.so / S.sd
       v3 col;
-      bool need = path_step<false>(P, F, S, T, c, &col);
+      bool need = path_step<false, EXIT>(P, F, S, T, c, &col);
       while (need && T.shadow == 2) {   // null shadow queries (trav_null)
         T.res = 0;
-        need = path_step<false>(P, F, S, T, c, &col);
+        need = path_step<false, EXIT>(P, F, S, T, c, &col);
       }
       if (need) {
         wf_store_state(B, cur, p, S);
@@ -2899,16 +2918,20 @@ hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipS
   if (lds > kMaxSceneLds) return hipErrorInvalidValue;
   if (p.moments && (stats || cnt || p.pack_out)) return hipErrorInvalidValue;
   void (*kern)(RenderParams);
+  const bool ex = p.exit_skip != 0 && !stats;   // the exit skip: device-memory scenes take the EXIT instantiations
   if (p.moments)   // PT_OPT_MOMENTS: the same choice among the MOMENTS instantiations
     kern = sweep ? (p.sweep_hull ? render_kernel<false, true, false, 2, true> : render_kernel<false, true, false, 1, true>)
-                 : (lds_scene ? render_kernel<false, true, false, 0, true> : render_kernel<false, false, false, 0, true>);
+                 : (lds_scene ? render_kernel<false, true, false, 0, true>
+                              : (ex ? render_kernel<false, false, false, 0, true, true> : render_kernel<false, false, false, 0, true>));
   else if (sweep)
     kern = p.sweep_hull ? render_kernel<false, true, false, 2> : render_kernel<false, true, false, 1>;
   else if (cnt)
-    kern = lds_scene ? render_kernel<false, true, true> : render_kernel<false, false, true>;
+    kern = lds_scene ? render_kernel<false, true, true>
+                     : (ex ? render_kernel<false, false, true, 0, false, true> : render_kernel<false, false, true>);
   else
     kern = lds_scene ? (stats ? render_kernel<true, true> : render_kernel<false, true>)
-                     : (stats ? render_kernel<true, false> : render_kernel<false, false>);
+                     : (stats ? render_kernel<true, false>
+                              : (ex ? render_kernel<false, false, false, 0, false, true> : render_kernel<false, false>));
   if (grid > 0) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p);
   return hipGetLastError();
 }
@@ -2987,12 +3010,17 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
                        : (cnt ? wf_trace_wide_kernel<true, 0> : wf_trace_wide_kernel<false, 0>);
   const size_t lds_t = wide ? 0 : lds;
   if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_t, trace, 256, lds_t);
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, wf_shade_kernel, 256, 0);
+  // the exit skip: the shading and tail kernels' EXIT instantiations (generation never reaches a bounce)
+  const bool ex = p0.exit_skip != 0;
+  void (*shade)(RenderParams, WfBuffers, int) = ex ? wf_shade_kernel<true> : wf_shade_kernel<false>;
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, shade, 256, 0);
   // PT_OPT_WF_TAIL (the 4-wide layouts of the wide walk): wf_tail_kernel after each round's trace
   const bool tail = wide && p0.wf_tail > 0;
   void (*tailk)(RenderParams, WfBuffers, int) =
-      p0.wide_qn ? (cnt ? wf_tail_kernel<true, true> : wf_tail_kernel<false, true>)
-                 : (cnt ? wf_tail_kernel<true, false> : wf_tail_kernel<false, false>);
+      ex ? (p0.wide_qn ? (cnt ? wf_tail_kernel<true, true, true> : wf_tail_kernel<false, true, true>)
+                       : (cnt ? wf_tail_kernel<true, false, true> : wf_tail_kernel<false, false, true>))
+         : (p0.wide_qn ? (cnt ? wf_tail_kernel<true, true> : wf_tail_kernel<false, true>)
+                       : (cnt ? wf_tail_kernel<true, false> : wf_tail_kernel<false, false>));
   if (p0.wf_tail > 0 && !tail) return hipErrorInvalidValue;   // the trace and shading kernels would skip its lists
   int per_cu_x = 0;
   if (e == hipSuccess && tail) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_x, tailk, 256, 0);
@@ -3057,7 +3085,7 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
       for (int h = 0; h < H; ++h) hipLaunchKernelGGL(trace, dim3(grid_t), dim3(256), lds_t, sh[h], ph[h], bh[h], cur);
       if (tail)
         for (int h = 0; h < H; ++h) hipLaunchKernelGGL(tailk, dim3(grid_x), dim3(256), 0, sh[h], ph[h], bh[h], cur);
-      for (int h = 0; h < H; ++h) wf_shade_kernel<<<grid_s, 256, 0, sh[h]>>>(ph[h], bh[h], cur);
+      for (int h = 0; h < H; ++h) hipLaunchKernelGGL(shade, dim3(grid_s), dim3(256), 0, sh[h], ph[h], bh[h], cur);
       cur ^= 1;
     }
     for (int h = 0; h < H; ++h)

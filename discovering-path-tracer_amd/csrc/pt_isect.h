@@ -41,4 +41,48 @@ PT_FN bool tri_test(v3 o, v3 d, float4 A, float4 B, float4 C, float* tout) {
   return true;
 }
 
+// sampleHemisphere (:229-243) from its two draws, r1 first.
+__host__ __device__ static __forceinline__ v3 hemisphere_dir(v3 n, float r1, float r2) {
+  const float th = acos_(sqrt_(1.0f - r1));
+  const float ph = (2.0f * 0x1.921fb6p+1f) * r2;
+  float st, ct, sp, cp;
+  sincos_(th, &st, &ct);
+  sincos_(ph, &sp, &cp);
+  const v3 l = mk(st * cp, st * sp, ct);
+  const v3 upv = fabs_(n.z) < 0.999f ? mk(0.0f, 0.0f, 1.0f) : mk(1.0f, 0.0f, 0.0f);
+  const v3 t = normalize(cross(upv, n));
+  const v3 b = cross(n, t);
+  return add(add(muls(t, l.x), muls(b, l.y)), muls(n, l.z));
+}
+
+// The exit skip (PT_OPT_EXIT_SKIP): whether the bounce ray from
+// ro = hp + hn * OFFSET provably misses the root box [lo, hi] whatever its
+// hemisphere direction, given r1, the draw sample_hemisphere makes first.
+// True only when, for one axis a: hn's other two components are +-0 bitwise
+// and 0.999 <= |hn.a| <= 2; ro lies more than 1e-30 beyond the root's face on
+// the side hn.a points to; and r1 < 1 (the cosine sincos_ returns for
+// acos_(sqrt_(1 - r1)) is positive on [0, 1) and negative at 1.0f).  Then the
+// direction's a component is hn.a * ct exactly, both root slab products on a
+// are negative and slab() is false.  tests/exit_skip_check.cpp checks it.
+PT_FN bool exit_axis(float n, float o, float lo, float hi) {
+  const float an = fabs_(n);
+  const float d = n > 0.0f ? o - hi : lo - o;
+  return an >= 0.999f && an <= 2.0f && d > 1e-30f;
+}
+PT_FN bool exit_skip(v3 hn, v3 ro, float r1, v3 lo, v3 hi) {
+  const bool zx = (f2u(hn.x) << 1) == 0u, zy = (f2u(hn.y) << 1) == 0u, zz = (f2u(hn.z) << 1) == 0u;
+  bool out = false;
+  if (zy && zz) out = exit_axis(hn.x, ro.x, lo.x, hi.x);
+  else if (zx && zz) out = exit_axis(hn.y, ro.y, lo.y, hi.y);
+  else if (zx && zy) out = exit_axis(hn.z, ro.z, lo.z, hi.z);
+  return out && r1 < 1.0f;
+}
+// Condition 1 alone: a normal for which exit_skip can ever hold (the host's
+// per-scene flag).
+PT_FN bool exit_normal(v3 hn) {
+  const bool zx = (f2u(hn.x) << 1) == 0u, zy = (f2u(hn.y) << 1) == 0u, zz = (f2u(hn.z) << 1) == 0u;
+  const float an = fabs_(zy && zz ? hn.x : zx && zz ? hn.y : hn.z);
+  return ((zy && zz) || (zx && zz) || (zx && zy)) && an >= 0.999f && an <= 2.0f;
+}
+
 }  // namespace ptd

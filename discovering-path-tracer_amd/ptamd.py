@@ -44,6 +44,7 @@ PT_OPT_SMALL_SWEEP = 24
 PT_OPT_CULL_TIGHT = 25
 PT_OPT_SWEEP_HULL = 26
 PT_OPT_MOMENTS = 27
+PT_OPT_EXIT_SKIP = 28
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).

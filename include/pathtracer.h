@@ -46,7 +46,7 @@ extern "C" {
  * PT_OPT_SWEEP_HULL); the per-pixel luminance moments and the
  * variance-guided filter (PT_OPT_MOMENTS, pt_moments_device_ptr,
  * pt_read_moments, pt_denoise_var_params, pt_denoise_var_default_params,
- * pt_denoise_var, pt_denoise_var_host). */
+ * pt_denoise_var, pt_denoise_var_host); the exit skip (PT_OPT_EXIT_SKIP). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -670,6 +670,17 @@ int pt_dist_finalize(pt_context* ctx);
  * = on; 0 = every sample of a live pixel is traced.  Needs
  * PT_OPT_PRIMARY_CULL; stats mode never skips.  Output is identical. */
 #define PT_OPT_CULL_TIGHT 25
+/* PT_OPT_EXIT_SKIP: 1 (default) = after a hit whose stored normal is
+ * axis-pure (two components +-0, the third of magnitude 0.999 to 2) at a point
+ * that lies, offset along the normal, beyond the root box's face on that side,
+ * the fast kernels end the path instead of sampling and tracing its bounce
+ * ray: the ray's component on that axis has the normal's sign for every
+ * hemisphere draw below 1, so the reference's root-box test fails and the
+ * path adds (0,0,0) (box.obj's outward faces).  In force
+ * only when some triangle of the scene has such a normal and every light's
+ * intensity is finite; stats mode never skips.  Output is identical;
+ * PT_OPT_COUNT_TRACED counts the walks not started. */
+#define PT_OPT_EXIT_SKIP 28
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
