@@ -417,6 +417,26 @@ struct pt_context {
   uint32_t moments_n = 0;
   float* d_var[2] = {nullptr, nullptr};
   size_t var_cap[2] = {0, 0};
+  // the seed base (PT_OPT_SEED_BASE) and temporal accumulation (pt_temporal_advance)
+  uint32_t opt_seed_base = 0;
+  uint32_t seed_extra = 0;             // inside pt_temporal_advance: the samples rendered since the last reset
+  struct TemporalSet {                 // one of the two library-owned result sets
+    float4* color = nullptr;
+    float2* moments = nullptr;
+    float* length = nullptr;
+    float* variance = nullptr;
+    size_t cap = 0;                    // pixels each image holds
+  } tset[2];
+  int t_cur = 0;                       // the set the last pt_temporal_advance wrote
+  uint32_t t_frames = 0, t_samples = 0;   // since the last reset; t_frames 0: no history
+  float t_cam[16] = {0};               // the last frame's camera
+  int t_w = 0, t_h = 0;                // ... and size
+  // the last frame's guide: d_guide while no later pt_render_guide has run (guide_serial ==
+  // t_guide_serial), else d_guide_prev, where that pt_render_guide put it aside
+  float4* d_guide_prev = nullptr;
+  size_t guide_prev_cap = 0;
+  unsigned long long guide_serial = 0, t_guide_serial = 0;
+  bool t_guide_aside = false;
   DistState* dist = nullptr;           // pt_dist_init
   pt_group* group = nullptr;           // pt_create_multi: every call goes to the group (pt_group.cpp)
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -428,6 +448,14 @@ struct pt_scene {
   std::vector<pt::BVHNode> nodes;
   uint32_t flags = 0;
 };
+
+// The temporal history is forgotten (pt_temporal_reset; a new scene, lights, params, frame size or
+// bound buffer): the next pt_temporal_advance runs without history and seeds from the seed base again.
+static void temporal_forget(pt_context* c) {
+  c->t_frames = 0;
+  c->t_samples = 0;
+  c->t_guide_aside = false;
+}
 
 // Before a launch that writes context-owned buffers: wait for the previous
 // such launch if it ran on another stream.
@@ -1109,6 +1137,7 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   p.height = c->height;
   p.first_batch = first_batch;
   p.n_batches = n_batches;
+  p.seed_base = c->opt_seed_base + c->seed_extra;   // PT_OPT_SEED_BASE (mod 2^32)
   p.max_depth = c->params.max_depth;
   p.sss_bounces = c->params.sss_bounces;
   // the exit skip (PT_OPT_EXIT_SKIP): only where it can fire and rad is finite
@@ -1530,6 +1559,13 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_moments);
   dev_free(c->d_var[0]);
   dev_free(c->d_var[1]);
+  dev_free(c->d_guide_prev);
+  for (auto& s : c->tset) {
+    dev_free(s.color);
+    dev_free(s.moments);
+    dev_free(s.length);
+    dev_free(s.variance);
+  }
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1634,6 +1670,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->n_wide = 0;
   c->has_scene = false;
   c->guide_valid = false;
+  temporal_forget(c);
   const int T = (int)(n_indices / 3);
   struct Staging {   // vertex/index copies live only until the triangle records are built
     float* v = nullptr;
@@ -1716,6 +1753,7 @@ int pt_upload_lights(pt_context* c, const pt_area_light* lights, size_t n) {
   dev_free(c->d_lights_dev);
   c->n_lights = 0;
   c->lights_host.clear();
+  temporal_forget(c);
   if (n) {
     PT_HIP(hipMalloc((void**)&c->d_lights, n * sizeof(ptd::LightRec)));
     PT_HIP(hipMalloc((void**)&c->d_lights_dev, n * sizeof(ptd::LightDev)));
@@ -1744,6 +1782,7 @@ int pt_set_params(pt_context* c, const pt_params* p) {
   if (p->max_depth < 0 || p->max_depth > 64 || p->sss_bounces < 0 || p->sss_bounces > 64)
     return fail(PT_ERR_INVALID, "max_depth and sss_bounces must be in [0,64]");
   c->params = *p;
+  temporal_forget(c);
   return PT_OK;
 }
 
@@ -1819,6 +1858,7 @@ int pt_resize_and_clear(pt_context* c, int w, int h) {
     if (c->own_accum) dev_free(c->d_accum);
     c->d_accum = nullptr;
     c->own_accum = false;
+    temporal_forget(c);   // another size or another buffer
     PT_HIP(hipMalloc((void**)&c->d_accum, (size_t)w * h * sizeof(float4)));
     c->own_accum = true;
     c->width = w;
@@ -1835,6 +1875,7 @@ int pt_bind_accum(pt_context* c, void* ptr, int w, int h) {
   PT_HIP(hipSetDevice(c->device));
   { const int rc_ = quiesce(c); if (rc_) return rc_; }
   if (c->own_accum) dev_free(c->d_accum);
+  if (c->d_accum != (float4*)ptr || c->own_accum || c->width != w || c->height != h) temporal_forget(c);
   c->d_accum = (float4*)ptr;
   c->own_accum = false;
   if (c->width != w || c->height != h) c->guide_valid = false;
@@ -2080,11 +2121,19 @@ int pt_render_guide(pt_context* c) {
     const int rw = wide_params(c, &p);
     if (rw) return rw;
   }
+  // the temporal history's guide is put aside before the image is written again (stream order keeps
+  // whatever still reads it correct: only the pointers move)
+  if (c->t_frames > 0 && !c->t_guide_aside && c->guide_serial == c->t_guide_serial) {
+    std::swap(c->d_guide, c->d_guide_prev);
+    std::swap(c->guide_cap, c->guide_prev_cap);
+    c->t_guide_aside = true;
+  }
   const int rg = grow_image(c, &c->d_guide, &c->guide_cap, (size_t)c->width * c->height);
   if (rg) return rg;
   const int ro = order_shared(c);
   if (ro) return ro;
   PT_HIP(ptd::launch_guide(p, c->d_guide, lds, c->stream));
+  c->guide_serial++;
   c->guide_valid = true;
   return mark_shared(c);
 }
@@ -2224,15 +2273,24 @@ int pt_denoise_var_host(const float* rgba, const float* moments, uint32_t n_samp
   if (!rgba || !moments || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
   if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
   if (n_samples < 2) return fail(PT_ERR_INVALID, "pt_denoise_var: the variance of the mean needs at least 2 samples");
+  const size_t n = (size_t)w * (size_t)h;
+  std::vector<float> va(n);
+  for (size_t i = 0; i < n; ++i) va[i] = ptdn::var_of_mean(moments[2 * i], moments[2 * i + 1], n_samples);
+  return pt_denoise_var_plane_host(rgba, va.data(), guide, w, h, params, out);
+}
+
+int pt_denoise_var_plane_host(const float* rgba, const float* variance, const float* guide, int w, int h,
+                              const pt_denoise_var_params* params, float* out) {
+  if (!rgba || !variance || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
   pt_denoise_var_params p;
   const int rp = denoise_var_params(params, &p);
   if (rp) return rp;
   const size_t n = (size_t)w * (size_t)h;
   std::vector<float4> g(n), a(n), b(n);
-  std::vector<float> va(n), vb(n);
+  std::vector<float> va(variance, variance + n), vb(n);
   memcpy(g.data(), guide, n * sizeof(float4));
   memcpy(a.data(), rgba, n * sizeof(float4));
-  for (size_t i = 0; i < n; ++i) va[i] = ptdn::var_of_mean(moments[2 * i], moments[2 * i + 1], n_samples);
   const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
   for (int i = 0; i < p.iterations; ++i) {
     const ptdn::VarImageFetch fetch = {a.data(), g.data(), va.data(), w};
@@ -2248,6 +2306,9 @@ int pt_denoise_var_host(const float* rgba, const float* moments, uint32_t n_samp
   memcpy(out, a.data(), n * sizeof(float4));
   return PT_OK;
 }
+
+static int var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,
+                      const float4* guide, float4* dst);
 
 int pt_denoise_var(pt_context* c, const pt_denoise_var_params* params, void* dst) {
   if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_var: not on a multi-device context (pt_create_multi)");
@@ -2267,6 +2328,14 @@ int pt_denoise_var(pt_context* c, const pt_denoise_var_params* params, void* dst
     const int rg = pt_render_guide(c);
     if (rg) return rg;
   }
+  return var_filter(c, p, c->d_accum, nullptr, c->d_guide, (float4*)dst);
+}
+
+// The variance-guided filter's passes of the context's frame: from colour src, the guide and either the
+// variance plane var0 (only read) or, var0 null, the variance of the mean of the context's moments.
+// dst null: the library-owned image pt_read_denoised reads.
+static int var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,
+                      const float4* guide, float4* dst) {
   const int w = c->width, h = c->height;
   const size_t n = (size_t)w * h;
   for (int k = 0; k < 2 && k < p.iterations - 1; ++k) {
@@ -2290,13 +2359,14 @@ int pt_denoise_var(pt_context* c, const pt_denoise_var_params* params, void* dst
   }
   const int ro = order_shared(c);
   if (ro) return ro;
-  PT_HIP(ptd::launch_moments_var(c->d_moments, c->d_var[0], w, h, c->moments_n, c->stream));
+  if (!var0) PT_HIP(ptd::launch_moments_var(c->d_moments, c->d_var[0], w, h, c->moments_n, c->stream));
   const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
-  const float4* cur = c->d_accum;
+  const float4* cur = src;
   for (int i = 0; i < p.iterations; ++i) {
     float4* to = i == p.iterations - 1 ? out : c->d_dn_scratch[i & 1];
-    PT_HIP(ptd::launch_atrous_var(cur, c->d_var[i & 1], c->d_guide, to, c->d_var[(i + 1) & 1], w, h, 1 << i, p.sigma_lum,
-                                  sn2, sz2, c->opt_denoise_lds != 0 && i < 2, c->stream));
+    const float* vsrc = i == 0 && var0 ? var0 : c->d_var[i & 1];
+    PT_HIP(ptd::launch_atrous_var(cur, vsrc, guide, to, c->d_var[(i + 1) & 1], w, h, 1 << i, p.sigma_lum, sn2, sz2,
+                                  c->opt_denoise_lds != 0 && i < 2, c->stream));
     cur = to;
   }
   if (!dst) {
@@ -2304,6 +2374,261 @@ int pt_denoise_var(pt_context* c, const pt_denoise_var_params* params, void* dst
     c->denoised_h = h;
   }
   return mark_shared(c);
+}
+
+// ---- temporal reprojection (pt_denoise.h reproject_pixel) --------------------
+int pt_temporal_default_params(pt_temporal_params* out) {
+  if (!out) return fail(PT_ERR_INVALID, "null argument");
+  out->max_history = 64;
+  out->alpha_min = 0.0f;
+  out->normal_min = 0.5f;
+  out->depth_rel = 0.05f;
+  return PT_OK;
+}
+
+static int temporal_params(const pt_temporal_params* in, pt_temporal_params* p) {
+  if (in)
+    *p = *in;
+  else
+    (void)pt_temporal_default_params(p);
+  if (!ptdn::temporal_params_ok(p->max_history, p->alpha_min, p->normal_min, p->depth_rel))
+    return fail(PT_ERR_INVALID,
+                "pt_temporal_params: max_history 1-65536, alpha_min in [0, 1], normal_min in [-1, 1], depth_rel finite and > 0");
+  return PT_OK;
+}
+
+// The checks pt_reproject and pt_reproject_host share: sizes, the sample count, the images' presence (the
+// history all there or all null) and that no output is an input or another output.
+static int reproject_args(const float* cam_cur, const float* cam_prev, int w, int h, uint32_t n,
+                          const pt_reproject_images* im) {
+  if (!cam_cur || !cam_prev || !im) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0 || (long long)w * h > (1ll << 31)) return fail(PT_ERR_INVALID, "bad resolution");
+  if (n < 1 || n > 65536) return fail(PT_ERR_INVALID, "pt_reproject: n takes 1 to 65536 samples");
+  if (!im->color || !im->moments || !im->guide || !im->out_color || !im->out_moments || !im->out_length ||
+      !im->out_variance)
+    return fail(PT_ERR_INVALID, "pt_reproject: null image");
+  const int nh = (im->hist_color ? 1 : 0) + (im->hist_moments ? 1 : 0) + (im->hist_length ? 1 : 0) + (im->hist_guide ? 1 : 0);
+  if (nh != 0 && nh != 4) return fail(PT_ERR_INVALID, "pt_reproject: the four history images are all given or all null");
+  const void* in[7] = {im->color, im->moments, im->guide, im->hist_color, im->hist_moments, im->hist_length, im->hist_guide};
+  const void* out[4] = {im->out_color, im->out_moments, im->out_length, im->out_variance};
+  for (int i = 0; i < 4; ++i) {
+    for (int k = 0; k < 7; ++k)
+      if (out[i] == in[k]) return fail(PT_ERR_INVALID, "pt_reproject: an output image is also an input");
+    for (int k = 0; k < i; ++k)
+      if (out[i] == out[k]) return fail(PT_ERR_INVALID, "pt_reproject: two output images are the same");
+  }
+  return PT_OK;
+}
+
+int pt_reproject_host(const float cam_cur[16], const float cam_prev[16], int w, int h, uint32_t n,
+                      const pt_reproject_images* im, const pt_temporal_params* params) {
+  const int ra = reproject_args(cam_cur, cam_prev, w, h, n, im);
+  if (ra) return ra;
+  pt_temporal_params p;
+  const int rp = temporal_params(params, &p);
+  if (rp) return rp;
+  const size_t np = (size_t)w * (size_t)h;
+  std::vector<float4> hc, hg;
+  std::vector<float2> hm;
+  ptdn::HistImages hist = {nullptr, nullptr, nullptr, nullptr};
+  if (im->hist_color) {
+    hc.resize(np);
+    hg.resize(np);
+    hm.resize(np);
+    memcpy(hc.data(), im->hist_color, np * sizeof(float4));
+    memcpy(hg.data(), im->hist_guide, np * sizeof(float4));
+    memcpy(hm.data(), im->hist_moments, np * sizeof(float2));
+    hist = {hc.data(), hm.data(), im->hist_length, hg.data()};
+  }
+  const ptdn::CamBasis B = ptdn::cam_basis(cam_cur), Bp = ptdn::cam_basis(cam_prev);
+  const ptdn::TemporalParams tp = {(float)p.max_history, p.alpha_min, p.normal_min, p.depth_rel};
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) {
+      const size_t i = (size_t)y * w + x;
+      float4 c, g;
+      float2 m;
+      memcpy(&c, im->color + 4 * i, sizeof c);
+      memcpy(&g, im->guide + 4 * i, sizeof g);
+      memcpy(&m, im->moments + 2 * i, sizeof m);
+      const ptdn::ReprojOut o = ptdn::reproject_pixel(hist, B, Bp, w, h, x, y, c, m, g, (float)n, tp);
+      memcpy(im->out_color + 4 * i, &o.c, sizeof o.c);
+      memcpy(im->out_moments + 2 * i, &o.m, sizeof o.m);
+      im->out_length[i] = o.len;
+      im->out_variance[i] = o.var;
+    }
+  return PT_OK;
+}
+
+int pt_reproject(pt_context* c, const float cam_cur[16], const float cam_prev[16], int w, int h, uint32_t n,
+                 const pt_reproject_images* im, const pt_temporal_params* params) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_reproject: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  const int ra = reproject_args(cam_cur, cam_prev, w, h, n, im);
+  if (ra) return ra;
+  pt_temporal_params p;
+  const int rp = temporal_params(params, &p);
+  if (rp) return rp;
+  const uintptr_t a16 = (uintptr_t)im->color | (uintptr_t)im->guide | (uintptr_t)im->hist_color |
+                        (uintptr_t)im->hist_guide | (uintptr_t)im->out_color;
+  const uintptr_t a8 = (uintptr_t)im->moments | (uintptr_t)im->hist_moments | (uintptr_t)im->out_moments;
+  const uintptr_t a4 = (uintptr_t)im->hist_length | (uintptr_t)im->out_length | (uintptr_t)im->out_variance;
+  if ((a16 & 15) || (a8 & 7) || (a4 & 3))
+    return fail(PT_ERR_INVALID, "pt_reproject: colours and guides must be 16-B aligned, moments 8-B, lengths and variance 4-B");
+  PT_HIP(hipSetDevice(c->device));
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(ptd::launch_reproject((const float4*)im->color, (const float2*)im->moments, (const float4*)im->guide,
+                               (const float4*)im->hist_color, (const float2*)im->hist_moments, im->hist_length,
+                               (const float4*)im->hist_guide, (float4*)im->out_color, (float2*)im->out_moments,
+                               im->out_length, im->out_variance, cam_cur, cam_prev, w, h, n, p.max_history, p.alpha_min,
+                               p.normal_min, p.depth_rel, c->stream));
+  if ((float4*)im->out_color == c->d_accum) {   // the accumulation buffer given as a destination
+    c->culled_state = 0;
+    c->moments_valid = false;
+  }
+  return mark_shared(c);
+}
+
+// One image set of at least n pixels.
+static int grow_tset(pt_context* c, pt_context::TemporalSet* s, size_t n) {
+  if (s->color && s->cap >= n) return PT_OK;
+  { const int rc_ = quiesce(c); if (rc_) return rc_; }
+  dev_free(s->color);
+  dev_free(s->moments);
+  dev_free(s->length);
+  dev_free(s->variance);
+  s->cap = 0;
+  PT_HIP(hipMalloc((void**)&s->color, n * sizeof(float4)));
+  PT_HIP(hipMalloc((void**)&s->moments, n * sizeof(float2)));
+  PT_HIP(hipMalloc((void**)&s->length, n * sizeof(float)));
+  PT_HIP(hipMalloc((void**)&s->variance, n * sizeof(float)));
+  s->cap = n;
+  return PT_OK;
+}
+
+static const char* temporal_unsupported(const pt_context* c) {
+  if (c->nranks > 1) return "not on a partition of more than one rank";
+  if (c->stats_mode) return "not in stats mode";
+  if (c->opt_count) return "not with PT_OPT_COUNT_TRACED";
+  return nullptr;
+}
+
+int pt_temporal_advance(pt_context* c, const float ubo[16], uint32_t n_batches) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_advance: not on a multi-device context (pt_create_multi)");
+  if (!c || !ubo) return fail(PT_ERR_INVALID, "null argument");
+  if (const char* why = temporal_unsupported(c)) return fail(PT_ERR_UNSUPPORTED, std::string("pt_temporal_advance: ") + why);
+  if (n_batches < 1 || n_batches > 65536) return fail(PT_ERR_INVALID, "pt_temporal_advance: n_batches takes 1 to 65536");
+  if (!c->opt_moments) return fail(PT_ERR_INVALID, "pt_temporal_advance: needs PT_OPT_MOMENTS 1");
+  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
+  if (c->n_lights < 1) return fail(PT_ERR_INVALID, "no lights uploaded");
+  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
+  PT_HIP(hipSetDevice(c->device));
+  const int w = c->width, h = c->height;
+  const size_t n = (size_t)w * h;
+  const bool have = c->t_frames > 0 && c->t_w == w && c->t_h == h;
+  if (!have) temporal_forget(c);
+  const int dst = have ? 1 - c->t_cur : 0;
+  {
+    const int rs = grow_tset(c, &c->tset[dst], n);
+    if (rs) return rs;
+  }
+  int rc = pt_set_camera(c, ubo);
+  if (rc) return rc;
+  rc = pt_clear_accum(c);
+  if (rc) return rc;
+  c->seed_extra = c->t_samples;
+  rc = render_impl(c, 0, n_batches, nullptr);
+  c->seed_extra = 0;
+  if (rc) return rc;
+  rc = pt_render_guide(c);   // puts the last frame's guide aside first
+  if (rc) return rc;
+  const pt_context::TemporalSet& src = c->tset[c->t_cur];
+  const pt_context::TemporalSet& out = c->tset[dst];
+  const float4* hist_guide = c->t_guide_aside ? c->d_guide_prev : nullptr;
+  const bool hist = have && hist_guide;
+  pt_temporal_params p;
+  (void)pt_temporal_default_params(&p);
+  rc = order_shared(c);
+  if (rc) return rc;
+  PT_HIP(ptd::launch_reproject(c->d_accum, c->d_moments, c->d_guide, hist ? src.color : nullptr,
+                               hist ? src.moments : nullptr, hist ? src.length : nullptr, hist ? hist_guide : nullptr,
+                               out.color, out.moments, out.length, out.variance, ubo, c->t_cam, w, h, n_batches,
+                               p.max_history, p.alpha_min, p.normal_min, p.depth_rel, c->stream));
+  c->t_cur = dst;
+  c->t_frames++;
+  c->t_samples += n_batches;
+  memcpy(c->t_cam, ubo, sizeof c->t_cam);
+  c->t_w = w;
+  c->t_h = h;
+  c->t_guide_serial = c->guide_serial;
+  c->t_guide_aside = false;
+  return mark_shared(c);
+}
+
+int pt_temporal_reset(pt_context* c) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_reset: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  temporal_forget(c);
+  return PT_OK;
+}
+
+int pt_temporal_info(pt_context* c, uint32_t* frames, uint32_t* samples) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_info: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  if (frames) *frames = c->t_frames;
+  if (samples) *samples = c->t_samples;
+  return PT_OK;
+}
+
+// Whether the context holds a temporal result of the current frame size.
+static bool temporal_ready(const pt_context* c) {
+  return c->t_frames > 0 && c->t_w == c->width && c->t_h == c->height && c->tset[c->t_cur].color;
+}
+
+void* pt_temporal_device_ptr(pt_context* c, int which) {
+  if (!c || c->group || !temporal_ready(c)) return nullptr;
+  const pt_context::TemporalSet& s = c->tset[c->t_cur];
+  return which == 0 ? (void*)s.color : which == 1 ? (void*)s.moments : which == 2 ? (void*)s.length
+         : which == 3 ? (void*)s.variance : nullptr;
+}
+
+int pt_read_temporal(pt_context* c, float* rgba, float* moments, float* length) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_temporal: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  if (!temporal_ready(c)) return fail(PT_ERR_INVALID, "no temporal result for the current frame (pt_temporal_advance)");
+  PT_HIP(hipSetDevice(c->device));
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  const pt_context::TemporalSet& s = c->tset[c->t_cur];
+  const size_t n = (size_t)c->t_w * c->t_h;
+  if (rgba) PT_HIP(hipMemcpyAsync(rgba, s.color, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (moments) PT_HIP(hipMemcpyAsync(moments, s.moments, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  if (length) PT_HIP(hipMemcpyAsync(length, s.length, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+int pt_temporal_denoise(pt_context* c, const pt_denoise_var_params* params, void* dst) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_denoise: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  pt_denoise_var_params p;
+  const int rp = denoise_var_params(params, &p);
+  if (rp) return rp;
+  if (!temporal_ready(c)) return fail(PT_ERR_INVALID, "no temporal result for the current frame (pt_temporal_advance)");
+  if (((uintptr_t)dst) & 15) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
+  const pt_context::TemporalSet& s = c->tset[c->t_cur];
+  if (dst && (float4*)dst == s.color) return fail(PT_ERR_INVALID, "pt_temporal_denoise: source and destination must differ");
+  // the frame's guide: still d_guide, or where a later pt_render_guide put it aside
+  const float4* guide = c->t_guide_aside ? c->d_guide_prev : c->guide_serial == c->t_guide_serial ? c->d_guide : nullptr;
+  if (!guide) return fail(PT_ERR_INVALID, "pt_temporal_denoise: the temporal frame's guide is gone");
+  PT_HIP(hipSetDevice(c->device));
+  const int rf = var_filter(c, p, s.color, s.variance, guide, (float4*)dst);
+  if (rf) return rf;
+  if ((float4*)dst == c->d_accum) {   // the accumulation buffer given as the destination
+    c->culled_state = 0;
+    c->moments_valid = false;
+  }
+  return PT_OK;
 }
 
 int pt_last_kernel(pt_context* c, int* kernel) {
@@ -2425,6 +2750,10 @@ int pt_set_option(pt_context* c, int key, int value) {
       if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_MOMENTS takes 0 or 1");
       if (value != c->opt_moments) c->moments_valid = false;
       c->opt_moments = value;
+      return PT_OK;
+    case PT_OPT_SEED_BASE:
+      if (value < 0) return fail(PT_ERR_INVALID, "PT_OPT_SEED_BASE takes 0 to 2^31-1");
+      c->opt_seed_base = (uint32_t)value;
       return PT_OK;
     case PT_OPT_GROUP_EXCHANGE:
     case PT_OPT_GROUP_CHECK:

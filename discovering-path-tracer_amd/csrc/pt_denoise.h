@@ -22,7 +22,8 @@
 //
 // Further down: the luminance of the moments the render kernels fold
 // (PT_OPT_MOMENTS) and the variance-guided filter built on them
-// (atrous_var_pixel: pt_denoise_var, pt_denoise_var_host), stated the same way.
+// (atrous_var_pixel: pt_denoise_var, pt_denoise_var_host), stated the same way,
+// and temporal reprojection (reproject_pixel: pt_reproject, pt_reproject_host).
 #pragma once
 #include "pt_math.h"
 
@@ -247,5 +248,128 @@ struct VarImageFetch {
   }
   __host__ __device__ inline float var(int qx, int qy) const { return variance[(size_t)qy * (size_t)W + (size_t)qx]; }
 };
+
+// ---- temporal reprojection (pt_reproject, pt_temporal_advance) --------------
+// SVGF's first stage: the new frame c (n samples, moments m, guide g = {n.xyz, t}
+// from camera B) is blended with the history (colour hc, moments hm, length hl
+// in samples, guide hg, all from camera Bp) found where the pixel's first hit
+// projects into the previous frame.  Per pixel p = (x, y):
+//   no history (out = c, out_m = m, out_len = float(n)) if any "else none" applies
+//   t = g_p.w;  if !(t < 1e30f) none                                   (a miss)
+//   P = add(B.pos, muls(guide_dir(B.dir, B.right, B.up, B.tan_fov, W, H, x, y), t))
+//   v = sub(P, Bp.pos);  z = dot(v, Bp.dir);  if !(z > 0) none
+//   aspect = float(W) / float(H)
+//   sx = dot(v, neg(Bp.right)) / (z * (Bp.tan_fov * aspect));   sy = dot(v, neg(Bp.up)) / (z * Bp.tan_fov)
+//   fx = ((sx + 1) * float(W)) * 0.5f;   fy = ((sy + 1) * float(H)) * 0.5f
+//   if !(fx > -1 && fx < float(W) && fy > -1 && fy < float(H)) none     (also NaN)
+//   x0f = floor_(fx), ax = fx - x0f, x0 = int(x0f);  y likewise;  dexp = length(v)
+//   taps q = (x0 + tx, y0 + ty), ty = 0..1 outer, tx = 0..1 inner, outside the frame skipped:
+//     b = (tx ? ax : 1 - ax) * (ty ? ay : 1 - ay)
+//     valid iff hl_q > 0 && hg_q.w < 1e30f && fabs_(hg_q.w - dexp) <= depth_rel * dexp
+//               && dot(g_p.xyz, hg_q.xyz) >= normal_min
+//     valid: sw += b;  sc.rgb += b * hc_q.rgb;  sm += b * hm_q;  lmin = fmin_(lmin, hl_q)
+//   if !(sw > 0) none
+//   h = sc / sw;  h_m = sm / sw;  N = fmin_(lmin, float(max_history))
+//   a = fmax_(alpha_min, float(n) / (N + float(n)))
+//   out.rgb = h + (c.rgb - h) * a;  out.a = c.a;  out_m = h_m + (m - h_m) * a;  out_len = N + float(n)
+//   always   out_var = fmax_(0, out_m.y - out_m.x * out_m.x) / fmax_(out_len - 1, 1)
+// t is a distance along a unit ray, so dexp is the distance the previous guide
+// should hold at that point; the guide ray passes through integer pixel
+// coordinates (ndc = 2x/W - 1), hence no half-pixel offset.  lmin starts at
+// +inf.  n and max_history are at most 65536: every length is an exact float.
+struct TemporalParams {
+  float max_history;   // float(max_history)
+  float alpha_min, normal_min, depth_rel;
+};
+PT_FN bool temporal_params_ok(uint32_t max_history, float alpha_min, float normal_min, float depth_rel) {
+  return max_history >= 1u && max_history <= 65536u && alpha_min >= 0.0f && alpha_min <= 1.0f && normal_min >= -1.0f &&
+         normal_min <= 1.0f && depth_rel > 0.0f && depth_rel <= 3.40282347e38f;
+}
+
+// The history images; color null: no history.
+struct HistImages {
+  const float4* color;
+  const float2* moments;
+  const float* length;
+  const float4* guide;
+};
+
+struct ReprojOut {
+  float4 c;
+  float2 m;
+  float len, var;
+};
+
+PT_FN ReprojOut reproject_pixel(const HistImages& hist, const CamBasis& B, const CamBasis& Bp, int W, int H, int x,
+                                int y, float4 c, float2 m, float4 g, float fn, TemporalParams tp) {
+  ReprojOut o;
+  o.c = c;
+  o.m = m;
+  o.len = fn;
+  bool found = false;
+  float3 sc = {0.0f, 0.0f, 0.0f};
+  float2 sm = {0.0f, 0.0f};
+  float sw = 0.0f, lmin = u2f(0x7f800000u);
+  const float t = g.w;
+  if (hist.color && t < 1e30f) {
+    const v3 P = add(B.pos, muls(guide_dir(B.dir, B.right, B.up, B.tan_fov, W, H, x, y), t));
+    const v3 v = sub(P, Bp.pos);
+    const float z = dot(v, Bp.dir);
+    if (z > 0.0f) {
+      const float aspect = (float)W / (float)H;
+      const float sx = dot(v, neg(Bp.right)) / (z * (Bp.tan_fov * aspect));
+      const float sy = dot(v, neg(Bp.up)) / (z * Bp.tan_fov);
+      const float fx = ((sx + 1.0f) * (float)W) * 0.5f;
+      const float fy = ((sy + 1.0f) * (float)H) * 0.5f;
+      if (fx > -1.0f && fx < (float)W && fy > -1.0f && fy < (float)H) {
+        const float x0f = floor_(fx), y0f = floor_(fy);
+        const float ax = fx - x0f, ay = fy - y0f;
+        const int x0 = (int)x0f, y0 = (int)y0f;
+        const float dexp = length(v);
+        const float dtol = tp.depth_rel * dexp;
+        const v3 np = mk(g.x, g.y, g.z);
+        for (int ty = 0; ty < 2; ++ty) {
+          const int qy = y0 + ty;
+          if (qy < 0 || qy >= H) continue;
+          const float by = ty ? ay : 1.0f - ay;
+          for (int tx = 0; tx < 2; ++tx) {
+            const int qx = x0 + tx;
+            if (qx < 0 || qx >= W) continue;
+            const float b = (tx ? ax : 1.0f - ax) * by;
+            const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
+            const float hl = hist.length[q];
+            const float4 hg = hist.guide[q];
+            if (hl > 0.0f && hg.w < 1e30f && fabs_(hg.w - dexp) <= dtol && dot(np, mk(hg.x, hg.y, hg.z)) >= tp.normal_min) {
+              const float4 hc = hist.color[q];
+              const float2 hm = hist.moments[q];
+              sw += b;
+              sc.x += b * hc.x;
+              sc.y += b * hc.y;
+              sc.z += b * hc.z;
+              sm.x += b * hm.x;
+              sm.y += b * hm.y;
+              lmin = fmin_(lmin, hl);
+            }
+          }
+        }
+        found = sw > 0.0f;
+      }
+    }
+  }
+  if (found) {
+    const float hx = sc.x / sw, hy = sc.y / sw, hz = sc.z / sw;
+    const float hm1 = sm.x / sw, hm2 = sm.y / sw;
+    const float N = fmin_(lmin, tp.max_history);
+    const float a = fmax_(tp.alpha_min, fn / (N + fn));
+    o.c.x = hx + (c.x - hx) * a;
+    o.c.y = hy + (c.y - hy) * a;
+    o.c.z = hz + (c.z - hz) * a;
+    o.m.x = hm1 + (m.x - hm1) * a;
+    o.m.y = hm2 + (m.y - hm2) * a;
+    o.len = N + fn;
+  }
+  o.var = fmax_(0.0f, o.m.y - o.m.x * o.m.x) / fmax_(o.len - 1.0f, 1.0f);
+  return o;
+}
 
 }  // namespace ptdn

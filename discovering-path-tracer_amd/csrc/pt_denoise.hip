@@ -1,6 +1,7 @@
 // pt_denoise.hip — the edge-avoiding a-trous filter's pass kernels
-// (pt_denoise) and those of the variance-guided filter (pt_denoise_var, below);
-// the filters' statements are pt_denoise.h, shared with the host.
+// (pt_denoise), those of the variance-guided filter (pt_denoise_var, below) and
+// the temporal reprojection kernel (pt_reproject, last); the statements are
+// pt_denoise.h, shared with the host.
 //
 // One pixel per lane, 16x16 pixels per workgroup, a wave a 16x4 strip: the
 // lanes of a tile row read 256 consecutive bytes of each image per tap.
@@ -135,7 +136,50 @@ __global__ __launch_bounds__(256) void atrous_var_staged_kernel(const float4* __
   vdst[i] = o.v;
 }
 
+// ---- temporal reprojection (pt_reproject, pt_denoise.h reproject_pixel) ------
+// The same shape once more: a tile row's lanes read and write consecutive 16-B
+// (colour, guide), 8-B (moments) and 4-B (length, variance) words of the
+// streamed images.  The four history taps are a gather whose addresses are
+// nearly coherent -- neighbouring pixels land on neighbouring history pixels --
+// so it is left to the caches; a tap reads its length and guide first and its
+// colour and moments only when it is valid.  No LDS.  The camera bases are
+// formed on the host (cam_basis) and arrive as kernel arguments.
+__global__ __launch_bounds__(256) void reproject_kernel(const float4* __restrict__ color,
+                                                        const float2* __restrict__ moments,
+                                                        const float4* __restrict__ guide, HistImages hist,
+                                                        float4* __restrict__ out_color,
+                                                        float2* __restrict__ out_moments,
+                                                        float* __restrict__ out_length,
+                                                        float* __restrict__ out_variance, CamBasis B, CamBasis Bp,
+                                                        int W, int H, float fn, TemporalParams tp) {
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const size_t i = (size_t)y * (size_t)W + (size_t)x;
+  const ReprojOut o = reproject_pixel(hist, B, Bp, W, H, x, y, color[i], moments[i], guide[i], fn, tp);
+  out_color[i] = o.c;
+  out_moments[i] = o.m;
+  out_length[i] = o.len;
+  out_variance[i] = o.var;
+}
+
 }  // namespace
+
+hipError_t launch_reproject(const float4* color, const float2* moments, const float4* guide, const float4* hist_color,
+                            const float2* hist_moments, const float* hist_length, const float4* hist_guide,
+                            float4* out_color, float2* out_moments, float* out_length, float* out_variance,
+                            const float cam_cur[16], const float cam_prev[16], int width, int height, uint32_t n,
+                            uint32_t max_history, float alpha_min, float normal_min, float depth_rel,
+                            hipStream_t stream) {
+  if (width <= 0 || height <= 0 || n < 1) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+  const HistImages hist = {hist_color, hist_moments, hist_length, hist_guide};
+  const TemporalParams tp = {(float)max_history, alpha_min, normal_min, depth_rel};
+  reproject_kernel<<<grid, 256, 0, stream>>>(color, moments, guide, hist, out_color, out_moments, out_length,
+                                             out_variance, cam_basis(cam_cur), cam_basis(cam_prev), width, height,
+                                             (float)n, tp);
+  return hipGetLastError();
+}
 
 hipError_t launch_moments_var(const float2* moments, float* var, int width, int height, uint32_t n_samples,
                               hipStream_t stream) {

@@ -176,6 +176,14 @@ struct RenderParams {
   // launch_wavefront), which read nothing past `moments`
   int exit_skip = 0;
   float root_lo[3] = {}, root_hi[3] = {};
+  // the seed base (PT_OPT_SEED_BASE): sample s of the launch draws from the seed ((first_batch + seed_base
+  // + s) * H + py) * W + px in uint32 arithmetic and still folds with weight first_batch + s.  0: the seeds
+  // of before.  Read at the seed sites only (render_kernel, the generation kernel's tight-cull draw,
+  // path_step's PH_BEGIN), as one scalar add to first_batch: of the ways tried (the product B * H * W added
+  // to the seed; first_batch + B formed on the host) the one that moved the kernels' code least
+  // (profiles/temporal/resource_usage.md).  It sits in the struct's tail padding: the kernel argument
+  // keeps its size
+  uint32_t seed_base = 0;
 };
 constexpr int kMixShift = 24;
 constexpr int kMaxCullRects = 8;
@@ -260,6 +268,15 @@ hipError_t launch_moments_var(const float2* moments, float* var, int width, int 
 hipError_t launch_atrous_var(const float4* src, const float* vsrc, const float4* guide, float4* dst, float* vdst,
                              int width, int height, int step, float sigma_lum, float sn2, float sz2, bool staged,
                              hipStream_t stream);
+// Temporal reprojection (pt_denoise.h reproject_pixel): the frame of n samples (color, moments, guide from
+// cam_cur) blended with the history images (from cam_prev; all four null: no history) into the four output
+// images, distinct from every input.
+hipError_t launch_reproject(const float4* color, const float2* moments, const float4* guide, const float4* hist_color,
+                            const float2* hist_moments, const float* hist_length, const float4* hist_guide,
+                            float4* out_color, float2* out_moments, float* out_length, float* out_variance,
+                            const float cam_cur[16], const float cam_prev[16], int width, int height, uint32_t n,
+                            uint32_t max_history, float alpha_min, float normal_min, float depth_rel,
+                            hipStream_t stream);
 // lanes of the wide walk's persistent grid on this device (overflow areas to allocate)
 long long wide_trace_lanes();
 // workgroups of the LDS-staged render kernel resident on this device at once

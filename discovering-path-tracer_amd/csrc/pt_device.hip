@@ -1057,8 +1057,8 @@ __global__ __launch_bounds__(256, SWEEP || (LDS && !STATS) ? 6 : PT_RENDER_MIN_B
      const uint32_t s = base + (uint32_t)j;
      float4 col4 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
      if (active && live && s < P.n_batches) {
-      const uint32_t batch = P.first_batch + s;
-      const uint32_t seed = (batch * (uint32_t)H + (uint32_t)py) * (uint32_t)W + (uint32_t)px;   // :435
+      const uint32_t batch = (P.first_batch + P.seed_base) + s;   // the seed's batch (PT_OPT_SEED_BASE); the fold's is below
+      const uint32_t seed = (batch * (uint32_t)H + (uint32_t)py) * (uint32_t)W + (uint32_t)px;
       uint32_t rng = seed;
       // randomGaussian x2 (:218-226, :445, :451): the four draws first, in
       // the shader's order; a wave none of whose lanes needs its path (no
@@ -1491,8 +1491,8 @@ __device__ bool path_step(const RenderParams& P, const CamFrame& F, PathSt& S, T
     bool finished = false;   // sample complete, `color` holds its radiance
     switch (S.phase) {
       case PH_BEGIN: {
-        const uint32_t batch = P.first_batch + S.s;
-        const uint32_t seed = (batch * (uint32_t)F.H + (uint32_t)F.py) * (uint32_t)F.W + (uint32_t)F.px;   // :435
+        const uint32_t batch = (P.first_batch + P.seed_base) + S.s;   // the seed's batch (PT_OPT_SEED_BASE)
+        const uint32_t seed = (batch * (uint32_t)F.H + (uint32_t)F.py) * (uint32_t)F.W + (uint32_t)F.px;
         v3 o, d;
         camera_ray(F, seed, &o, &d);
         S.rng = seed;                                                         // :307
@@ -1861,8 +1861,8 @@ __global__ __launch_bounds__(256) void wf_gen_kernel(RenderParams P, WfBuffers B
       // reaches nothing and is (0,0,0)
       bool reach = pixel_live(P, F.ndcX0, F.ndcY0);
       if (reach && !pixel_tight(P, F.ndcX0, F.ndcY0)) {
-        const uint32_t batch = P.first_batch + S.s;
-        uint32_t rng = (batch * (uint32_t)F.H + (uint32_t)F.py) * (uint32_t)F.W + (uint32_t)F.px;   // :435
+        const uint32_t batch = (P.first_batch + P.seed_base) + S.s;   // the seed's batch (PT_OPT_SEED_BASE)
+        uint32_t rng = (batch * (uint32_t)F.H + (uint32_t)F.py) * (uint32_t)F.W + (uint32_t)F.px;
         const float u1a = fmax_(1e-38f, rng_next(&rng));
         rng_next(&rng);
         const float u1j = fmax_(1e-38f, rng_next(&rng));

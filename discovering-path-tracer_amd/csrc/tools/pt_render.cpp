@@ -6,7 +6,7 @@
 //   pt_render scene.obj [-w 1920] [-h 1080] [-spp 8] [-depth 4] [-sss 3]
 //             [-fused] [-o out.pfm] [-png out.png] [-device 0 | -devices 0,1,..]
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
-//             [-denoise | -denoise-var] [-guide normals.pfm]
+//             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -22,6 +22,13 @@
 // before rendering and filters with the variance-guided filter
 // (pt_denoise_var, default parameters; at least 2 spp).  All three need a
 // single-device context.
+// -temporal K runs K frames of the temporal loop (pt_temporal_advance) at -spp
+// samples each instead of one render: camera k (k = 0 .. K-1) is the default
+// camera rotated k times about +y by the float32 step x' = x*c + z*s,
+// z' = z*c - x*s with c = 0.99939083f, s = 0.0348995f (2 degrees), applied to
+// the position and the direction.  -o / -png then hold the temporal colour,
+// or, with -denoise-var, pt_temporal_denoise's result at the default
+// parameters.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,7 +52,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr,
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
-            "       [-denoise | -denoise-var] [-guide normals.pfm] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
+            "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
             "       [-progressive N [-chunk K] [-orbit-at B]]\n",
             argv[0]);
     return 2;
@@ -54,7 +61,7 @@ int main(int argc, char** argv) {
   int W = 1024, H = 1024, spp = 8, device = 0;   // VulkanRayTracer.cpp:21-22
   pt_params params{4, 3};
   bool fused = false;
-  int progressive = 0, chunk = 8, orbit_at = -1;
+  int progressive = 0, chunk = 8, orbit_at = -1, temporal = 0;
   std::string cache_path, png_path, guide_path;
   bool denoise = false, denoise_var = false;
   std::vector<int> devices;   // -devices: a multi-device context
@@ -83,6 +90,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "-progressive")) progressive = atoi(next());
     else if (!strcmp(argv[i], "-chunk")) chunk = atoi(next());
     else if (!strcmp(argv[i], "-orbit-at")) orbit_at = atoi(next());
+    else if (!strcmp(argv[i], "-temporal")) temporal = atoi(next());
   }
   pt_scene* scene = nullptr;
   auto t0 = std::chrono::steady_clock::now();
@@ -109,7 +117,7 @@ int main(int argc, char** argv) {
     check(pt_group_info(ctx, nullptr, nullptr, 0, &peer), "group_info");
     printf("devices: %zu (%s)\n", devices.size(), peer ? "peer stores into the first device's frame" : "packed tile copies");
   }
-  if (denoise_var) check(pt_set_option(ctx, PT_OPT_MOMENTS, 1), "moments");
+  if (denoise_var || temporal > 0) check(pt_set_option(ctx, PT_OPT_MOMENTS, 1), "moments");
   check(pt_scene_upload(ctx, scene), "upload scene");
   const float pos[3] = {0.0f, 2.0f, 0.0f}, nrm[3] = {0.0f, -1.0f, 0.0f}, inten[3] = {10.0f, 10.0f, 10.0f},
               size[2] = {2.5f, 2.5f};   // VulkanRayTracer.cpp:149-162
@@ -163,6 +171,19 @@ int main(int argc, char** argv) {
   auto r0 = std::chrono::steady_clock::now();
   if (progressive > 0) {
     // the accumulation buffer already holds the progressive result
+  } else if (temporal > 0) {
+    float cam[16];
+    memcpy(cam, ubo, sizeof cam);
+    const float c2 = 0.99939083f, s2 = 0.0348995f;
+    for (int k = 0; k < temporal; ++k) {
+      if (k > 0)
+        for (int o = 0; o <= 4; o += 4) {   // the position, then the direction
+          const float x = cam[o], z = cam[o + 2];
+          cam[o] = x * c2 + z * s2;
+          cam[o + 2] = z * c2 - x * s2;
+        }
+      check(pt_temporal_advance(ctx, cam, (uint32_t)spp), "temporal advance");
+    }
   } else if (fused) {
     check(pt_render(ctx, 0, (uint32_t)spp), "render");
   } else {
@@ -170,11 +191,21 @@ int main(int argc, char** argv) {
   }
   check(pt_synchronize(ctx), "sync");
   auto r1 = std::chrono::steady_clock::now();
-  if (progressive == 0)
+  if (temporal > 0 && progressive == 0)
+    printf("temporal: %d frames of %dx%d x %d spp in %.3f ms\n", temporal, W, H, spp,
+           std::chrono::duration<double, std::milli>(r1 - r0).count());
+  else if (progressive == 0)
     printf("rendered %dx%d x %d spp in %.3f ms\n", W, H, spp, std::chrono::duration<double, std::milli>(r1 - r0).count());
   if (!out_path.empty() || !png_path.empty()) {
     std::vector<float> rgba((size_t)W * H * 4);
-    if (denoise_var) {
+    if (temporal > 0 && progressive == 0) {
+      if (denoise_var) {
+        check(pt_temporal_denoise(ctx, nullptr, nullptr), "temporal denoise");
+        check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+      } else {
+        check(pt_read_temporal(ctx, rgba.data(), nullptr, nullptr), "read temporal");
+      }
+    } else if (denoise_var) {
       check(pt_denoise_var(ctx, nullptr, nullptr), "denoise-var");
       check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
     } else if (denoise) {

@@ -45,6 +45,7 @@ PT_OPT_CULL_TIGHT = 25
 PT_OPT_SWEEP_HULL = 26
 PT_OPT_MOMENTS = 27
 PT_OPT_EXIT_SKIP = 28
+PT_OPT_SEED_BASE = 29
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -66,7 +67,9 @@ EXPORTS = [
     "pt_denoise_default_params", "pt_guide_ray", "pt_render_guide", "pt_guide_device_ptr", "pt_read_guide",
     "pt_denoise", "pt_read_denoised", "pt_denoise_host",
     "pt_moments_device_ptr", "pt_read_moments", "pt_denoise_var_default_params", "pt_denoise_var",
-    "pt_denoise_var_host",
+    "pt_denoise_var_host", "pt_denoise_var_plane_host",
+    "pt_temporal_default_params", "pt_reproject", "pt_reproject_host", "pt_temporal_advance", "pt_temporal_reset",
+    "pt_temporal_info", "pt_temporal_device_ptr", "pt_read_temporal", "pt_temporal_denoise",
 ]
 
 
@@ -96,6 +99,19 @@ class DenoiseParams(ctypes.Structure):
 class DenoiseVarParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int), ("sigma_lum", ctypes.c_float), ("sigma_normal", ctypes.c_float),
                 ("sigma_depth", ctypes.c_float)]
+
+
+class TemporalParams(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_uint32), ("alpha_min", ctypes.c_float), ("normal_min", ctypes.c_float),
+                ("depth_rel", ctypes.c_float)]
+
+
+class ReprojectImages(ctypes.Structure):
+    """pt_reproject_images: device pointers for pt_reproject, host pointers
+    for pt_reproject_host."""
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "color", "moments", "guide", "hist_color", "hist_moments", "hist_length", "hist_guide",
+        "out_color", "out_moments", "out_length", "out_variance")]
 
 
 _lib = None
@@ -177,6 +193,16 @@ def lib():
             "pt_denoise_var_default_params": ([ctypes.POINTER(DenoiseVarParams)], i32),
             "pt_denoise_var": ([vp, ctypes.POINTER(DenoiseVarParams), vp], i32),
             "pt_denoise_var_host": ([vp, vp, u32, vp, i32, i32, ctypes.POINTER(DenoiseVarParams), vp], i32),
+            "pt_denoise_var_plane_host": ([vp, vp, vp, i32, i32, ctypes.POINTER(DenoiseVarParams), vp], i32),
+            "pt_temporal_default_params": ([ctypes.POINTER(TemporalParams)], i32),
+            "pt_reproject": ([vp, vp, vp, i32, i32, u32, ctypes.POINTER(ReprojectImages),
+                              ctypes.POINTER(TemporalParams)], i32),
+            "pt_reproject_host": ([vp, vp, i32, i32, u32, ctypes.POINTER(ReprojectImages),
+                                   ctypes.POINTER(TemporalParams)], i32),
+            "pt_temporal_advance": ([vp, vp, u32], i32), "pt_temporal_reset": ([vp], i32),
+            "pt_temporal_info": ([vp, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
+            "pt_temporal_device_ptr": ([vp, i32], vp), "pt_read_temporal": ([vp, vp, vp, vp], i32),
+            "pt_temporal_denoise": ([vp, ctypes.POINTER(DenoiseVarParams), vp], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -465,6 +491,65 @@ def denoise_var_host(rgba, moments, n_samples, guide, width, height, params=None
     return out.reshape(height, width, 4)
 
 
+def denoise_var_plane_host(rgba, variance, guide, width, height, params=None):
+    """pt_denoise_var_plane_host: the variance-guided filter on the host from
+    an explicit (H, W) variance plane, (H, W, 4) float32."""
+    a = np.ascontiguousarray(rgba, np.float32).reshape(-1)
+    v = np.ascontiguousarray(variance, np.float32).reshape(-1)
+    g = np.ascontiguousarray(guide, np.float32).reshape(-1)
+    if a.size != width * height * 4 or g.size != a.size or v.size != width * height:
+        raise PTError("rgba and guide must hold width*height*4 floats, variance width*height")
+    out = np.empty(a.size, np.float32)
+    _check(lib().pt_denoise_var_plane_host(a.ctypes.data, v.ctypes.data, g.ctypes.data, width, height,
+                                           _denoise_var_params(params), out.ctypes.data), "pt_denoise_var_plane_host")
+    return out.reshape(height, width, 4)
+
+
+def temporal_default_params():
+    """pt_temporal_default_params as a TemporalParams."""
+    p = TemporalParams()
+    _check(lib().pt_temporal_default_params(ctypes.byref(p)), "pt_temporal_default_params")
+    return p
+
+
+def _temporal_params(params):
+    """None (the library's defaults), a TemporalParams, or (max_history,
+    alpha_min, normal_min, depth_rel) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, TemporalParams):
+        return ctypes.byref(params)
+    mh, am, nm, dr = params
+    return ctypes.byref(TemporalParams(int(mh), float(am), float(nm), float(dr)))
+
+
+def reproject_host(cam_cur, cam_prev, width, height, n, color, moments, guide, history=None, params=None):
+    """pt_reproject_host: temporal reprojection on the host.  history: None or
+    (colour, moments, length, guide) of the previous frame.  Returns (colour
+    (H, W, 4), moments (H, W, 2), length (H, W), variance (H, W)), float32."""
+    cc = np.ascontiguousarray(cam_cur, np.float32).reshape(16)
+    cp = np.ascontiguousarray(cam_prev, np.float32).reshape(16)
+    npx = width * height
+    c = np.ascontiguousarray(color, np.float32).reshape(-1)
+    m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+    g = np.ascontiguousarray(guide, np.float32).reshape(-1)
+    if c.size != npx * 4 or g.size != npx * 4 or m.size != npx * 2:
+        raise PTError("colour and guide must hold width*height*4 floats, moments width*height*2")
+    hist = [None] * 4
+    if history is not None:
+        hist = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in history]
+        if [a.size for a in hist] != [npx * 4, npx * 2, npx, npx * 4]:
+            raise PTError("history: colour width*height*4 floats, moments *2, length *1, guide *4")
+    oc, om = np.empty(npx * 4, np.float32), np.empty(npx * 2, np.float32)
+    ol, ov = np.empty(npx, np.float32), np.empty(npx, np.float32)
+    im = ReprojectImages(c.ctypes.data, m.ctypes.data, g.ctypes.data, *[_ptr(a) for a in hist],
+                         oc.ctypes.data, om.ctypes.data, ol.ctypes.data, ov.ctypes.data)
+    _check(lib().pt_reproject_host(cc.ctypes.data, cp.ctypes.data, width, height, int(n), ctypes.byref(im),
+                                   _temporal_params(params)), "pt_reproject_host")
+    return (oc.reshape(height, width, 4), om.reshape(height, width, 2), ol.reshape(height, width),
+            ov.reshape(height, width))
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -664,6 +749,51 @@ class Renderer:
         and its moments; with dst_ptr None the library-owned result is read
         back and returned as (H, W, 4) float32."""
         _check(lib().pt_denoise_var(self._c, _denoise_var_params(params), dst_ptr), "pt_denoise_var")
+        if dst_ptr is not None:
+            return None
+        out = np.empty(self.width * self.height * 4, np.float32)
+        _check(lib().pt_read_denoised(self._c, out.ctypes.data, out.size), "pt_read_denoised")
+        return out.reshape(self.height, self.width, 4)
+
+    def reproject(self, cam_cur, cam_prev, width, height, n, images, params=None):
+        """pt_reproject: enqueue the temporal reprojection of device images;
+        `images` is a ReprojectImages of device pointers."""
+        cc = np.ascontiguousarray(cam_cur, np.float32).reshape(16)
+        cp = np.ascontiguousarray(cam_prev, np.float32).reshape(16)
+        _check(lib().pt_reproject(self._c, cc.ctypes.data, cp.ctypes.data, width, height, int(n), ctypes.byref(images),
+                                  _temporal_params(params)), "pt_reproject")
+
+    def temporal_advance(self, ubo16, n_batches):
+        """pt_temporal_advance: one frame of the temporal loop (PT_OPT_MOMENTS 1)."""
+        u = np.ascontiguousarray(ubo16, np.float32).reshape(16)
+        _check(lib().pt_temporal_advance(self._c, u.ctypes.data, int(n_batches)), "pt_temporal_advance")
+
+    def temporal_reset(self):
+        _check(lib().pt_temporal_reset(self._c), "pt_temporal_reset")
+
+    def temporal_info(self):
+        """(frames, samples) since the last reset."""
+        f, s = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().pt_temporal_info(self._c, ctypes.byref(f), ctypes.byref(s)), "pt_temporal_info")
+        return int(f.value), int(s.value)
+
+    def temporal_ptr(self, which):
+        """pt_temporal_device_ptr: 0 colour, 1 moments, 2 length, 3 variance; None when there is none."""
+        return lib().pt_temporal_device_ptr(self._c, which)
+
+    def read_temporal(self):
+        """pt_read_temporal: (colour (H, W, 4), moments (H, W, 2), length (H, W)) float32."""
+        n = self.width * self.height
+        c, m, l = np.empty(n * 4, np.float32), np.empty(n * 2, np.float32), np.empty(n, np.float32)
+        _check(lib().pt_read_temporal(self._c, c.ctypes.data, m.ctypes.data, l.ctypes.data), "pt_read_temporal")
+        return (c.reshape(self.height, self.width, 4), m.reshape(self.height, self.width, 2),
+                l.reshape(self.height, self.width))
+
+    def temporal_denoise(self, params=None, dst_ptr=None):
+        """pt_temporal_denoise: the variance-guided filter of the temporal
+        result; with dst_ptr None the library-owned result is read back and
+        returned as (H, W, 4) float32."""
+        _check(lib().pt_temporal_denoise(self._c, _denoise_var_params(params), dst_ptr), "pt_temporal_denoise")
         if dst_ptr is not None:
             return None
         out = np.empty(self.width * self.height * 4, np.float32)

@@ -46,7 +46,12 @@ extern "C" {
  * PT_OPT_SWEEP_HULL); the per-pixel luminance moments and the
  * variance-guided filter (PT_OPT_MOMENTS, pt_moments_device_ptr,
  * pt_read_moments, pt_denoise_var_params, pt_denoise_var_default_params,
- * pt_denoise_var, pt_denoise_var_host); the exit skip (PT_OPT_EXIT_SKIP). */
+ * pt_denoise_var, pt_denoise_var_host); the exit skip (PT_OPT_EXIT_SKIP); the
+ * seed base and temporal reprojection (PT_OPT_SEED_BASE, pt_temporal_params,
+ * pt_reproject_images, pt_temporal_default_params, pt_reproject,
+ * pt_reproject_host, pt_temporal_advance, pt_temporal_reset, pt_temporal_info,
+ * pt_temporal_device_ptr, pt_read_temporal, pt_temporal_denoise,
+ * pt_denoise_var_plane_host). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -367,6 +372,101 @@ int pt_denoise_var(pt_context* ctx, const pt_denoise_var_params* params, void* d
  * W*H*2, n_samples >= 2.  Pure host function; bit-identical to pt_denoise_var. */
 int pt_denoise_var_host(const float* rgba, const float* moments, uint32_t n_samples, const float* guide, int width,
                         int height, const pt_denoise_var_params* params, float* out);
+/* The same passes on the host from an explicit variance plane of W*H floats
+ * (pass 0's v) instead of moments: pt_denoise_var_host is this function after
+ * its own var0.  Pure host function; bit-identical to pt_temporal_denoise. */
+int pt_denoise_var_plane_host(const float* rgba, const float* variance, const float* guide, int width, int height,
+                              const pt_denoise_var_params* params, float* out);
+
+/* ---- temporal reprojection: frame history across camera moves ----------
+ * SVGF's first stage (Schied et al., HPG 2017).  pt_progressive_camera throws
+ * the image away when the camera changes, as the reference's mainLoop does;
+ * the calls below carry it over instead: the first hit of each pixel of the
+ * new frame (its guide) is projected into the previous camera, the previous
+ * result is read there through four bilinear taps that pass a depth and a
+ * normal test against the previous guide, and the new frame is blended in by
+ * sample counts.  Single-GPU contexts only (PT_ERR_UNSUPPORTED otherwise).
+ *
+ * The statement, shared by the kernel and the host function (every operation
+ * rounds once, divisions are IEEE, nothing is fused; cam_basis is the camera
+ * frame of the guide ray above: right = normalize(cross(dir, -up)), up' =
+ * normalize(cross(right, dir)), tan_fov = tan(radians(fov / 2)); guide_dir is
+ * the guide ray's direction).  Per pixel p = (x, y) of a W x H frame:
+ *   inputs   c (float4), m (float2 {m1,m2}), n >= 1: the new frame, its moments, its sample count
+ *            g (float4 {n.xyz, t}): the new camera's guide;   B = cam_basis(cam_cur), Bp = cam_basis(cam_prev)
+ *            hc, hm, hl (float, samples; 0 = none), hg: the history's colour, moments, length and guide
+ *   no history for p (out = c, out_m = m, out_len = float(n)) if any "else none" below applies
+ *     t = g_p.w;  if !(t < 1e30f) none                                   (a miss)
+ *     P = B.pos + guide_dir(B, W, H, x, y) * t
+ *     v = P - Bp.pos;  z = dot(v, Bp.dir);  if !(z > 0) none
+ *     aspect = float(W) / float(H)
+ *     sx = dot(v, -Bp.right) / (z * (Bp.tan_fov * aspect));   sy = dot(v, -Bp.up) / (z * Bp.tan_fov)
+ *     fx = ((sx + 1) * float(W)) * 0.5f;   fy = ((sy + 1) * float(H)) * 0.5f
+ *     if !(fx > -1 && fx < float(W) && fy > -1 && fy < float(H)) none     (also NaN)
+ *     x0f = floor(fx), ax = fx - x0f, x0 = int(x0f);  y likewise;  dexp = length(v)
+ *     taps q = (x0 + tx, y0 + ty), ty = 0..1 outer, tx = 0..1 inner, outside the frame skipped:
+ *       b = (tx ? ax : 1 - ax) * (ty ? ay : 1 - ay)
+ *       valid iff hl_q > 0 && hg_q.w < 1e30f && fabs(hg_q.w - dexp) <= depth_rel * dexp
+ *                 && dot(g_p.xyz, hg_q.xyz) >= normal_min
+ *       valid: sw += b;  sc.rgb += b * hc_q.rgb;  sm += b * hm_q;  lmin = fmin(lmin, hl_q)
+ *     if !(sw > 0) none
+ *     h = sc / sw;  h_m = sm / sw;  N = fmin(lmin, float(max_history))
+ *     a = fmax(alpha_min, float(n) / (N + float(n)))
+ *     out.rgb = h + (c.rgb - h) * a;  out.a = c.a;  out_m = h_m + (m - h_m) * a;  out_len = N + float(n)
+ *   always   out_var = fmax(0, out_m.y - out_m.x * out_m.x) / fmax(out_len - 1, 1)
+ * t is a distance along a unit ray, so dexp is the distance the previous guide
+ * should hold at that point.  The guide ray passes through integer pixel
+ * coordinates (ndc = 2x/W - 1): no half-pixel offset appears.
+ *
+ * Defaults (pt_temporal_default_params): max_history 64, alpha_min 0,
+ * normal_min 0.5, depth_rel 0.05.  Ranges: max_history 1..65536, alpha_min in
+ * [0, 1], normal_min in [-1, 1], depth_rel finite and > 0; n and n_batches
+ * 1..65536, so every length is an exact float.  Null params: the defaults.
+ * Anything else: PT_ERR_INVALID. */
+typedef struct pt_temporal_params { uint32_t max_history; float alpha_min, normal_min, depth_rel; } pt_temporal_params;
+typedef struct pt_reproject_images {            /* device pointers for pt_reproject, host pointers for pt_reproject_host */
+  const float *color, *moments, *guide;                                  /* W*H*4, W*H*2, W*H*4 */
+  const float *hist_color, *hist_moments, *hist_length, *hist_guide;    /* all four null: no history */
+  float *out_color, *out_moments, *out_length, *out_variance;           /* W*H*4, *2, *1, *1; distinct from the inputs */
+} pt_reproject_images;
+int pt_temporal_default_params(pt_temporal_params* out);
+/* Enqueues the statement on the context's stream.  Colours and guides 16-B
+ * aligned, moments 8-B, lengths and the variance 4-B; no output may be an
+ * input or another output (PT_ERR_INVALID). */
+int pt_reproject(pt_context* ctx, const float cam_cur[16], const float cam_prev[16], int width, int height, uint32_t n,
+                 const pt_reproject_images* images, const pt_temporal_params* params);
+/* The same statement on the host.  Pure host function; the same bits. */
+int pt_reproject_host(const float cam_cur[16], const float cam_prev[16], int width, int height, uint32_t n,
+                      const pt_reproject_images* images, const pt_temporal_params* params);
+/* One frame of the temporal loop, all enqueued and none of it waited for:
+ * sets the camera, clears the accumulator, renders batches 0..n_batches-1 with
+ * moments at the seed base PT_OPT_SEED_BASE plus the samples rendered since
+ * the last reset (mod 2^32) -- the accumulation image and pt_read_moments then
+ * hold exactly what pt_render(0, n_batches) at that seed base gives --, renders
+ * the guide, and reprojects at the default parameters from the previous call's
+ * result, guide and camera into the other of two library-owned image sets
+ * (the first frame after a reset: no history).  Needs PT_OPT_MOMENTS 1, a
+ * scene, lights and a frame (PT_ERR_INVALID); PT_ERR_UNSUPPORTED where moments
+ * are: multi-device contexts, a partition of more than one rank, stats mode,
+ * PT_OPT_COUNT_TRACED.  The history is forgotten by pt_temporal_reset,
+ * pt_upload_scene, pt_scene_upload, pt_upload_lights, pt_set_params and a
+ * change of frame size or of the bound buffer -- never by the camera.
+ * pt_render, pt_dispatch and the progressive calls neither use nor disturb
+ * it. */
+int pt_temporal_advance(pt_context* ctx, const float camera_ubo[16], uint32_t n_batches);
+int pt_temporal_reset(pt_context* ctx);
+/* Frames and samples (mod 2^32) since the last reset; either may be null. */
+int pt_temporal_info(pt_context* ctx, uint32_t* frames, uint32_t* samples);
+/* The last result in device memory: which = 0 colour (W*H float4), 1 moments
+ * (float2), 2 length in samples (float), 3 variance of the mean (float); null
+ * when there is none. */
+void* pt_temporal_device_ptr(pt_context* ctx, int which);
+/* Waits for the last result and copies it; each pointer may be null. */
+int pt_read_temporal(pt_context* ctx, float* rgba, float* moments, float* length);
+/* pt_denoise_var's passes on the temporal colour, with the statement's out_var
+ * as pass 0's variance and the frame's guide; dst_device as for
+ * pt_denoise_var.  PT_ERR_INVALID without a temporal result. */
+int pt_temporal_denoise(pt_context* ctx, const pt_denoise_var_params* params, void* dst_device);
 
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile
@@ -681,6 +781,15 @@ int pt_dist_finalize(pt_context* ctx);
  * intensity is finite; stats mode never skips.  Output is identical;
  * PT_OPT_COUNT_TRACED counts the walks not started. */
 #define PT_OPT_EXIT_SKIP 28
+/* PT_OPT_SEED_BASE: B = 0 (default) to 2^31-1.  The sample of batch b is drawn
+ * from the seed ((b + B) * H + py) * W + px (uint32 arithmetic) instead of
+ * (b * H + py) * W + px, and still folded into the accumulator and the moments
+ * with weight b: a frame rendered from batch 0 with fresh random numbers.  The
+ * shader ties the seed to the fold weight, so every frame from batch 0 repeats
+ * its numbers per pixel, and frames averaged over time would add little.
+ * Every render path (multi-device contexts forward it).  0: the frames of
+ * before. */
+#define PT_OPT_SEED_BASE 29
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
