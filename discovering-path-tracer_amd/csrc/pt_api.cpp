@@ -437,6 +437,8 @@ struct pt_context {
   size_t guide_prev_cap = 0;
   unsigned long long guide_serial = 0, t_guide_serial = 0;
   bool t_guide_aside = false;
+  float* d_spatial_var = nullptr;      // pt_temporal_denoise_spatial's variance plane
+  size_t spatial_var_cap = 0;
   DistState* dist = nullptr;           // pt_dist_init
   pt_group* group = nullptr;           // pt_create_multi: every call goes to the group (pt_group.cpp)
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -1560,6 +1562,7 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_var[0]);
   dev_free(c->d_var[1]);
   dev_free(c->d_guide_prev);
+  dev_free(c->d_spatial_var);
   for (auto& s : c->tset) {
     dev_free(s.color);
     dev_free(s.moments);
@@ -2623,6 +2626,128 @@ int pt_temporal_denoise(pt_context* c, const pt_denoise_var_params* params, void
   if (!guide) return fail(PT_ERR_INVALID, "pt_temporal_denoise: the temporal frame's guide is gone");
   PT_HIP(hipSetDevice(c->device));
   const int rf = var_filter(c, p, s.color, s.variance, guide, (float4*)dst);
+  if (rf) return rf;
+  if ((float4*)dst == c->d_accum) {   // the accumulation buffer given as the destination
+    c->culled_state = 0;
+    c->moments_valid = false;
+  }
+  return PT_OK;
+}
+
+// ---- spatial variance of short histories (pt_denoise.h spatial_var_pixel) ----
+int pt_spatial_var_default_params(pt_spatial_var_params* out) {
+  if (!out) return fail(PT_ERR_INVALID, "null argument");
+  out->below = 2;
+  out->radius = 1;
+  out->sigma_normal = 1.0f;
+  out->sigma_depth = 0.5f;
+  return PT_OK;
+}
+
+static int spatial_var_params(const pt_spatial_var_params* in, pt_spatial_var_params* p) {
+  if (in)
+    *p = *in;
+  else
+    (void)pt_spatial_var_default_params(p);
+  if (!ptdn::spatial_params_ok(p->below, p->radius, p->sigma_normal, p->sigma_depth))
+    return fail(PT_ERR_INVALID,
+                "pt_spatial_var_params: below 0-65536, radius 1-3; sigmas finite, > 0 and with a finite non-zero square");
+  return PT_OK;
+}
+
+// The checks pt_spatial_variance and pt_spatial_variance_host share.
+static int spatial_var_args(const void* moments, const void* length, const void* variance, const void* guide, int w,
+                            int h, const void* out) {
+  if (!moments || !length || !variance || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0 || (long long)w * h > (1ll << 31)) return fail(PT_ERR_INVALID, "bad resolution");
+  if (out == moments || out == length || out == variance || out == guide)
+    return fail(PT_ERR_INVALID, "pt_spatial_variance: the output is also an input");
+  return PT_OK;
+}
+
+int pt_spatial_variance_host(const float* moments, const float* length, const float* variance, const float* guide,
+                             int w, int h, const pt_spatial_var_params* params, float* out) {
+  const int ra = spatial_var_args(moments, length, variance, guide, w, h, out);
+  if (ra) return ra;
+  pt_spatial_var_params p;
+  const int rp = spatial_var_params(params, &p);
+  if (rp) return rp;
+  const size_t n = (size_t)w * (size_t)h;
+  std::vector<float2> m(n);
+  std::vector<float4> g(n);
+  memcpy(m.data(), moments, n * sizeof(float2));
+  memcpy(g.data(), guide, n * sizeof(float4));
+  const ptdn::SpatialImageFetch fetch = {m.data(), length, g.data(), w};
+  const float below = (float)p.below;
+  const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) {
+      const size_t i = (size_t)y * w + x;
+      const float lenp = length[i];
+      out[i] = lenp < below ? ptdn::spatial_var_pixel(fetch, w, h, x, y, p.radius, sn2, sz2, g[i], lenp) : variance[i];
+    }
+  return PT_OK;
+}
+
+int pt_spatial_variance(pt_context* c, const void* moments, const void* length, const void* variance,
+                        const void* guide, int w, int h, const pt_spatial_var_params* params, void* out) {
+  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_spatial_variance: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  const int ra = spatial_var_args(moments, length, variance, guide, w, h, out);
+  if (ra) return ra;
+  pt_spatial_var_params p;
+  const int rp = spatial_var_params(params, &p);
+  if (rp) return rp;
+  if (((uintptr_t)moments & 7) || (((uintptr_t)length | (uintptr_t)variance | (uintptr_t)out) & 3) || ((uintptr_t)guide & 15))
+    return fail(PT_ERR_INVALID, "pt_spatial_variance: moments must be 8-B aligned, the guide 16-B, length, variance and out 4-B");
+  PT_HIP(hipSetDevice(c->device));
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(ptd::launch_spatial_var((const float2*)moments, (const float*)length, (const float*)variance,
+                                 (const float4*)guide, (float*)out, w, h, p.below, p.radius,
+                                 p.sigma_normal * p.sigma_normal, p.sigma_depth * p.sigma_depth, c->stream));
+  if ((float4*)out == c->d_accum) {   // the accumulation buffer given as the destination
+    c->culled_state = 0;
+    c->moments_valid = false;
+  }
+  return mark_shared(c);
+}
+
+int pt_temporal_denoise_spatial(pt_context* c, const pt_denoise_var_params* params,
+                                const pt_spatial_var_params* spatial, void* dst) {
+  if (c && c->group)
+    return fail(PT_ERR_UNSUPPORTED, "pt_temporal_denoise_spatial: not on a multi-device context (pt_create_multi)");
+  if (!c) return fail(PT_ERR_INVALID, "null context");
+  pt_denoise_var_params p;
+  const int rp = denoise_var_params(params, &p);
+  if (rp) return rp;
+  pt_spatial_var_params sp;
+  const int rs = spatial_var_params(spatial, &sp);
+  if (rs) return rs;
+  if (!temporal_ready(c)) return fail(PT_ERR_INVALID, "no temporal result for the current frame (pt_temporal_advance)");
+  if (((uintptr_t)dst) & 15) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
+  const pt_context::TemporalSet& s = c->tset[c->t_cur];
+  if (dst && (float4*)dst == s.color)
+    return fail(PT_ERR_INVALID, "pt_temporal_denoise_spatial: source and destination must differ");
+  const float4* guide = c->t_guide_aside ? c->d_guide_prev : c->guide_serial == c->t_guide_serial ? c->d_guide : nullptr;
+  if (!guide) return fail(PT_ERR_INVALID, "pt_temporal_denoise_spatial: the temporal frame's guide is gone");
+  PT_HIP(hipSetDevice(c->device));
+  const int w = c->width, h = c->height;
+  const size_t n = (size_t)w * h;
+  if (!c->d_spatial_var || c->spatial_var_cap < n) {
+    { const int rc_ = quiesce(c); if (rc_) return rc_; }
+    dev_free(c->d_spatial_var);
+    c->spatial_var_cap = 0;
+    PT_HIP(hipMalloc((void**)&c->d_spatial_var, n * sizeof(float)));
+    c->spatial_var_cap = n;
+  }
+  const int ro = order_shared(c);
+  if (ro) return ro;
+  PT_HIP(ptd::launch_spatial_var(s.moments, s.length, s.variance, guide, c->d_spatial_var, w, h, sp.below, sp.radius,
+                                 sp.sigma_normal * sp.sigma_normal, sp.sigma_depth * sp.sigma_depth, c->stream));
+  const int rm = mark_shared(c);
+  if (rm) return rm;
+  const int rf = var_filter(c, p, s.color, c->d_spatial_var, guide, (float4*)dst);
   if (rf) return rf;
   if ((float4*)dst == c->d_accum) {   // the accumulation buffer given as the destination
     c->culled_state = 0;

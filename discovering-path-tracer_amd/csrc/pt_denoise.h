@@ -23,7 +23,9 @@
 // Further down: the luminance of the moments the render kernels fold
 // (PT_OPT_MOMENTS) and the variance-guided filter built on them
 // (atrous_var_pixel: pt_denoise_var, pt_denoise_var_host), stated the same way,
-// and temporal reprojection (reproject_pixel: pt_reproject, pt_reproject_host).
+// temporal reprojection (reproject_pixel: pt_reproject, pt_reproject_host) and
+// the spatial variance estimate of pixels with a short history
+// (spatial_var_pixel: pt_spatial_variance, pt_spatial_variance_host).
 #pragma once
 #include "pt_math.h"
 
@@ -372,4 +374,86 @@ PT_FN ReprojOut reproject_pixel(const HistImages& hist, const CamBasis& B, const
   return o;
 }
 
+// ---- spatial variance of short histories (pt_spatial_variance) --------------
+// SVGF's variance estimation stage: a pixel whose history is shorter than
+// `below` samples has no usable variance of its own (one sample: m2 == m1 * m1,
+// out_var above is 0), so it takes the variance of the moments pooled over its
+// neighbourhood under the geometric edge-stops.  Per pixel p, from moments m,
+// length len (>= 1), variance var and guide g = {n.xyz, t}:
+//   if !(len_p < float(below))  out_p = var_p                       (the same bits)
+//   else over q = p + (dx, dy), dy = -r..r outer, dx = -r..r inner, taps outside
+//   the frame skipped, the centre included:
+//     d2n = (dnx*dnx + dny*dny) + dnz*dnz  (normals of g_p - g_q);  dz = g_p.w - g_q.w
+//     w   = exp_(-(d2n / sn2 + (dz * dz) / sz2)) * len_q
+//     sw += w;  s1 += w * m_q.x;  s2 += w * m_q.y
+//   M1 = s1 / sw;  M2 = s2 / sw;  out_p = fmax_(0, M2 - M1 * M1) / len_p
+// sn2 = sigma_normal^2, sz2 = sigma_depth^2.  The centre tap weighs len_p >= 1,
+// so sw > 0 for finite input; a hit next to a miss has dz * dz = inf, w = 0; two
+// misses pool their zero moments.  A tap weighs its sample count, which makes
+// M2 - M1 * M1 the pooled per-sample variance; / len_p: that of p's mean.
+constexpr int kMaxSpatialRadius = 3;
+
+PT_FN bool spatial_params_ok(uint32_t below, int radius, float sigma_normal, float sigma_depth) {
+  if (below > 65536u || radius < 1 || radius > kMaxSpatialRadius) return false;
+  const float big = 3.40282347e38f;
+  if (!(sigma_normal > 0.0f && sigma_normal <= big && sigma_depth > 0.0f && sigma_depth <= big)) return false;
+  const float n2 = sigma_normal * sigma_normal, z2 = sigma_depth * sigma_depth;
+  return n2 > 0.0f && n2 <= big && z2 > 0.0f && z2 <= big;
+}
+
+// One short pixel (the caller has tested len_p < below).  Fetch:
+// operator()(qx, qy, &m, &len, &g) for a tap inside the frame.
+template <class Fetch>
+PT_FN float spatial_var_pixel(const Fetch& fetch, int W, int H, int x, int y, int r, float sn2, float sz2, float4 gp,
+                              float lenp) {
+  float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
+  for (int dy = -r; dy <= r; ++dy) {
+    const int qy = y + dy;
+    if (qy < 0 || qy >= H) continue;
+    for (int dx = -r; dx <= r; ++dx) {
+      const int qx = x + dx;
+      if (qx < 0 || qx >= W) continue;
+      float2 mq;
+      float lq;
+      float4 gq;
+      fetch(qx, qy, &mq, &lq, &gq);
+      const float nx = gp.x - gq.x, ny = gp.y - gq.y, nz = gp.z - gq.z;
+      const float d2n = (nx * nx + ny * ny) + nz * nz;
+      const float dz = gp.w - gq.w;
+      // a tap whose guide equals the centre's (the centre itself; a miss beside a miss -- and misses never find
+      // history, so a frame's background stays short): d2n = dz = 0, the argument is -0, exp_(-0) is 1 and
+      // 1 * len_q is len_q -- the statement's bits for finite guides, without the exp_ and the two divisions
+      float w = lq;
+      if (!(gp.x == gq.x && gp.y == gq.y && gp.z == gq.z && gp.w == gq.w))
+        w = exp_(-(d2n / sn2 + (dz * dz) / sz2)) * lq;
+      sw += w;
+      s1 += w * mq.x;
+      s2 += w * mq.y;
+    }
+  }
+  const float M1 = s1 / sw, M2 = s2 / sw;
+  return fmax_(0.0f, M2 - M1 * M1) / lenp;
+}
+
+struct SpatialImageFetch {
+  const float2* moments;
+  const float* length;
+  const float4* guide;
+  int W;
+  __host__ __device__ inline void operator()(int qx, int qy, float2* m, float* l, float4* g) const {
+    const size_t i = (size_t)qy * (size_t)W + (size_t)qx;
+    *m = moments[i];
+    *l = length[i];
+    *g = guide[i];
+  }
+};
+
 }  // namespace ptdn
+
+namespace ptd {
+// The estimate's launch (pt_denoise.hip spatial_var_kernel): out, distinct from
+// the four inputs, receives var where len >= below and the statement elsewhere.
+hipError_t launch_spatial_var(const float2* moments, const float* length, const float* variance, const float4* guide,
+                              float* out, int width, int height, uint32_t below, int radius, float sn2, float sz2,
+                              hipStream_t stream);
+}  // namespace ptd

@@ -1,6 +1,7 @@
 // pt_denoise.hip — the edge-avoiding a-trous filter's pass kernels
-// (pt_denoise), those of the variance-guided filter (pt_denoise_var, below) and
-// the temporal reprojection kernel (pt_reproject, last); the statements are
+// (pt_denoise), those of the variance-guided filter (pt_denoise_var, below),
+// the temporal reprojection kernel (pt_reproject) and the spatial variance
+// estimate of short histories (pt_spatial_variance, last); the statements are
 // pt_denoise.h, shared with the host.
 //
 // One pixel per lane, 16x16 pixels per workgroup, a wave a 16x4 strip: the
@@ -163,7 +164,55 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float4* __restrict
   out_variance[i] = o.var;
 }
 
+// ---- spatial variance of short histories (pt_denoise.h spatial_var_pixel) ----
+// The same shape.  Every lane reads its length and variance (a tile row: 64
+// consecutive bytes of each); a lane whose history is long enough stores the
+// variance and is done.  Only a short lane goes on to its guide and the
+// (2r + 1)^2 taps of moments, length and guide (28 B a tap), so a wave with no
+// short lane -- and hence a tile with none -- reads neither guide nor moments:
+// its branch is skipped on an empty exec mask, no barrier needed.  In a running
+// loop a few percent of the first-hit pixels are short, and they come in runs (a
+// disoccluded face, a frame edge); the misses stay short for good (they never
+// find history), and their taps onto other misses take the statement's
+// equal-guide shortcut.  The taps are read from the images: staging a 22x22 halo
+// of three images (13.6 KB at r = 3) would make a tile with one short pixel
+// read 484 x 28 B to serve 49 taps and cost every tile a barrier; where all
+// pixels are short (a first frame) neighbouring lanes' taps overlap and come
+// from the caches, as atrous_kernel's do.  That costs 0.0033 ms per tap at
+// 1080p, radius 1 to 3 alike, and most of it is the three loads: the shortcut
+// takes the exp_ and the divisions off nine pixels in ten of an orbit frame and
+// buys 9 %.  A staged variant has not been built; at the default radius 1 it
+// could save at most the 0.034 ms the nine taps cost.
+__global__ __launch_bounds__(256) void spatial_var_kernel(const float2* __restrict__ moments,
+                                                          const float* __restrict__ length,
+                                                          const float* __restrict__ variance,
+                                                          const float4* __restrict__ guide, float* __restrict__ out,
+                                                          int W, int H, float below, int r, float sn2, float sz2) {
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const size_t i = (size_t)y * (size_t)W + (size_t)x;
+  const float lenp = length[i];
+  float v = variance[i];
+  if (lenp < below) {
+    const SpatialImageFetch fetch = {moments, length, guide, W};
+    v = spatial_var_pixel(fetch, W, H, x, y, r, sn2, sz2, guide[i], lenp);
+  }
+  out[i] = v;
+}
+
 }  // namespace
+
+hipError_t launch_spatial_var(const float2* moments, const float* length, const float* variance, const float4* guide,
+                              float* out, int width, int height, uint32_t below, int radius, float sn2, float sz2,
+                              hipStream_t stream) {
+  if (width <= 0 || height <= 0 || below > 65536u || radius < 1 || radius > kMaxSpatialRadius)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+  spatial_var_kernel<<<grid, 256, 0, stream>>>(moments, length, variance, guide, out, width, height, (float)below,
+                                               radius, sn2, sz2);
+  return hipGetLastError();
+}
 
 hipError_t launch_reproject(const float4* color, const float2* moments, const float4* guide, const float4* hist_color,
                             const float2* hist_moments, const float* hist_length, const float4* hist_guide,

@@ -6,7 +6,7 @@
 //   pt_render scene.obj [-w 1920] [-h 1080] [-spp 8] [-depth 4] [-sss 3]
 //             [-fused] [-o out.pfm] [-png out.png] [-device 0 | -devices 0,1,..]
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
-//             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K]
+//             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -28,7 +28,9 @@
 // z' = z*c - x*s with c = 0.99939083f, s = 0.0348995f (2 degrees), applied to
 // the position and the direction.  -o / -png then hold the temporal colour,
 // or, with -denoise-var, pt_temporal_denoise's result at the default
-// parameters.
+// parameters.  -temporal-spatial (with -temporal K) filters the final frame with
+// pt_temporal_denoise_spatial instead, both parameter sets at their defaults:
+// pixels with a short history take the spatial variance estimate.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -52,7 +54,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr,
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
-            "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
+            "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
             "       [-progressive N [-chunk K] [-orbit-at B]]\n",
             argv[0]);
     return 2;
@@ -63,7 +65,7 @@ int main(int argc, char** argv) {
   bool fused = false;
   int progressive = 0, chunk = 8, orbit_at = -1, temporal = 0;
   std::string cache_path, png_path, guide_path;
-  bool denoise = false, denoise_var = false;
+  bool denoise = false, denoise_var = false, temporal_spatial = false;
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -91,6 +93,11 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "-chunk")) chunk = atoi(next());
     else if (!strcmp(argv[i], "-orbit-at")) orbit_at = atoi(next());
     else if (!strcmp(argv[i], "-temporal")) temporal = atoi(next());
+    else if (!strcmp(argv[i], "-temporal-spatial")) temporal_spatial = true;
+  }
+  if (temporal_spatial && temporal <= 0) {
+    fprintf(stderr, "-temporal-spatial needs -temporal K\n");
+    return 2;
   }
   pt_scene* scene = nullptr;
   auto t0 = std::chrono::steady_clock::now();
@@ -199,7 +206,10 @@ int main(int argc, char** argv) {
   if (!out_path.empty() || !png_path.empty()) {
     std::vector<float> rgba((size_t)W * H * 4);
     if (temporal > 0 && progressive == 0) {
-      if (denoise_var) {
+      if (temporal_spatial) {
+        check(pt_temporal_denoise_spatial(ctx, nullptr, nullptr, nullptr), "temporal denoise spatial");
+        check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+      } else if (denoise_var) {
         check(pt_temporal_denoise(ctx, nullptr, nullptr), "temporal denoise");
         check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
       } else {

@@ -70,6 +70,7 @@ EXPORTS = [
     "pt_denoise_var_host", "pt_denoise_var_plane_host",
     "pt_temporal_default_params", "pt_reproject", "pt_reproject_host", "pt_temporal_advance", "pt_temporal_reset",
     "pt_temporal_info", "pt_temporal_device_ptr", "pt_read_temporal", "pt_temporal_denoise",
+    "pt_spatial_var_default_params", "pt_spatial_variance_host", "pt_spatial_variance", "pt_temporal_denoise_spatial",
 ]
 
 
@@ -104,6 +105,11 @@ class DenoiseVarParams(ctypes.Structure):
 class TemporalParams(ctypes.Structure):
     _fields_ = [("max_history", ctypes.c_uint32), ("alpha_min", ctypes.c_float), ("normal_min", ctypes.c_float),
                 ("depth_rel", ctypes.c_float)]
+
+
+class SpatialVarParams(ctypes.Structure):
+    _fields_ = [("below", ctypes.c_uint32), ("radius", ctypes.c_int), ("sigma_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float)]
 
 
 class ReprojectImages(ctypes.Structure):
@@ -203,6 +209,11 @@ def lib():
             "pt_temporal_info": ([vp, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
             "pt_temporal_device_ptr": ([vp, i32], vp), "pt_read_temporal": ([vp, vp, vp, vp], i32),
             "pt_temporal_denoise": ([vp, ctypes.POINTER(DenoiseVarParams), vp], i32),
+            "pt_spatial_var_default_params": ([ctypes.POINTER(SpatialVarParams)], i32),
+            "pt_spatial_variance_host": ([vp, vp, vp, vp, i32, i32, ctypes.POINTER(SpatialVarParams), vp], i32),
+            "pt_spatial_variance": ([vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(SpatialVarParams), vp], i32),
+            "pt_temporal_denoise_spatial": ([vp, ctypes.POINTER(DenoiseVarParams), ctypes.POINTER(SpatialVarParams),
+                                             vp], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -550,6 +561,41 @@ def reproject_host(cam_cur, cam_prev, width, height, n, color, moments, guide, h
             ov.reshape(height, width))
 
 
+def spatial_var_default_params():
+    """pt_spatial_var_default_params as a SpatialVarParams."""
+    p = SpatialVarParams()
+    _check(lib().pt_spatial_var_default_params(ctypes.byref(p)), "pt_spatial_var_default_params")
+    return p
+
+
+def _spatial_var_params(params):
+    """None (the library's defaults), a SpatialVarParams, or (below, radius,
+    sigma_normal, sigma_depth) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, SpatialVarParams):
+        return ctypes.byref(params)
+    below, radius, sn, sz = params
+    return ctypes.byref(SpatialVarParams(int(below), int(radius), float(sn), float(sz)))
+
+
+def spatial_variance_host(moments, length, variance, guide, width, height, params=None):
+    """pt_spatial_variance_host: the variance plane with the pixels whose
+    length is below params.below estimated from their neighbourhood's moments,
+    (H, W) float32."""
+    npx = width * height
+    m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+    l = np.ascontiguousarray(length, np.float32).reshape(-1)
+    v = np.ascontiguousarray(variance, np.float32).reshape(-1)
+    g = np.ascontiguousarray(guide, np.float32).reshape(-1)
+    if m.size != npx * 2 or l.size != npx or v.size != npx or g.size != npx * 4:
+        raise PTError("moments must hold width*height*2 floats, length and variance width*height, guide width*height*4")
+    out = np.empty(npx, np.float32)
+    _check(lib().pt_spatial_variance_host(m.ctypes.data, l.ctypes.data, v.ctypes.data, g.ctypes.data, width, height,
+                                          _spatial_var_params(params), out.ctypes.data), "pt_spatial_variance_host")
+    return out.reshape(height, width)
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -794,6 +840,26 @@ class Renderer:
         result; with dst_ptr None the library-owned result is read back and
         returned as (H, W, 4) float32."""
         _check(lib().pt_temporal_denoise(self._c, _denoise_var_params(params), dst_ptr), "pt_temporal_denoise")
+        if dst_ptr is not None:
+            return None
+        out = np.empty(self.width * self.height * 4, np.float32)
+        _check(lib().pt_read_denoised(self._c, out.ctypes.data, out.size), "pt_read_denoised")
+        return out.reshape(self.height, self.width, 4)
+
+    def spatial_variance(self, moments_ptr, length_ptr, variance_ptr, guide_ptr, width, height, out_ptr, params=None):
+        """pt_spatial_variance: enqueue the spatial variance estimate of device
+        images (float2 moments, float length and variance, float4 guide) into
+        the float plane at out_ptr."""
+        _check(lib().pt_spatial_variance(self._c, moments_ptr, length_ptr, variance_ptr, guide_ptr, width, height,
+                                         _spatial_var_params(params), out_ptr), "pt_spatial_variance")
+
+    def temporal_denoise_spatial(self, params=None, spatial_params=None, dst_ptr=None):
+        """pt_temporal_denoise_spatial: pt_temporal_denoise with the variance
+        of short histories estimated spatially first; with dst_ptr None the
+        library-owned result is read back and returned as (H, W, 4) float32."""
+        _check(lib().pt_temporal_denoise_spatial(self._c, _denoise_var_params(params),
+                                                 _spatial_var_params(spatial_params), dst_ptr),
+               "pt_temporal_denoise_spatial")
         if dst_ptr is not None:
             return None
         out = np.empty(self.width * self.height * 4, np.float32)

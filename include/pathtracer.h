@@ -51,7 +51,9 @@ extern "C" {
  * pt_reproject_images, pt_temporal_default_params, pt_reproject,
  * pt_reproject_host, pt_temporal_advance, pt_temporal_reset, pt_temporal_info,
  * pt_temporal_device_ptr, pt_read_temporal, pt_temporal_denoise,
- * pt_denoise_var_plane_host). */
+ * pt_denoise_var_plane_host); the spatial variance estimate of short histories
+ * (pt_spatial_var_params, pt_spatial_var_default_params,
+ * pt_spatial_variance_host, pt_spatial_variance, pt_temporal_denoise_spatial). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -467,6 +469,63 @@ int pt_read_temporal(pt_context* ctx, float* rgba, float* moments, float* length
  * as pass 0's variance and the frame's guide; dst_device as for
  * pt_denoise_var.  PT_ERR_INVALID without a temporal result. */
 int pt_temporal_denoise(pt_context* ctx, const pt_denoise_var_params* params, void* dst_device);
+
+/* ---- spatial variance of pixels with too few samples -------------------
+ * SVGF's variance estimation stage.  A pixel holding one sample has m2 ==
+ * m1 * m1, so the statement's out_var is 0, the filter's den is 1e-6 and every
+ * tap of another luminance weighs nothing: at one sample per frame the first
+ * frame after a reset, every disoccluded pixel and every pixel entering at the
+ * frame edge pass pt_temporal_denoise unfiltered.  Where the history is shorter
+ * than `below` samples the variance is therefore estimated from the moments of
+ * the neighbourhood under the filter's geometric edge-stops.  The statement,
+ * shared by the kernel and the host function (every operation rounds once,
+ * divisions are IEEE, nothing is fused, exp is the pinned fp32 exp).  Per pixel
+ * p of a W x H frame, from moments m (float2 {m1, m2}), length len (float,
+ * >= 1), variance var (float) and guide g (float4 {n.xyz, t}):
+ *   if !(len_p < float(below))   out_p = var_p                      (the same bits)
+ *   else over q = p + (dx, dy), dy = -radius..radius outer, dx likewise inner,
+ *   taps outside the frame skipped, the centre included:
+ *     d2n = (dnx*dnx + dny*dny) + dnz*dnz   (normals of g_p - g_q);   dz = g_p.w - g_q.w
+ *     w   = exp(-(d2n / (sn*sn) + (dz*dz) / (sz*sz))) * len_q
+ *     sw += w;   s1 += w * m_q.x;   s2 += w * m_q.y
+ *   M1 = s1 / sw;   M2 = s2 / sw;   out_p = fmax(0, M2 - M1 * M1) / len_p
+ * The centre tap weighs len_p >= 1, so sw > 0 for finite input; a hit next to a
+ * miss has dz*dz = inf, hence w = 0; two misses pool their zero moments.  A tap
+ * weighs its sample count: M2 - M1 * M1 is the pooled variance of one sample,
+ * divided by the pixel's own count.
+ *
+ * Ranges: below 0..65536 (0 and 1 select no pixel: out = var), radius 1..3,
+ * both sigmas finite and > 0 with finite non-zero squares.  Null params: the
+ * defaults.  Anything else: PT_ERR_INVALID.
+ * Defaults (pt_spatial_var_default_params): below 2, radius 1, sigma_normal 1,
+ * sigma_depth 0.5: of a grid over below {2, 3, 4, 8}, radius {1, 2, 3} and both
+ * sigmas {0.25, 0.5, 1}, scored on first frames, 60 degree jumps and eighth
+ * orbit frames of two scenes at 1 and 2 spp against 256 spp, the best point
+ * that leaves no orbit frame worse than pt_temporal_denoise does.  The best
+ * point overall, below 8 at the same radius and sigmas, scores 1.3 % better by
+ * making 2-spp orbit frames worse; a wider window always scores worse
+ * (profiles/spatial_var/grid.json). */
+typedef struct pt_spatial_var_params { uint32_t below; int radius; float sigma_normal, sigma_depth; } pt_spatial_var_params;
+int pt_spatial_var_default_params(pt_spatial_var_params* out);
+/* The statement on the host: moments W*H*2 floats, length and variance W*H,
+ * guide W*H*4, out W*H, distinct from every input.  Pure host function. */
+int pt_spatial_variance_host(const float* moments, const float* length, const float* variance, const float* guide,
+                             int width, int height, const pt_spatial_var_params* params, float* out);
+/* Enqueues the statement on the context's stream; all pointers are device
+ * memory, moments 8-B aligned, length and variance 4-B, the guide 16-B, out
+ * 4-B and distinct from every input (PT_ERR_INVALID).  The same bits as the
+ * host function. */
+int pt_spatial_variance(pt_context* ctx, const void* moments, const void* length, const void* variance,
+                        const void* guide, int width, int height, const pt_spatial_var_params* params, void* out);
+/* pt_temporal_denoise with pass 0's variance plane replaced by the estimate
+ * from the temporal result's moments, length, variance and guide, written to a
+ * library-owned plane: the temporal result (pt_temporal_device_ptr 0-3) is
+ * only read, so the history is not disturbed.  filter_params and
+ * spatial_params null: the defaults of each; dst_device as for
+ * pt_temporal_denoise.  Errors: those of pt_temporal_denoise, and bad
+ * spatial_params.  When no pixel is short it gives pt_temporal_denoise's bits. */
+int pt_temporal_denoise_spatial(pt_context* ctx, const pt_denoise_var_params* filter_params,
+                                const pt_spatial_var_params* spatial_params, void* dst_device);
 
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile

@@ -1,0 +1,178 @@
+// Test infrastructure: a stand-alone host program around
+// pt_spatial_variance_host (csrc/pt_denoise.h spatial_var_pixel, compiled for
+// the host), on the shapes the tests use -- for sanitizer runs on the CPU:
+//
+//   S="-O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off \
+//      -fno-fast-math -D__HIP_PLATFORM_AMD__ -Iinclude -Idiscovering-path-tracer_amd/csrc"
+//   for f in tests/spatial_var_check.cpp discovering-path-tracer_amd/csrc/pt_api.cpp \
+//            discovering-path-tracer_amd/csrc/pt_group.cpp discovering-path-tracer_amd/csrc/scene/*.cpp; do
+//     hipcc $S -c $f -o san/$(basename $f .cpp).o; done          # host objects, instrumented
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined san/*.o \
+//     discovering-path-tracer_amd/build/pt_device.o discovering-path-tracer_amd/build/pt_denoise.o \
+//     -lpthread -o spatial_var_check && ./spatial_var_check
+//
+// (the host code under test carries the instrumentation; the program calls
+// nothing that touches a GPU, and it is run on the CPU only).
+// tests/test_spatial_var.py builds it plainly against libptamd.so and runs it.
+// At 16x16, 37x23 and 64x48, radii 1 to 3 and below 0, 1, 2, 4 and 65536 it
+// runs seeded images -- lengths of 1 among long ones, on the frame's corners
+// and edges, a block of misses, a normal flip and a depth step -- and checks
+// that the output is finite and not negative, that a pixel at or above the
+// threshold keeps its variance bit for bit, that below 0 and 1 change nothing,
+// that the exact arrays it was given (no slack behind them) suffice, a
+// checkerboard with a known answer, and that bad arguments are refused.  Exit
+// status 0 and one "ok" line, or 1 and what failed.
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "pathtracer.h"
+
+namespace {
+
+uint32_t g_state = 2463534242u;
+float rnd() {   // xorshift32 -> [0, 1)
+  g_state ^= g_state << 13;
+  g_state ^= g_state >> 17;
+  g_state ^= g_state << 5;
+  return (float)(g_state >> 8) * (1.0f / 16777216.0f);
+}
+
+int fails = 0;
+void expect(bool ok, const char* what) {
+  if (!ok) {
+    fprintf(stderr, "FAILED: %s\n", what);
+    ++fails;
+  }
+}
+
+struct Images {
+  std::vector<float> m, l, v, g;
+};
+
+Images make(int W, int H) {
+  const size_t n = (size_t)W * H;
+  Images im;
+  im.m.assign(n * 2, 0.0f);
+  im.l.assign(n, 0.0f);
+  im.v.assign(n, 0.0f);
+  im.g.assign(n * 4, 0.0f);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t i = (size_t)y * W + x;
+      float* g = &im.g[4 * i];
+      const bool miss = y >= H / 4 && y < H / 4 + H / 3 && x >= W / 4 && x < W / 4 + W / 3;
+      if (miss) {
+        g[3] = 1e30f;
+      } else {
+        g[2] = x < W / 8 ? -1.0f : 1.0f;                                   // a normal flip
+        g[3] = (3.0f + 0.01f * (float)x + 0.02f * (float)y) * (y >= 3 * H / 4 ? 1.2f : 1.0f);
+      }
+      const bool edge = x == 0 || y == 0 || x == W - 1 || y == H - 1;
+      float len = (float)(2 + (int)(63.0f * rnd()));
+      if (rnd() < 0.35f || (edge && rnd() < 0.5f)) len = 1.0f;
+      if ((x == 0 || x == W - 1) && (y == 0 || y == H - 1)) len = 1.0f;   // the four corners
+      const bool fire = rnd() < 0.05f;
+      const float m1 = miss ? 0.0f : 2.0f * rnd() * (fire ? 40.0f : 1.0f);
+      const float spread = (0.05f + 1.45f * rnd()) * (fire ? 40.0f : 1.0f);
+      const float m2 = miss ? 0.0f : len == 1.0f ? m1 * m1 : m1 * m1 + spread * spread;
+      im.m[2 * i] = m1, im.m[2 * i + 1] = m2;
+      im.l[i] = len;
+      im.v[i] = fmaxf(0.0f, m2 - m1 * m1) / fmaxf(len - 1.0f, 1.0f);
+    }
+  return im;
+}
+
+void shapes() {
+  const int sizes[3][2] = {{16, 16}, {37, 23}, {64, 48}};
+  const uint32_t belows[5] = {0, 1, 2, 4, 65536};
+  for (const auto& s : sizes) {
+    const int W = s[0], H = s[1];
+    const size_t n = (size_t)W * H;
+    const Images im = make(W, H);
+    std::vector<float> out(n);
+    for (int r = 1; r <= 3; ++r)
+      for (uint32_t below : belows) {
+        const pt_spatial_var_params p = {below, r, r == 2 ? 0.25f : 1.0f, r == 3 ? 0.5f : 1.0f};
+        std::fill(out.begin(), out.end(), -7.0f);
+        expect(pt_spatial_variance_host(im.m.data(), im.l.data(), im.v.data(), im.g.data(), W, H, &p, out.data()) == PT_OK,
+               "the call");
+        bool finite = true, kept = true;
+        size_t estimated = 0, positive = 0;
+        for (size_t i = 0; i < n; ++i) {
+          finite = finite && isfinite(out[i]) && out[i] >= 0.0f;
+          if (im.l[i] < (float)below) {
+            ++estimated;
+            if (out[i] > 0.0f) ++positive;
+          } else {
+            kept = kept && memcmp(&out[i], &im.v[i], 4) == 0;
+          }
+        }
+        expect(finite, "the output is finite and not negative");
+        expect(kept, "a pixel at or above the threshold keeps its variance bit for bit");
+        if (below <= 1) expect(estimated == 0 && memcmp(out.data(), im.v.data(), n * 4) == 0, "below 0 and 1 change nothing");
+        if (below == 65536) expect(estimated == n, "below 65536 selects every pixel");
+        if (below >= 2) expect(estimated > 0 && positive > estimated / 2, "short pixels get a variance above 0");
+      }
+    // null params are the defaults
+    std::vector<float> a(n), b(n);
+    pt_spatial_var_params d;
+    expect(pt_spatial_var_default_params(&d) == PT_OK, "defaults");
+    expect(pt_spatial_variance_host(im.m.data(), im.l.data(), im.v.data(), im.g.data(), W, H, nullptr, a.data()) == PT_OK &&
+               pt_spatial_variance_host(im.m.data(), im.l.data(), im.v.data(), im.g.data(), W, H, &d, b.data()) == PT_OK &&
+               memcmp(a.data(), b.data(), n * 4) == 0,
+           "null params are the defaults");
+    // arguments
+    const float *m = im.m.data(), *l = im.l.data(), *v = im.v.data(), *g = im.g.data();
+    expect(pt_spatial_variance_host(nullptr, l, v, g, W, H, nullptr, out.data()) == PT_ERR_INVALID, "null moments");
+    expect(pt_spatial_variance_host(m, nullptr, v, g, W, H, nullptr, out.data()) == PT_ERR_INVALID, "null length");
+    expect(pt_spatial_variance_host(m, l, nullptr, g, W, H, nullptr, out.data()) == PT_ERR_INVALID, "null variance");
+    expect(pt_spatial_variance_host(m, l, v, nullptr, W, H, nullptr, out.data()) == PT_ERR_INVALID, "null guide");
+    expect(pt_spatial_variance_host(m, l, v, g, W, H, nullptr, nullptr) == PT_ERR_INVALID, "null out");
+    expect(pt_spatial_variance_host(m, l, v, g, 0, H, nullptr, out.data()) == PT_ERR_INVALID, "size");
+    expect(pt_spatial_variance_host(m, l, v, g, W, H, nullptr, const_cast<float*>(v)) == PT_ERR_INVALID, "out is an input");
+    const pt_spatial_var_params bad[6] = {{65537, 1, 1.0f, 1.0f}, {2, 0, 1.0f, 1.0f},  {2, 4, 1.0f, 1.0f},
+                                          {2, 1, 0.0f, 1.0f},     {2, 1, 1.0f, -1.0f}, {2, 1, 1e-30f, 1.0f}};
+    for (const auto& p : bad)
+      expect(pt_spatial_variance_host(m, l, v, g, W, H, &p, out.data()) == PT_ERR_INVALID, "bad params");
+  }
+}
+
+// Flat guide, one sample everywhere, L alternating 1 and 10: the nine taps of
+// an interior pixel weigh 1 each, five of its own L and four of the other.
+// Centre 1: M1 = 45 / 9 = 5, M2 = 405 / 9 = 45, variance 20; centre 10: M1 =
+// 54 / 9 = 6, M2 = 504 / 9 = 56, variance 20.  An edge or corner pixel has as
+// many taps of either: M1 = 5.5, M2 = 50.5, variance 20.25.  All exact.
+void checkerboard() {
+  const int W = 19, H = 17;
+  const size_t n = (size_t)W * H;
+  std::vector<float> m(n * 2), l(n, 1.0f), v(n, 0.0f), g(n * 4, 0.0f), out(n);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t i = (size_t)y * W + x;
+      const float L = ((x + y) & 1) ? 10.0f : 1.0f;
+      m[2 * i] = L, m[2 * i + 1] = L * L;
+      g[4 * i + 2] = 1.0f, g[4 * i + 3] = 3.0f;
+    }
+  expect(pt_spatial_variance_host(m.data(), l.data(), v.data(), g.data(), W, H, nullptr, out.data()) == PT_OK, "checkerboard call");
+  bool ok = true;
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const bool edge = x == 0 || y == 0 || x == W - 1 || y == H - 1;
+      ok = ok && out[(size_t)y * W + x] == (edge ? 20.25f : 20.0f);
+    }
+  expect(ok, "checkerboard: 20 inside, 20.25 on the edges");
+}
+
+}  // namespace
+
+int main() {
+  shapes();
+  checkerboard();
+  if (fails) return 1;
+  printf("ok: pt_spatial_variance_host on 3 shapes x 3 radii x 5 thresholds and a checkerboard\n");
+  return 0;
+}
