@@ -1,4 +1,5 @@
-// pt_api.cpp — the C-ABI shim (include/pathtracer.h).
+// pt_api.cpp — the core of the C-ABI shim (include/pathtracer.h); pt_context.h
+// has the context and names the files that hold the rest of the shim.
 //
 // Replaces the Vulkan resource/dispatch seam of src/Vulkan/VulkanRayTracer.cpp:
 // staging buffers + vkCmdCopyBuffer become hipMemcpyAsync, the descriptor set
@@ -7,55 +8,28 @@
 // an explicit pt_synchronize / pt_read_accum.  Scene preparation that the
 // device layout needs (threading the BVH, building triangle records) happens
 // here once per upload.
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
-#include <rccl/rccl.h>   // types only: the functions are resolved at run time (rccl_api)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "../../include/pathtracer.h"
-#include "pt_denoise.h"
-#include "pt_device.h"
-#include "pt_group.h"
+#include "pt_context.h"
 #include "pt_cull.h"
+#include "pt_denoise.h"
 #include "pt_isect.h"
 #include "pt_math.h"
-#include "scene/bvh.h"
-#include "scene/camera.h"
-#include "scene/light.h"
-#include "scene/obj_loader.h"
 #include "scene/small_sweep.h"
 #include "scene/threaded_bvh.h"
 #include "scene/wide_bvh.h"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define PT_HIP(call)                                                                   \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess) return fail(PT_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-void dev_free(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
+thread_local std::string g_err;   // pt_last_error(): its one definition (pt_fail_internal sets it)
 
 // The sweep walk's enabling bound (PT_OPT_SMALL_SWEEP -1, the default): a
 // scene that has a sweep table (at most pt::kSweepMaxLeaves triangles) is
@@ -76,430 +50,7 @@ std::vector<float4> as_float4(const std::vector<float>& f) {
   return v;
 }
 
-// ---- primary-ray bundle culling -----------------------------
-// Camera model of raytrace_comp.comp:430-460 in the orthonormal camera frame
-// (right, up, ez = dir/|dir|) centred on the camera position, with the
-// kernel's right = normalize(cross(dir, -up0)), up = normalize(cross(right, dir)):
-//   origin O = (ox, oy, 0),     |ox|, |oy| <= 0.02 * Rg        (aperture, :445-448)
-//   bdir ∝ (a, b, 1),  a = -ndcX*T*A/L, b = -ndcY*T/L          (:456-457)
-//   ndcX = ndcX0 + jx*0.5/W,    |jx| <= Rg                     (:451-454)
-//   F = 3*bdir,  dir ∝ F - O                                   (:459-460)
-// where Rg bounds every Box-Muller radius sqrt(-2 log u1) with u1 >= 1e-38
-// (:220): sqrt(-2 ln 1e-38) = 13.2286.  The ray reaches depth Z at slope
-//   X/Z = a + ox (1/Z - 1/Fz),  Fz = 3/sqrt(1+a^2+b^2),
-// so a point of depth Z > 0 with slope s is reachable from a pixel only if
-// |s - a| <= 0.02 Rg max|1/Z - 1/Fz| for some a of the pixel's jittered range.
-// Every object (root box corners, light rectangle corners — convex sets whose
-// slope hull is the hull of the corners' slopes) therefore maps to an NDC
-// rectangle of pixel origins that can reach it; outside all rectangles every
-// primary ray misses the root box (so traceRay returns no hit) and every light
-// (the pre-pass hits nothing), and the sample is exactly (0,0,0).  All maths
-// in double with margins far above the kernel's float rounding.
-// The derivation holds for any bound Rg on the two radii of a sample: with
-// ptd::kGaussR it covers every sample; with ptd::kCullTightR it covers the
-// samples whose two draws u1 are at least ptd::kCullTightU0 (pt_cull.h), which
-// the kernel checks per sample before it skips one (PT_OPT_CULL_TIGHT).
-using ptd::kGaussR;
-
-struct D3 { double x, y, z; };
-D3 d3(const float* f) { return {f[0], f[1], f[2]}; }
-D3 dsub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-D3 dadd(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-D3 dmul(D3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-double ddot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-D3 dcross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-double dlen(D3 a) { return sqrt(ddot(a, a)); }
-
-// Returns the rectangle count (>= 0) or -1 when no guarantee is derived.
-// Rg: the bound on the Box-Muller radii the rectangles hold for.
-int cull_rects(const float cam[16], int W, int H, const float* lo, const float* hi, const pt_area_light* lights,
-               int n_lights, float* rects, int max_rects, double Rg = kGaussR) {
-  if (W <= 0 || H <= 0 || n_lights < 0 || n_lights + 1 > max_rects || !(Rg >= 0.0 && Rg <= kGaussR)) return -1;
-  const D3 cpos = d3(cam), cdir = d3(cam + 4), cup = d3(cam + 8);
-  const double fov = cam[12];
-  const double L = dlen(cdir);
-  if (!(L > 1e-6 && L < 1e6) || !(fov > 0.01 && fov < 170.0)) return -1;
-  const D3 rx = dcross(cdir, dmul(cup, -1.0));
-  const double rl = dlen(rx);
-  if (!(rl > 1e-6 * L * dlen(cup))) return -1;
-  const D3 right = dmul(rx, 1.0 / rl);
-  const D3 ux = dcross(right, cdir);
-  const D3 up = dmul(ux, 1.0 / dlen(ux));
-  const D3 ez = dmul(cdir, 1.0 / L);
-  const double T = tan(fov * 0.5 * M_PI / 180.0), A = (double)W / (double)H;
-  const double jx = Rg * 0.5 / W, jy = Rg * 0.5 / H;                        // jitter in NDC
-  const double amax = (1.0 + jx) * T * A / L, bmax = (1.0 + jy) * T / L;
-  const double fz_min = 3.0 / sqrt(1.0 + amax * amax + bmax * bmax), fz_max = 3.0;
-  const double rho = 0.02 * Rg * 1.001;
-  int n = 0;
-  auto add_object = [&](const D3* pts, int np) -> bool {
-    double sx0 = INFINITY, sx1 = -INFINITY, sy0 = INFINITY, sy1 = -INFINITY, z0 = INFINITY, z1 = -INFINITY;
-    for (int i = 0; i < np; ++i) {
-      const D3 r = dsub(pts[i], cpos);
-      const double X = ddot(r, right), Y = ddot(r, up), Z = ddot(r, ez);
-      if (!(Z > 1e-4 * (1.0 + dlen(r)))) return false;   // at or behind the camera plane (or NaN)
-      sx0 = fmin(sx0, X / Z); sx1 = fmax(sx1, X / Z);
-      sy0 = fmin(sy0, Y / Z); sy1 = fmax(sy1, Y / Z);
-      z0 = fmin(z0, Z); z1 = fmax(z1, Z);
-    }
-    const double dd = fmax(fmax(fabs(1.0 / z0 - 1.0 / fz_min), fabs(1.0 / z0 - 1.0 / fz_max)),
-                           fmax(fabs(1.0 / z1 - 1.0 / fz_min), fabs(1.0 / z1 - 1.0 / fz_max)));
-    const double del = rho * dd;
-    // slope -> NDC (the maps are decreasing), then the jitter and a margin of
-    // ~1 pixel plus 1e-4 relative for the kernel's float evaluation
-    double x0 = -(sx1 + del) * L / (T * A), x1 = -(sx0 - del) * L / (T * A);
-    double y0 = -(sy1 + del) * L / T, y1 = -(sy0 - del) * L / T;
-    const double mx = 2.0 / W + 1e-4 * (1.0 + fabs(x0) + fabs(x1)), my = 2.0 / H + 1e-4 * (1.0 + fabs(y0) + fabs(y1));
-    x0 -= jx + mx; x1 += jx + mx; y0 -= jy + my; y1 += jy + my;
-    if (!(x0 == x0 && x1 == x1 && y0 == y0 && y1 == y1)) return false;
-    float* o = rects + 4 * n++;
-    o[0] = nextafterf((float)x0, -INFINITY); o[1] = nextafterf((float)x1, INFINITY);
-    o[2] = nextafterf((float)y0, -INFINITY); o[3] = nextafterf((float)y1, INFINITY);
-    return true;
-  };
-  // root box, dilated for the slab test's float rounding
-  {
-    double m = 0.0;
-    for (int k = 0; k < 3; ++k) m = fmax(m, fmax(fabs((double)lo[k]), fabs((double)hi[k])));
-    m = 1e-4 * m + 1e-6;
-    D3 pts[8];
-    for (int i = 0; i < 8; ++i)
-      pts[i] = {(i & 1 ? hi[0] + m : lo[0] - m), (i & 2 ? hi[1] + m : lo[1] - m), (i & 4 ? hi[2] + m : lo[2] - m)};
-    if (!add_object(pts, 8)) return -1;
-  }
-  // light rectangles: pos ± right*half0 ± up*half1 with the frame of
-  // setup_lights_kernel (:261-264), halves dilated
-  for (int l = 0; l < n_lights; ++l) {
-    const pt_area_light& li = lights[l];
-    const D3 nr = d3(li.normal);
-    const double nl = dlen(nr);
-    if (!(nl > 0.0)) return -1;
-    const D3 nn = dmul(nr, 1.0 / nl);
-    // the kernel picks the basis from its float normalize; near the switch
-    // point either basis may be taken, and the rectangle's orientation is
-    // then unknown — use its circumscribed square (both orientations inside)
-    const D3 basis = fabs(nn.y) < 0.999 ? D3{0, 1, 0} : D3{1, 0, 0};
-    const D3 lr = dmul(dcross(nn, basis), 1.0 / dlen(dcross(nn, basis)));
-    const D3 lu = dcross(lr, nn);
-    double h0 = fabs((double)li.size[0]) * 0.5, h1 = fabs((double)li.size[1]) * 0.5;
-    const D3 pos = d3(li.position);
-    const double pm = fmax(fmax(fabs(pos.x), fabs(pos.y)), fabs(pos.z));
-    if (fabs(fabs(nn.y) - 0.999) < 1e-4) h0 = h1 = fmax(h0, h1) * 1.41422;
-    h0 = h0 * 1.0001 + 1e-4 * pm + 1e-6;
-    h1 = h1 * 1.0001 + 1e-4 * pm + 1e-6;
-    if (!(h0 < 1e30 && h1 < 1e30)) return -1;
-    D3 pts[8];
-    for (int i = 0; i < 4; ++i) {
-      const D3 c = dadd(dadd(pos, dmul(lr, i & 1 ? h0 : -h0)), dmul(lu, i & 2 ? h1 : -h1));
-      // a thin slab around the plane covers the float plane-intersection error
-      const double th = 1e-4 * (pm + h0 + h1) + 1e-6;
-      pts[2 * i] = dadd(c, dmul(nn, th));
-      pts[2 * i + 1] = dadd(c, dmul(nn, -th));
-    }
-    if (!add_object(pts, 8)) return -1;
-  }
-  return n;
-}
-
 }  // namespace
-
-// Native multi-GPU step loop state (pt_dist_*): an RCCL communicator of its
-// own, a high-priority stream for the gathers, two render streams (frames
-// alternate), and double-buffered send / receive slots.
-constexpr int kDistStreams = 3;                 // render streams: frames k, k+1, .. in flight
-constexpr int kDistSets = 2 * kDistStreams;     // frame k uses buffer set k % (2 D) (see pt_dist_run)
-struct DistState {
-  ncclComm_t comm = nullptr;
-  int nranks = 0, rank = 0;
-  int comm_count = -1;   // ncclCommCount of the communicator (-1: not reported by the library)
-  hipStream_t comm_stream = nullptr;
-  hipStream_t streams[kDistStreams] = {};
-  hipStream_t own[kDistStreams + 1] = {};   // created here: render streams, then the gather stream
-                                            // (pt_dist_set_streams may override)
-  hipEvent_t render_done[kDistSets] = {}, gather_done[kDistSets] = {};
-  hipEvent_t entry[kDistStreams + 1] = {};  // pt_dist_run's entry barrier: each stream's last work
-  float* send[kDistStreams] = {};        // non-root ranks: frame k's live items (k % D)
-  float* recv[kDistSets] = {};           // root: one slot per rank of the partition; slot 0 its own
-  float* ingest = nullptr;               // emulated root: stand-in for the other ranks' slots
-  size_t slot_floats = 0, cap_floats = 0;
-  std::vector<float> layout_key;         // frame_key of the layout the slots were sized for
-  // root: frame buffers that hold a whole assembled frame of a layout (its
-  // culled items' constant (0,0,0,1) included); later frames of that layout
-  // rebuild only their live items there (the culled bytes are the same)
-  std::vector<std::pair<const void*, std::vector<float>>> assembled;
-  bool ready = false;
-  bool caller_streams = false;           // pt_dist_set_streams gave render streams (then at most 2)
-};
-
-struct pt_context {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  float4* d_nodes = nullptr;        // threaded, implied internal nodes collapsed (fast kernel)
-  int n_nodes = 0;
-  float4* d_nodes_full = nullptr;   // threaded, every reference node (stats mode)
-  float4* d_sweep = nullptr;        // the sweep table of a tiny scene (scene/small_sweep.h), or null
-  float4* d_sweep_plain = nullptr;  // ... and the same table without hull codes (PT_OPT_SWEEP_HULL 0)
-  int sweep_boxes = 0, sweep_leaves = 0;
-  int sweep_hull = 0;               // boxes of the table with a hull code
-  // culled wide walk (wide_walk.h): nodes, triangle records by rank, rank ->
-  // slot, per-lane stack overflow areas (grown on demand)
-  float4* d_wide = nullptr;
-  float4* d_wide_q = nullptr;        // the same wide nodes in the 64-B layout
-  float4* d_wide_leafbox = nullptr;  // the reference's leaf boxes by rank (64-B walk)
-  float4* d_wide_tris = nullptr;
-  int* d_wide_rank_of = nullptr;
-  int2* d_wide_ovf = nullptr;
-  long long wide_ovf_lanes = 0;
-  int wide_ovf_stack = 0;   // the stack bound d_wide_ovf was sized for
-  int n_wide = 0, wide_stack = 0;
-  std::string wide_reason = "no scene";
-  int opt_wide = 1;           // PT_OPT_WIDE
-  int opt_wf_fuse = 1;        // PT_OPT_WF_FUSE
-  int opt_wf_tail = -1;       // PT_OPT_WF_TAIL (-1 auto)
-  int opt_wf_grid = 100;      // PT_OPT_WF_GRID (percent of a full-occupancy traversal grid)
-  int opt_wf_refill = 0;      // PT_OPT_WF_REFILL (0 auto)
-  int opt_wide_node = 64;     // PT_OPT_WIDE_NODE
-  int n_nodes_full = 0;
-  float4* d_tris = nullptr;
-  int n_tris = 0;
-  ptd::LightRec* d_lights = nullptr;
-  ptd::LightDev* d_lights_dev = nullptr;
-  int n_lights = 0;
-  float4* d_accum = nullptr;
-  bool own_accum = false;
-  int width = 0, height = 0;
-  unsigned long long* d_stats = nullptr;
-  float cam[16] = {0};
-  bool has_camera = false;
-  bool has_scene = false;
-  pt_params params{4, 3};
-  int nranks = 1, rank = 0;
-  std::vector<int> slots{1};    // partition slots per rank (pt_set_partition_slots)
-  std::vector<ptd::Part> parts;  // every rank's share, derived from slots (ensure_parts)
-  bool parts_valid = false;     // parts match slots
-  bool parts_synced = false;    // d_parts holds parts
-  int* d_parts = nullptr;       // every rank's slot positions, kMaxSlots ints each (rank_tile)
-  size_t parts_cap = 0;
-  std::vector<int> parts_key;
-  bool stats_mode = false;
-  int opt_scene_lds = 1;   // PT_OPT_SCENE_IN_LDS: 0 never, 1 auto, 2 always
-  int opt_sample_lanes = 0;   // PT_OPT_SAMPLE_LANES: 0 auto, else 1/2/4/8
-  int opt_fresh = 0;          // PT_OPT_FRESH_BATCH0
-  int opt_item_order = -1;    // PT_OPT_ITEM_ORDER (-1 auto)
-  int opt_mixed = -1;         // PT_OPT_MIXED_LANES: -1 auto, 0 off, k = whole tiles for k % of the resident slots
-  int opt_kernel = 0;         // PT_OPT_KERNEL: 0 auto, 1 path-recursive, 3 wavefront
-  int opt_cull = 1;           // PT_OPT_PRIMARY_CULL
-  int opt_cull_tight = 1;     // PT_OPT_CULL_TIGHT
-  int opt_wf_paths = 0;       // PT_OPT_WF_PATHS (0 = 2^27)
-  long long wf_fail = 0;      // wavefront paths whose allocation failed (0: none)
-  int opt_count = 0;          // PT_OPT_COUNT_TRACED
-  int opt_small_sweep = -1;   // PT_OPT_SMALL_SWEEP: -1 auto (kSweepAutoBoxes), 0 off, 1 whenever the scene has a table
-  int opt_sweep_hull = 1;     // PT_OPT_SWEEP_HULL
-  int opt_exit_skip = 1;      // PT_OPT_EXIT_SKIP
-  int opt_wide_build = 1;     // PT_OPT_WIDE_BUILD (pt::WideBuild; read at upload)
-  int opt_wf_streams = 1;     // PT_OPT_WF_STREAMS (2 measured slower: 10M cloud +9 %, sphere -0.8 %)
-  hipStream_t wf_stream2 = nullptr;           // the wavefront pipeline's second half (created on first use)
-  hipEvent_t wf_fork = nullptr, wf_join = nullptr;
-  int last_kernel = 0;        // kernel of the last render (1 recursive, 3 wavefront)
-  // compact-launch item lists (live items, then culled ones), rebuilt when
-  // the frame, partition, sample lanes or cull rectangles change
-  int* d_items = nullptr;
-  size_t items_cap = 0;
-  int n_live_items = 0, n_culled_items = 0;   // launched live items (mixed lanes: whole tiles + parts)
-  bool items_mixed = false;                    // the live origins carry per-item lane counts
-  std::vector<int> block_lanes;                // lanes per 16x16 block in the current item lists (0: not launched)
-  // measured mixed-lane schedule (mix_feedback)
-  unsigned* d_cost = nullptr;                  // per 16x4 part: summed wave durations of a measuring launch
-  unsigned* h_cost = nullptr;                  // pinned copy
-  size_t cost_n = 0;                           // blocks allocated
-  hipEvent_t cost_ev = nullptr;
-  bool cost_pending = false, cost_stale = false, cost_measure = false, cost_ready = false;
-  int cost_stable = 0, cost_frames = 0, cost_gen = 0;
-  std::vector<float> cost_key, cost_scratch;
-  std::vector<int> cost_lanes;                 // block_lanes of the measuring launch
-  std::vector<double> block_cost;              // per 16x4 part, at one lane per pixel (averaged)
-  int scene_serial = 0;                        // bumped by scene and light uploads
-  int last_mix = 0;                            // pt_mixed_info: the last launch's schedule
-  // What the accumulation buffer's culled items hold (render_impl): 0 not
-  // known, 1 finite (+-0 after a clear), 2 (0,0,0,1) in every culled item of
-  // the item layout culled_key in buffer culled_buf.  Only the library's own
-  // calls are assumed to write the buffer.
-  int culled_state = 0;
-  std::vector<float> culled_key;
-  const void* culled_buf = nullptr;
-  long long render_slots = -1;                 // resident LDS render workgroups (mixed lanes' budget)
-  size_t render_slots_lds = 0;                 // ... at this many bytes of staged scene
-  bool render_slots_sweep = false;             // ... of the sweep-walk kernel (false: the threaded walk's)
-  size_t culled_org_off = 0;   // h_items / d_items: where the culled items' first pixels start
-  size_t live_org_off = 0;     // ... and the live items' ones
-  std::vector<int> h_items;
-  std::vector<float> items_key;
-  ptd::RenderParams last{};     // configuration of the last pt_render
-  bool last_valid = false;
-  // sparse exchange: this rank's live items, and all ranks' (root)
-  int* d_pack_items = nullptr;
-  size_t pack_cap = 0;
-  int n_pack_items = 0;
-  std::vector<float> pack_key;
-  int* d_unpack = nullptr;      // per entry: rank, x0, y0, slot (-1 = culled)
-  size_t unpack_cap = 0;
-  int n_unpack = 0;
-  int* d_unpack_live = nullptr;   // the same table without the culled items' entries
-  size_t unpack_live_cap = 0;
-  int n_unpack_live = 0;
-  std::vector<float> unpack_key;
-  std::vector<float> packed_key;   // frame parameters of the last pt_render_packed
-  std::vector<float> key_scratch, items_scratch;   // per-launch keys, built without reallocating
-  float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};   // root AABB of the uploaded tree
-  std::vector<pt_area_light> lights_host;
-  bool exit_normals = false;   // some triangle's stored normal is axis-pure (pt_isect.h exit_normal)
-  // wavefront pipeline buffers (PT_OPT_KERNEL 3), grown on demand
-  ptd::WfBuffers wf{};
-  void* wf_block = nullptr;
-  // progressive loop (VulkanRayTracer::mainLoop, :717-865)
-  float prog_cam[16] = {0};
-  bool prog_has_cam = false;
-  uint32_t prog_batch = 0;
-  // double-buffered asynchronous readback: device snapshot -> pinned host
-  struct Readback {
-    float4* dev = nullptr;
-    void* host = nullptr;
-    size_t bytes = 0;
-    hipEvent_t snap = nullptr, done = nullptr;
-    int ticket = 0;        // 0 = free
-    int w = 0, h = 0;
-  } rb[2];
-  hipStream_t copy_stream = nullptr;
-  // Launches that write context-owned buffers (the accumulation buffer, the
-  // wavefront path buffers) are ordered across streams: the next such launch
-  // waits for the last one when it runs on another stream (order_shared).
-  hipEvent_t shared_ev = nullptr;
-  hipStream_t shared_stream = nullptr;
-  // Every stream this context has enqueued work on that reads its buffers
-  // (node/triangle arrays, item tables, accumulation and wavefront buffers),
-  // with an event recorded after the last such work (note_use).  A host-side
-  // rebuild of those buffers waits on these events only (quiesce), never on
-  // the whole device, so it does not wait on another component's RCCL or
-  // torch work sharing the GPU.
-  struct Use {
-    hipStream_t stream;
-    hipEvent_t ev;
-  };
-  std::vector<Use> uses;
-  int rb_next_ticket = 1;
-  bool timed = false;
-  // ring of event pairs, one per render launch since pt_reset_launch_times
-  static constexpr int kRing = 512;
-  hipEvent_t ring[kRing][2] = {};
-  int ring_n = 0;
-  int last_slot = 0;          // ring slot of the newest launch (pt_last_launch_ms)
-  int opt_timing = 0;         // PT_OPT_LAUNCH_TIMING: event pair on every k-th launch, 0 = none (default:
-                              // a pair costs the one-stream frame ~10 us, profiles/r06a)
-  long long launch_n = 0;     // render launches since pt_reset_launch_times
-  long long ring_launch[kRing] = {};   // launch number of each recorded pair
-  // first-hit guide image and a-trous filter (pt_render_guide, pt_denoise):
-  // library-owned W x H float4 images, grown on demand
-  float4* d_guide = nullptr;
-  size_t guide_cap = 0;                // pixels d_guide holds
-  bool guide_valid = false;            // d_guide is the guide of the current scene, camera and size
-  float4* d_dn_scratch[2] = {nullptr, nullptr};   // the passes' ping-pong images
-  size_t dn_scratch_cap[2] = {0, 0};
-  float4* d_denoised = nullptr;        // pt_denoise's destination when the caller gives none
-  size_t denoised_cap = 0;
-  int denoised_w = 0, denoised_h = 0;  // size of the image d_denoised holds (0: none yet)
-  int opt_denoise_lds = 1;             // PT_OPT_DENOISE_LDS
-  // per-pixel luminance moments (PT_OPT_MOMENTS) and pt_denoise_var's variance planes:
-  int opt_moments = 0;
-  float2* d_moments = nullptr;         // W x H {m1, m2}
-  size_t moments_cap = 0;              // pixels d_moments holds
-  bool moments_valid = false;          // d_moments holds batches 0..moments_n-1 of the current frame
-  uint32_t moments_n = 0;
-  float* d_var[2] = {nullptr, nullptr};
-  size_t var_cap[2] = {0, 0};
-  // the seed base (PT_OPT_SEED_BASE) and temporal accumulation (pt_temporal_advance)
-  uint32_t opt_seed_base = 0;
-  uint32_t seed_extra = 0;             // inside pt_temporal_advance: the samples rendered since the last reset
-  struct TemporalSet {                 // one of the two library-owned result sets
-    float4* color = nullptr;
-    float2* moments = nullptr;
-    float* length = nullptr;
-    float* variance = nullptr;
-    size_t cap = 0;                    // pixels each image holds
-  } tset[2];
-  int t_cur = 0;                       // the set the last pt_temporal_advance wrote
-  uint32_t t_frames = 0, t_samples = 0;   // since the last reset; t_frames 0: no history
-  float t_cam[16] = {0};               // the last frame's camera
-  int t_w = 0, t_h = 0;                // ... and size
-  // the last frame's guide: d_guide while no later pt_render_guide has run (guide_serial ==
-  // t_guide_serial), else d_guide_prev, where that pt_render_guide put it aside
-  float4* d_guide_prev = nullptr;
-  size_t guide_prev_cap = 0;
-  unsigned long long guide_serial = 0, t_guide_serial = 0;
-  bool t_guide_aside = false;
-  float* d_spatial_var = nullptr;      // pt_temporal_denoise_spatial's variance plane
-  size_t spatial_var_cap = 0;
-  DistState* dist = nullptr;           // pt_dist_init
-  pt_group* group = nullptr;           // pt_create_multi: every call goes to the group (pt_group.cpp)
-  bool in_dist = false;                // inside pt_dist_run: it records the use events itself
-};
-
-struct pt_scene {
-  pt::ObjScene obj;
-  std::vector<uint32_t> bvh_indices;
-  std::vector<pt::BVHNode> nodes;
-  uint32_t flags = 0;
-};
-
-// The temporal history is forgotten (pt_temporal_reset; a new scene, lights, params, frame size or
-// bound buffer): the next pt_temporal_advance runs without history and seeds from the seed base again.
-static void temporal_forget(pt_context* c) {
-  c->t_frames = 0;
-  c->t_samples = 0;
-  c->t_guide_aside = false;
-}
-
-// Before a launch that writes context-owned buffers: wait for the previous
-// such launch if it ran on another stream.
-static int order_shared(pt_context* c) {
-  if (c->shared_stream && c->shared_stream != c->stream) PT_HIP(hipStreamWaitEvent(c->stream, c->shared_ev, 0));
-  return PT_OK;
-}
-// After enqueueing work that reads or writes context-owned buffers on
-// c->stream: record it in that stream's use event (a context rarely sees more
-// than a handful of streams; past kMaxUses the oldest entry is waited for and
-// dropped).
-constexpr size_t kMaxUses = 16;
-static int note_use(pt_context* c) {
-  for (auto& u : c->uses)
-    if (u.stream == c->stream) {
-      PT_HIP(hipEventRecord(u.ev, c->stream));
-      return PT_OK;
-    }
-  if (c->uses.size() >= kMaxUses) {
-    PT_HIP(hipEventSynchronize(c->uses.front().ev));
-    PT_HIP(hipEventDestroy(c->uses.front().ev));
-    c->uses.erase(c->uses.begin());
-  }
-  pt_context::Use u{c->stream, nullptr};
-  PT_HIP(hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
-  c->uses.push_back(u);
-  PT_HIP(hipEventRecord(u.ev, c->stream));
-  return PT_OK;
-}
-// After it (or after the last launch that reads those buffers back).
-static int mark_shared(pt_context* c) {
-  PT_HIP(hipEventRecord(c->shared_ev, c->stream));
-  c->shared_stream = c->stream;
-  return note_use(c);
-}
-// Before buffers that launches on any stream may still read are freed or
-// overwritten from the host (list rebuilds, reallocation): wait for this
-// context's own work on every stream it used -- not for the whole device.
-static int quiesce(pt_context* c) {
-  for (auto& u : c->uses) PT_HIP(hipEventSynchronize(u.ev));
-  return PT_OK;
-}
 
 // Pixels of columns [g0, g0+n) (or rows) whose NDC origin (the kernel's
 // ndc = 2*p/res - 1) lies in [lo, hi].
@@ -518,46 +69,39 @@ static int pixels_in(int g0, int n, int res, float lo, float hi) {
 // rectangle (cull[0]: full paths, ~9 rays per sample on box.obj) x 8 + pixels
 // inside a light rectangle (pre-pass only).  Output does not depend on the
 // order; every consumer (launch, pack, unpack table) uses this one list.
-// Rank r's share of the slotted partition (pt_device.h Part): the period's
+// Every rank's share of the slotted partition (pt_device.h Part): the period's
 // slots ordered by (k + 1/2) / slots[rank] for each rank's k-th slot (ties by
 // rank), so every rank's slots are spread evenly over the period.
-static ptd::Part part_of_slots(const std::vector<int>& slots, int r) {
+static std::vector<ptd::Part> parts_of_slots(const std::vector<int>& slots) {
   std::vector<std::pair<double, int>> seq;
   for (int i = 0; i < (int)slots.size(); ++i)
     for (int k = 0; k < slots[i]; ++k) seq.push_back({(k + 0.5) / slots[i], i});
   std::stable_sort(seq.begin(), seq.end());
-  ptd::Part pt{};
-  pt.m = (int)seq.size();
-  for (int v = 0; v < pt.m; ++v)
-    if (seq[v].second == r) pt.pos[pt.cnt++] = v;
-  return pt;
-}
-// Every rank's share, computed once per partition change (one sort of the
-// period for all ranks) -- not per launch: at 8 ranks the per-call derivation
-// cost ~10 us of host time per render launch.
-static void ensure_parts(pt_context* c) {
-  if (c->parts_valid && c->parts.size() == c->slots.size()) return;
-  std::vector<std::pair<double, int>> seq;
-  for (int i = 0; i < (int)c->slots.size(); ++i)
-    for (int k = 0; k < c->slots[i]; ++k) seq.push_back({(k + 0.5) / c->slots[i], i});
-  std::stable_sort(seq.begin(), seq.end());
-  c->parts.assign(c->slots.size(), ptd::Part{});
-  for (auto& pt : c->parts) pt.m = (int)seq.size();
+  std::vector<ptd::Part> parts(slots.size(), ptd::Part{});
+  for (auto& pt : parts) pt.m = (int)seq.size();
   for (int v = 0; v < (int)seq.size(); ++v) {
-    ptd::Part& pt = c->parts[seq[v].second];
+    ptd::Part& pt = parts[seq[v].second];
     pt.pos[pt.cnt++] = v;
   }
+  return parts;
+}
+// Computed once per partition change (one sort of the period for all ranks)
+// -- not per launch: at 8 ranks the per-call derivation cost ~10 us of host
+// time per render launch.
+static void ensure_parts(pt_context* c) {
+  if (c->parts_valid && c->parts.size() == c->slots.size()) return;
+  c->parts = parts_of_slots(c->slots);
   c->parts_valid = true;
   c->parts_synced = false;
 }
-static const ptd::Part& part_of(pt_context* c, int r) {
+const ptd::Part& part_of(pt_context* c, int r) {
   ensure_parts(c);
   return c->parts[r];
 }
 
 // Upload every rank's slot positions when the partition changed; the device
 // copy of rank r's starts at d_parts + r * kMaxSlots.
-static int upload_ints_(const std::vector<int>& h, int** d, size_t* cap) {
+static int upload_ints(const std::vector<int>& h, int** d, size_t* cap) {
   if (h.size() > *cap) {
     dev_free(*d);
     *cap = 0;
@@ -580,7 +124,7 @@ static int sync_parts(pt_context* c) {
     return PT_OK;
   }
   { const int rc_ = quiesce(c); if (rc_) return rc_; }
-  const int rc = upload_ints_(all, &c->d_parts, &c->parts_cap);
+  const int rc = upload_ints(all, &c->d_parts, &c->parts_cap);
   if (rc) return rc;
   c->parts_key = all;
   c->parts_synced = true;
@@ -593,8 +137,8 @@ static int sync_parts(pt_context* c) {
 // kernel, the rest to fill_culled_kernel.  A culled workgroup still costs a
 // workgroup launch (a fully culled 1080p frame took 0.10 ms at 4 sample
 // lanes), so only live ones are launched.
-static void item_lists(const ptd::RenderParams& p, const ptd::Part& part, std::vector<int>* live,
-                       std::vector<int>* culled) {
+void item_lists(const ptd::RenderParams& p, const ptd::Part& part, std::vector<int>* live,
+                std::vector<int>* culled) {
   const int W = p.width, H = p.height, spl = p.spl, rows = 16 / spl;
   const int tiles = ptd::part_count(part, p.blocks_total);
   live->clear();
@@ -859,14 +403,8 @@ static int compact_items(pt_context* c, ptd::RenderParams* p, const MixPlan* mix
     } else {
       origins(live);
     }
-    if (c->h_items.size() > c->items_cap) {
-      dev_free(c->d_items);
-      c->items_cap = 0;
-      PT_HIP(hipMalloc((void**)&c->d_items, c->h_items.size() * sizeof(int)));
-      c->items_cap = c->h_items.size();
-    }
-    if (!c->h_items.empty())
-      PT_HIP(hipMemcpy(c->d_items, c->h_items.data(), c->h_items.size() * sizeof(int), hipMemcpyHostToDevice));
+    const int ru = upload_ints(c->h_items, &c->d_items, &c->items_cap);
+    if (ru) return ru;
     c->n_live_items = n_launch;
     c->n_culled_items = (int)culled.size();
     c->items_mixed = mix && (mix->cost || (p->spl > 1 && mix->budget > 0));
@@ -888,7 +426,6 @@ static int compact_items(pt_context* c, ptd::RenderParams* p, const MixPlan* mix
   return PT_OK;
 }
 
-namespace {
 // The frame parameters an item layout depends on, into *key (its capacity is
 // kept between launches: no allocation per launch).
 void frame_key(const pt_context* c, const ptd::RenderParams& p, std::vector<float>* key) {
@@ -897,25 +434,7 @@ void frame_key(const pt_context* c, const ptd::RenderParams& p, std::vector<floa
   for (int r = 0; r < p.n_cull; ++r) key->insert(key->end(), p.cull[r], p.cull[r] + 4);
   for (int sl : c->slots) key->push_back((float)sl);   // every rank's share (the assembly table)
 }
-int upload_ints(const std::vector<int>& h, int** d, size_t* cap) {
-  if (h.size() > *cap) {
-    dev_free(*d);
-    *cap = 0;
-    PT_HIP(hipMalloc((void**)d, h.size() * sizeof(int)));
-    *cap = h.size();
-  }
-  if (!h.empty()) PT_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
-  return PT_OK;
-}
-// Wavefront buffers for `paths` paths in one allocation.  Up to 2^27 paths
-// (416 B each: 56 GB of the 288-GB HBM) are kept per launch, so config 4's
-// 4K x 16 spp frame (133M paths) runs as one chunk: every ray round has 8x
-// the rays of a 2^24 chunk, and each round's drain (its longest walk) is paid
-// 65 times per frame instead of 520 -- 767 -> 560 ms (2^26: 591).  More
-// batches run in chunks of that size; an allocation that fails halves it.
-constexpr long long kWfMaxPaths = 1ll << 27;
-constexpr int kWfAutoTris = 32768;
-constexpr int kWfWideAutoTris = 16384;   // ... with the culled wide walk (render_impl)
+
 // The root's assembly table for frames rendered with params p: per rank its
 // live items {rank, x0, y0, slot} and its culled items {rank, x0, y0, -1},
 // (x0, y0) the item's first pixel.
@@ -947,7 +466,16 @@ int unpack_table(pt_context* c, const ptd::RenderParams& p, const std::vector<fl
   c->unpack_key = key;
   return PT_OK;
 }
-int wf_reserve(pt_context* c, long long pixels, uint32_t batches, long long* chunk_paths) {
+// Wavefront buffers for `paths` paths in one allocation.  Up to 2^27 paths
+// (416 B each: 56 GB of the 288-GB HBM) are kept per launch, so config 4's
+// 4K x 16 spp frame (133M paths) runs as one chunk: every ray round has 8x
+// the rays of a 2^24 chunk, and each round's drain (its longest walk) is paid
+// 65 times per frame instead of 520 -- 767 -> 560 ms (2^26: 591).  More
+// batches run in chunks of that size; an allocation that fails halves it.
+constexpr long long kWfMaxPaths = 1ll << 27;
+constexpr int kWfAutoTris = 32768;
+constexpr int kWfWideAutoTris = 16384;   // ... with the culled wide walk (render_impl)
+static int wf_reserve(pt_context* c, long long pixels, uint32_t batches, long long* chunk_paths) {
   const long long limit = c->opt_wf_paths > 0 ? c->opt_wf_paths : kWfMaxPaths;
   long long want = std::max(pixels, std::min(pixels * (long long)batches, limit));
   if (c->wf_fail > 0) want = std::max(pixels, std::min(want, c->wf_fail / 2));   // an earlier allocation failed
@@ -984,14 +512,7 @@ int wf_reserve(pt_context* c, long long pixels, uint32_t batches, long long* chu
   c->wf.cap = want;
   return PT_OK;
 }
-}  // namespace
 
-extern "C" int pt_items_pack(pt_context* c, void* dst);
-extern "C" int pt_items_unpack_all(pt_context* c, const void* src, size_t slot_floats, void* frame);
-
-namespace {
-// pt_render / pt_render_packed (pack_out != null: fresh frame, live items
-// written to pack_out in the pt_items_pack layout).
 // The camera block and the frame main() derives from it (:447-448, :457),
 // computed on the host with pt_math.h.
 void camera_params(const float cam[16], ptd::RenderParams* p) {
@@ -1036,24 +557,10 @@ int wide_params(pt_context* c, ptd::RenderParams* p) {
   return PT_OK;
 }
 
-struct Assembly {   // pt_render_packed's optional gathered frame to assemble
-  const void* src = nullptr;
-  size_t slot_floats = 0;
-  void* frame = nullptr;
-};
-// The parameters of a path-recursive launch as render_impl made it, so that
-// pt_dist_run can launch the next frames of a run (same scene, camera,
-// options and item layout; only the packed output and the frame to assemble
-// change) without rebuilding them: the host cost of a frame is then the
-// launch and its events (relaunch).
-struct Launched {
-  ptd::RenderParams p;
-  bool lds = false, cnt = false, valid = false;
-};
 // Whether the context's launches walk the scene's sweep table (PT_OPT_SMALL_SWEEP): the
 // option admits the scene, and the launch is the plain LDS-staged path-recursive kernel
 // (a scene with a table always fits in LDS; the auto kernel choice is path-recursive for it).
-bool sweep_in_force(const pt_context* c) {
+static bool sweep_in_force(const pt_context* c) {
   const bool wanted =
       c->d_sweep && (c->opt_small_sweep == 1 || (c->opt_small_sweep < 0 && c->sweep_boxes <= kSweepAutoBoxes));
   return wanted && c->opt_scene_lds != 0 && c->opt_kernel != 3 && !c->stats_mode && c->opt_count == 0;
@@ -1075,8 +582,10 @@ int relaunch(pt_context* c, const ptd::RenderParams& p, bool lds, bool cnt) {
   c->launch_n++;
   return PT_OK;
 }
-int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4* pack_out,
-                const Assembly& as = Assembly(), Launched* launched = nullptr) {
+// pt_render / pt_render_packed (pack_out != null: fresh frame, live items
+// written to pack_out in the pt_items_pack layout).
+int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4* pack_out, const Assembly& as,
+                Launched* launched) {
   if (!c) return fail(PT_ERR_INVALID, "null context");
   if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
   if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
@@ -1092,13 +601,10 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
     const size_t n = (size_t)c->width * c->height;
     if (n_batches > 0) {
       if (!c->d_moments || c->moments_cap < n) {
-        { const int rc_ = quiesce(c); if (rc_) return rc_; }
-        dev_free(c->d_moments);
-        c->moments_cap = 0;
         c->moments_valid = false;
         PT_HIP(hipSetDevice(c->device));
-        PT_HIP(hipMalloc((void**)&c->d_moments, n * sizeof(float2)));
-        c->moments_cap = n;
+        const int rg = grow_dev(c, &c->d_moments, &c->moments_cap, n);
+        if (rg) return rg;
         PT_HIP(hipMemsetAsync(c->d_moments, 0, n * sizeof(float2), c->stream));
       }
       fold_moments = true;
@@ -1108,24 +614,13 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   } else if (n_batches > 0 && !pack_out) {
     c->moments_valid = false;   // the accumulator moves on without them
   }
-  ptd::RenderParams p;
+  ptd::RenderParams p{};   // what is not set below is 0 or null: no wide walk, item list, packed output, assembly
   p.moments = fold_moments ? c->d_moments : nullptr;
-  p.wide = nullptr;
-  p.wide_tris = nullptr;
-  p.wide_rank_of = nullptr;
-  p.wide_ovf = nullptr;
-  p.wide_ovf_lanes = 0;
-  p.wide_stack = 0;
-  p.wide_handback = 0;
-  p.wf_fuse = 0;
-  p.wf_tail = 0;
   p.wf_grid = c->opt_wf_grid;
   // PT_OPT_WF_REFILL auto: 16 idle lanes on a full grid, 8 on a split one
   // (more rays per lane per round; the refill's cost is shared by fewer
   // concurrent waves: profiles/r05i)
   p.wide_refill = c->opt_wf_refill > 0 ? c->opt_wf_refill : (c->opt_wf_grid < 100 ? 8 : 16);
-  p.wide_qn = 0;
-  p.wide_leafbox = nullptr;
   p.nodes = c->stats_mode ? c->d_nodes_full : c->d_nodes;
   p.tris = c->d_tris;
   p.hit_tris = c->d_tris;
@@ -1164,7 +659,6 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   p.part_pos = c->d_parts + (size_t)c->rank * ptd::kMaxSlots;
   p.n_tiles = ptd::part_count(hpart, p.blocks_total);
   p.fresh = pack_out ? 1 : c->opt_fresh;
-  p.pack_out = nullptr;
   if (c->opt_sample_lanes) {
     p.spl = c->opt_sample_lanes;
   } else {
@@ -1233,19 +727,15 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   p.item_order = c->opt_item_order >= 0 ? c->opt_item_order : (!wf && c->nranks == 1 ? 0 : 1);
   p.n_cull = -1;
   c->last_mix = 0;
-  p.items = nullptr;
-  p.culled_org = nullptr;
-  p.items_org = nullptr;
-  p.n_items = p.n_culled_items = 0;
   if (c->opt_cull && !c->stats_mode)
-    p.n_cull = cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
+    p.n_cull = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
                           c->n_lights, &p.cull[0][0], ptd::kMaxCullRects);
   // the tight rectangles (PT_OPT_CULL_TIGHT): the kernel's per-sample skip; every host-side use of the
   // rectangles (items, fills, partitions) keeps the loose ones.  Off (-1, "never skip") unless both derive
   p.n_cull_tight = -1;
   p.cull_u0 = ptd::kCullTightU0;
   if (p.n_cull >= 0 && c->opt_cull_tight) {
-    p.n_cull_tight = cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
+    p.n_cull_tight = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
                                 c->n_lights, &p.cull_tight[0][0], ptd::kMaxCullRects, ptd::kCullTightR);
     if (p.n_cull_tight != p.n_cull) p.n_cull_tight = -1;
   }
@@ -1301,11 +791,6 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   }
   c->last_kernel = wf ? 3 : 1;
   c->last_valid = true;
-  p.unpack_src = nullptr;
-  p.unpack_frame = nullptr;
-  p.unpack_table = nullptr;
-  p.n_unpack = 0;
-  p.unpack_slot_f4 = 0;
   if (pack_out && as.frame == (void*)c->d_accum) c->culled_state = 0;   // the assembly writes this buffer
   if (pack_out) {
     frame_key(c, p, &c->key_scratch);
@@ -1433,9 +918,32 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   return PT_OK;
 }
 
-}  // namespace
+// The device arrays of the uploaded scene: pt_upload_scene replaces them,
+// pt_destroy frees them.
+static void scene_release(pt_context* c) {
+  dev_free(c->d_nodes);
+  dev_free(c->d_nodes_full);
+  dev_free(c->d_sweep);
+  dev_free(c->d_sweep_plain);
+  c->sweep_boxes = c->sweep_leaves = c->sweep_hull = 0;
+  dev_free(c->d_wide);
+  dev_free(c->d_wide_q);
+  dev_free(c->d_wide_leafbox);
+  dev_free(c->d_wide_tris);
+  dev_free(c->d_wide_rank_of);
+  dev_free(c->d_tris);
+  // the wide walk's overflow area is sized by the scene's stack bound: a
+  // deeper tree needs a new one (it is reallocated at the next wide launch)
+  dev_free(c->d_wide_ovf);
+  c->wide_ovf_lanes = 0;
+  c->wide_ovf_stack = 0;
+  c->n_wide = 0;
+}
 
-int pt_fail_internal(int code, const std::string& msg) { return fail(code, msg); }
+int pt_fail_internal(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
 void pt_note_accum_written(pt_context* c, bool finite) {
   if (!c) return;
   c->culled_state = finite ? 1 : 0;
@@ -1478,8 +986,6 @@ int pt_create(int device_ordinal, pt_context** out) {
   *out = c;
   return PT_OK;
 }
-
-int pt_dist_finalize(pt_context* c);
 
 int pt_create_multi(const int* device_ordinals, int n, pt_context** out) {
   if (!out || !device_ordinals) return fail(PT_ERR_INVALID, "null argument");
@@ -1530,18 +1036,7 @@ int pt_destroy(pt_context* c) {
   (void)quiesce(c);
   for (auto& u : c->uses) (void)hipEventDestroy(u.ev);
   c->uses.clear();
-  dev_free(c->d_nodes);
-  dev_free(c->d_nodes_full);
-  dev_free(c->d_sweep);
-  dev_free(c->d_sweep_plain);
-  c->sweep_boxes = c->sweep_leaves = c->sweep_hull = 0;
-  dev_free(c->d_wide);
-  dev_free(c->d_wide_q);
-  dev_free(c->d_wide_leafbox);
-  dev_free(c->d_wide_tris);
-  dev_free(c->d_wide_rank_of);
-  dev_free(c->d_wide_ovf);
-  dev_free(c->d_tris);
+  scene_release(c);
   dev_free(c->d_lights);
   dev_free(c->d_lights_dev);
   if (c->own_accum) dev_free(c->d_accum);
@@ -1554,21 +1049,8 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_unpack);
   dev_free(c->d_unpack_live);
   dev_free(c->wf_block);
-  dev_free(c->d_guide);
-  dev_free(c->d_dn_scratch[0]);
-  dev_free(c->d_dn_scratch[1]);
-  dev_free(c->d_denoised);
   dev_free(c->d_moments);
-  dev_free(c->d_var[0]);
-  dev_free(c->d_var[1]);
-  dev_free(c->d_guide_prev);
-  dev_free(c->d_spatial_var);
-  for (auto& s : c->tset) {
-    dev_free(s.color);
-    dev_free(s.moments);
-    dev_free(s.length);
-    dev_free(s.variance);
-  }
+  post_release(c);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1601,11 +1083,7 @@ int pt_synchronize(pt_context* c) {
   if (!c) return fail(PT_ERR_INVALID, "null context");
   PT_HIP(hipSetDevice(c->device));
   PT_HIP(hipStreamSynchronize(c->stream));
-  if (c->dist) {   // the native step loop's streams
-    for (hipStream_t s : {c->dist->streams[0], c->dist->streams[1], c->dist->comm_stream})
-      if (s) PT_HIP(hipStreamSynchronize(s));
-  }
-  return PT_OK;
+  return c->dist ? dist_synchronize(c) : PT_OK;   // the native step loop's streams
 }
 
 int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats, const uint32_t* indices,
@@ -1654,23 +1132,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   float hi[3] = {threaded[1].x, threaded[1].y, threaded[1].z};
   PT_HIP(hipSetDevice(c->device));
   { const int rc_ = quiesce(c); if (rc_) return rc_; }
-  dev_free(c->d_nodes);
-  dev_free(c->d_nodes_full);
-  dev_free(c->d_sweep);
-  dev_free(c->d_sweep_plain);
-  c->sweep_boxes = c->sweep_leaves = c->sweep_hull = 0;
-  dev_free(c->d_wide);
-  dev_free(c->d_wide_q);
-  dev_free(c->d_wide_leafbox);
-  dev_free(c->d_wide_tris);
-  dev_free(c->d_wide_rank_of);
-  dev_free(c->d_tris);
-  // the wide walk's overflow area is sized by the scene's stack bound: a
-  // deeper tree needs a new one (it is reallocated at the next wide launch)
-  dev_free(c->d_wide_ovf);
-  c->wide_ovf_lanes = 0;
-  c->wide_ovf_stack = 0;
-  c->n_wide = 0;
+  scene_release(c);
   c->has_scene = false;
   c->guide_valid = false;
   temporal_forget(c);
@@ -1790,7 +1252,7 @@ int pt_set_params(pt_context* c, const pt_params* p) {
 }
 
 int pt_set_partition(pt_context* c, int nranks, int rank) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_set_partition: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_set_partition");
   if (!c) return fail(PT_ERR_INVALID, "null context");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(PT_ERR_INVALID, "bad partition");
   c->nranks = nranks;
@@ -1802,7 +1264,7 @@ int pt_set_partition(pt_context* c, int nranks, int rank) {
 }
 
 int pt_set_partition_slots(pt_context* c, int nranks, int rank, const int* slots) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_set_partition_slots: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_set_partition_slots");
   if (!c || !slots) return fail(PT_ERR_INVALID, "null argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(PT_ERR_INVALID, "bad partition");
   long long m = 0;
@@ -1897,14 +1359,7 @@ int pt_read_accum(pt_context* c, float* rgba, size_t n) {
   if (c && c->group) return ptg::read_accum(c->group, rgba, n);
   if (!c || !rgba) return fail(PT_ERR_INVALID, "null argument");
   if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
-  const size_t need = (size_t)c->width * c->height * 4;
-  if (n < need) return fail(PT_ERR_INVALID, "output buffer too small: need " + std::to_string(need) + " floats");
-  PT_HIP(hipSetDevice(c->device));
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(hipMemcpyAsync(rgba, c->d_accum, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  PT_HIP(hipStreamSynchronize(c->stream));
-  return PT_OK;
+  return read_image(c, c->d_accum, c->width, c->height, 4, rgba, n);
 }
 
 int pt_render(pt_context* c, uint32_t first_batch, uint32_t n_batches) {
@@ -1918,7 +1373,7 @@ int pt_render(pt_context* c, uint32_t first_batch, uint32_t n_batches) {
 // traffic.  The accumulation buffer is neither read nor written.
 int pt_render_packed(pt_context* c, uint32_t n_batches, void* packed, const void* gathered, size_t slot_floats,
                      void* frame) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_render_packed: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_render_packed");
   if (!c || !packed) return fail(PT_ERR_INVALID, "null argument");
   if (((uintptr_t)packed) & 15) return fail(PT_ERR_INVALID, "packed buffer must be 16-B aligned");
   if (c->stats_mode) return fail(PT_ERR_UNSUPPORTED, "stats mode renders into the accumulation buffer");
@@ -2034,728 +1489,6 @@ int pt_readback_end(pt_context* c, int ticket, float* rgba, size_t n) {
   return fail(PT_ERR_INVALID, "unknown or already collected readback ticket " + std::to_string(ticket));
 }
 
-// ---- first-hit guide image and a-trous denoiser (pt_denoise.h) --------------
-int pt_denoise_default_params(pt_denoise_params* out) {
-  if (!out) return fail(PT_ERR_INVALID, "null argument");
-  out->iterations = 5;
-  out->sigma_color = 16.0f;
-  out->sigma_normal = 0.35f;
-  out->sigma_depth = 0.25f;
-  return PT_OK;
-}
-
-static int denoise_params(const pt_denoise_params* in, pt_denoise_params* p) {
-  if (in)
-    *p = *in;
-  else
-    (void)pt_denoise_default_params(p);
-  if (!ptdn::params_ok(p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth))
-    return fail(PT_ERR_INVALID, "pt_denoise_params: iterations 1-6; sigmas finite, > 0 and with a finite non-zero square");
-  return PT_OK;
-}
-
-int pt_guide_ray(const float ubo[16], int w, int h, int x, int y, float o3[3], float d3[3]) {
-  if (!ubo || !o3 || !d3) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0 || x < 0 || y < 0 || x >= w || y >= h) return fail(PT_ERR_INVALID, "pixel outside the frame");
-  const ptdn::CamBasis b = ptdn::cam_basis(ubo);
-  const ptm::v3 d = ptdn::guide_dir(b.dir, b.right, b.up, b.tan_fov, w, h, x, y);
-  o3[0] = b.pos.x; o3[1] = b.pos.y; o3[2] = b.pos.z;
-  d3[0] = d.x; d3[1] = d.y; d3[2] = d.z;
-  return PT_OK;
-}
-
-int pt_denoise_host(const float* rgba, const float* guide, int w, int h, const pt_denoise_params* params, float* out) {
-  if (!rgba || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
-  pt_denoise_params p;
-  const int rp = denoise_params(params, &p);
-  if (rp) return rp;
-  const size_t n = (size_t)w * (size_t)h;
-  std::vector<float4> g(n), a(n), b(n);
-  memcpy(g.data(), guide, n * sizeof(float4));
-  memcpy(a.data(), rgba, n * sizeof(float4));
-  for (int i = 0; i < p.iterations; ++i) {
-    const ptdn::Sigma2 s = ptdn::pass_sigma2(p.sigma_color, p.sigma_normal, p.sigma_depth, i);
-    const ptdn::ImageFetch fetch = {a.data(), g.data(), w};
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) b[(size_t)y * w + x] = ptdn::atrous_pixel(fetch, w, h, x, y, 1 << i, s);
-    a.swap(b);
-  }
-  memcpy(out, a.data(), n * sizeof(float4));
-  return PT_OK;
-}
-
-// A library-owned image of at least n pixels.
-static int grow_image(pt_context* c, float4** img, size_t* cap, size_t n) {
-  if (*img && *cap >= n) return PT_OK;
-  { const int rc_ = quiesce(c); if (rc_) return rc_; }
-  dev_free(*img);
-  *cap = 0;
-  PT_HIP(hipMalloc((void**)img, n * sizeof(float4)));
-  *cap = n;
-  return PT_OK;
-}
-
-int pt_render_guide(pt_context* c) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_render_guide: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
-  if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
-  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
-  PT_HIP(hipSetDevice(c->device));
-  c->guide_valid = false;
-  ptd::RenderParams p{};
-  p.nodes = c->d_nodes;
-  p.n_nodes = c->n_nodes;
-  p.tris = c->d_tris;
-  p.hit_tris = c->d_tris;
-  p.n_tris = c->n_tris;
-  p.width = c->width;
-  p.height = c->height;
-  camera_params(c->cam, &p);
-  p.blocks_x = (c->width + 15) / 16;
-  p.blocks_total = p.blocks_x * ((c->height + 15) / 16);
-  p.n_cull = -1;
-  const bool wide = c->opt_wide && c->n_wide > 0;
-  const bool fits = ptd::scene_lds_bytes(p) <= ptd::kMaxSceneLds;
-  if (!wide && c->opt_scene_lds == 2 && !fits) return fail(PT_ERR_UNSUPPORTED, "scene too large for the LDS variant");
-  const bool lds = !wide && (c->opt_scene_lds == 2 || (c->opt_scene_lds == 1 && fits));
-  if (wide) {
-    const int rw = wide_params(c, &p);
-    if (rw) return rw;
-  }
-  // the temporal history's guide is put aside before the image is written again (stream order keeps
-  // whatever still reads it correct: only the pointers move)
-  if (c->t_frames > 0 && !c->t_guide_aside && c->guide_serial == c->t_guide_serial) {
-    std::swap(c->d_guide, c->d_guide_prev);
-    std::swap(c->guide_cap, c->guide_prev_cap);
-    c->t_guide_aside = true;
-  }
-  const int rg = grow_image(c, &c->d_guide, &c->guide_cap, (size_t)c->width * c->height);
-  if (rg) return rg;
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(ptd::launch_guide(p, c->d_guide, lds, c->stream));
-  c->guide_serial++;
-  c->guide_valid = true;
-  return mark_shared(c);
-}
-
-void* pt_guide_device_ptr(pt_context* c) {
-  if (!c || c->group || !c->guide_valid) return nullptr;
-  return (void*)c->d_guide;
-}
-
-// Copies a library-owned W x H image to the host behind the work enqueued so far.
-static int read_image(pt_context* c, const float4* img, int w, int h, float* out, size_t n) {
-  const size_t need = (size_t)w * h * 4;
-  if (n < need) return fail(PT_ERR_INVALID, "output buffer too small: need " + std::to_string(need) + " floats");
-  PT_HIP(hipSetDevice(c->device));
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(hipMemcpyAsync(out, img, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  PT_HIP(hipStreamSynchronize(c->stream));
-  return PT_OK;
-}
-
-int pt_read_guide(pt_context* c, float* out, size_t n) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_guide: not on a multi-device context (pt_create_multi)");
-  if (!c || !out) return fail(PT_ERR_INVALID, "null argument");
-  if (!c->guide_valid) return fail(PT_ERR_INVALID, "no guide image for the current scene, camera and size (pt_render_guide)");
-  return read_image(c, c->d_guide, c->width, c->height, out, n);
-}
-
-int pt_denoise(pt_context* c, const pt_denoise_params* params, const void* src, void* dst) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_denoise: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  pt_denoise_params p;
-  const int rp = denoise_params(params, &p);
-  if (rp) return rp;
-  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
-  if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
-  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
-  if ((((uintptr_t)src) & 15) || (((uintptr_t)dst) & 15)) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
-  const float4* in = src ? (const float4*)src : c->d_accum;
-  if (dst && (const float4*)dst == in) return fail(PT_ERR_INVALID, "pt_denoise: source and destination must differ");
-  PT_HIP(hipSetDevice(c->device));
-  if (!c->guide_valid) {
-    const int rg = pt_render_guide(c);
-    if (rg) return rg;
-  }
-  const int w = c->width, h = c->height;
-  const size_t n = (size_t)w * h;
-  for (int k = 0; k < 2 && k < p.iterations - 1; ++k) {   // the ping-pong images the passes need
-    const int rs = grow_image(c, &c->d_dn_scratch[k], &c->dn_scratch_cap[k], n);
-    if (rs) return rs;
-  }
-  float4* out = (float4*)dst;
-  if (!out) {
-    c->denoised_w = c->denoised_h = 0;
-    const int rd = grow_image(c, &c->d_denoised, &c->denoised_cap, n);
-    if (rd) return rd;
-    out = c->d_denoised;
-  }
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  // pass i reads the previous pass's image (the source first) and writes a
-  // scratch image, the last one the destination; the source is only read
-  const float4* cur = in;
-  for (int i = 0; i < p.iterations; ++i) {
-    float4* to = i == p.iterations - 1 ? out : c->d_dn_scratch[i & 1];
-    const ptdn::Sigma2 s = ptdn::pass_sigma2(p.sigma_color, p.sigma_normal, p.sigma_depth, i);
-    PT_HIP(ptd::launch_atrous(cur, c->d_guide, to, w, h, 1 << i, s.c, s.n, s.z, c->opt_denoise_lds != 0 && i < 2,
-                              c->stream));
-    cur = to;
-  }
-  if (!dst) {
-    c->denoised_w = w;
-    c->denoised_h = h;
-  }
-  if (out == c->d_accum) {   // the accumulation buffer given as the destination
-    c->culled_state = 0;
-    c->moments_valid = false;
-  }
-  return mark_shared(c);
-}
-
-int pt_read_denoised(pt_context* c, float* rgba, size_t n) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_denoised: not on a multi-device context (pt_create_multi)");
-  if (!c || !rgba) return fail(PT_ERR_INVALID, "null argument");
-  if (!c->d_denoised || c->denoised_w == 0)
-    return fail(PT_ERR_INVALID, "no library-owned denoised image (pt_denoise with a null destination)");
-  return read_image(c, c->d_denoised, c->denoised_w, c->denoised_h, rgba, n);
-}
-
-// ---- luminance moments and the variance-guided filter (pt_denoise.h) --------
-static bool moments_ready(const pt_context* c) {
-  return c->opt_moments && c->moments_valid && c->d_moments && c->moments_n >= 1;
-}
-
-void* pt_moments_device_ptr(pt_context* c) {
-  if (!c || c->group || !moments_ready(c)) return nullptr;
-  return (void*)c->d_moments;
-}
-
-int pt_read_moments(pt_context* c, float* out, size_t n, uint32_t* n_samples) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_moments: not on a multi-device context (pt_create_multi)");
-  if (!c || !out) return fail(PT_ERR_INVALID, "null argument");
-  if (!c->opt_moments || !c->d_moments || c->moments_cap < (size_t)c->width * c->height)
-    return fail(PT_ERR_INVALID, "no moments image (PT_OPT_MOMENTS, then a render)");
-  const size_t need = (size_t)c->width * c->height * 2;
-  if (n < need) return fail(PT_ERR_INVALID, "output buffer too small: need " + std::to_string(need) + " floats");
-  PT_HIP(hipSetDevice(c->device));
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(hipMemcpyAsync(out, c->d_moments, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  PT_HIP(hipStreamSynchronize(c->stream));
-  if (n_samples) *n_samples = moments_ready(c) ? c->moments_n : 0u;   // 0: not batches 0..n-1 in order
-  return PT_OK;
-}
-
-int pt_denoise_var_default_params(pt_denoise_var_params* out) {
-  if (!out) return fail(PT_ERR_INVALID, "null argument");
-  out->iterations = 4;
-  out->sigma_lum = 1.5f;
-  out->sigma_normal = 1.0f;
-  out->sigma_depth = 1.0f;
-  return PT_OK;
-}
-
-static int denoise_var_params(const pt_denoise_var_params* in, pt_denoise_var_params* p) {
-  if (in)
-    *p = *in;
-  else
-    (void)pt_denoise_var_default_params(p);
-  if (!ptdn::var_params_ok(p->iterations, p->sigma_lum, p->sigma_normal, p->sigma_depth))
-    return fail(PT_ERR_INVALID, "pt_denoise_var_params: iterations 1-6; sigmas finite, > 0 and with a finite non-zero square");
-  return PT_OK;
-}
-
-int pt_denoise_var_host(const float* rgba, const float* moments, uint32_t n_samples, const float* guide, int w, int h,
-                        const pt_denoise_var_params* params, float* out) {
-  if (!rgba || !moments || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
-  if (n_samples < 2) return fail(PT_ERR_INVALID, "pt_denoise_var: the variance of the mean needs at least 2 samples");
-  const size_t n = (size_t)w * (size_t)h;
-  std::vector<float> va(n);
-  for (size_t i = 0; i < n; ++i) va[i] = ptdn::var_of_mean(moments[2 * i], moments[2 * i + 1], n_samples);
-  return pt_denoise_var_plane_host(rgba, va.data(), guide, w, h, params, out);
-}
-
-int pt_denoise_var_plane_host(const float* rgba, const float* variance, const float* guide, int w, int h,
-                              const pt_denoise_var_params* params, float* out) {
-  if (!rgba || !variance || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
-  pt_denoise_var_params p;
-  const int rp = denoise_var_params(params, &p);
-  if (rp) return rp;
-  const size_t n = (size_t)w * (size_t)h;
-  std::vector<float4> g(n), a(n), b(n);
-  std::vector<float> va(variance, variance + n), vb(n);
-  memcpy(g.data(), guide, n * sizeof(float4));
-  memcpy(a.data(), rgba, n * sizeof(float4));
-  const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
-  for (int i = 0; i < p.iterations; ++i) {
-    const ptdn::VarImageFetch fetch = {a.data(), g.data(), va.data(), w};
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) {
-        const ptdn::VarOut o = ptdn::atrous_var_pixel(fetch, w, h, x, y, 1 << i, p.sigma_lum, sn2, sz2);
-        b[(size_t)y * w + x] = o.c;
-        vb[(size_t)y * w + x] = o.v;
-      }
-    a.swap(b);
-    va.swap(vb);
-  }
-  memcpy(out, a.data(), n * sizeof(float4));
-  return PT_OK;
-}
-
-static int var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,
-                      const float4* guide, float4* dst);
-
-int pt_denoise_var(pt_context* c, const pt_denoise_var_params* params, void* dst) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_var: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  pt_denoise_var_params p;
-  const int rp = denoise_var_params(params, &p);
-  if (rp) return rp;
-  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
-  if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
-  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
-  if (!moments_ready(c)) return fail(PT_ERR_INVALID, "pt_denoise_var: no valid moments (PT_OPT_MOMENTS, then a render from batch 0)");
-  if (c->moments_n < 2) return fail(PT_ERR_INVALID, "pt_denoise_var: the variance of the mean needs at least 2 samples");
-  if (((uintptr_t)dst) & 15) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
-  if (dst && (float4*)dst == c->d_accum) return fail(PT_ERR_INVALID, "pt_denoise_var: source and destination must differ");
-  PT_HIP(hipSetDevice(c->device));
-  if (!c->guide_valid) {
-    const int rg = pt_render_guide(c);
-    if (rg) return rg;
-  }
-  return var_filter(c, p, c->d_accum, nullptr, c->d_guide, (float4*)dst);
-}
-
-// The variance-guided filter's passes of the context's frame: from colour src, the guide and either the
-// variance plane var0 (only read) or, var0 null, the variance of the mean of the context's moments.
-// dst null: the library-owned image pt_read_denoised reads.
-static int var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,
-                      const float4* guide, float4* dst) {
-  const int w = c->width, h = c->height;
-  const size_t n = (size_t)w * h;
-  for (int k = 0; k < 2 && k < p.iterations - 1; ++k) {
-    const int rs = grow_image(c, &c->d_dn_scratch[k], &c->dn_scratch_cap[k], n);
-    if (rs) return rs;
-  }
-  for (int k = 0; k < 2; ++k) {   // the variance planes: var0 in [0], pass i from [i & 1] to [(i + 1) & 1]
-    if (c->d_var[k] && c->var_cap[k] >= n) continue;
-    { const int rc_ = quiesce(c); if (rc_) return rc_; }
-    dev_free(c->d_var[k]);
-    c->var_cap[k] = 0;
-    PT_HIP(hipMalloc((void**)&c->d_var[k], n * sizeof(float)));
-    c->var_cap[k] = n;
-  }
-  float4* out = (float4*)dst;
-  if (!out) {
-    c->denoised_w = c->denoised_h = 0;
-    const int rd = grow_image(c, &c->d_denoised, &c->denoised_cap, n);
-    if (rd) return rd;
-    out = c->d_denoised;
-  }
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  if (!var0) PT_HIP(ptd::launch_moments_var(c->d_moments, c->d_var[0], w, h, c->moments_n, c->stream));
-  const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
-  const float4* cur = src;
-  for (int i = 0; i < p.iterations; ++i) {
-    float4* to = i == p.iterations - 1 ? out : c->d_dn_scratch[i & 1];
-    const float* vsrc = i == 0 && var0 ? var0 : c->d_var[i & 1];
-    PT_HIP(ptd::launch_atrous_var(cur, vsrc, guide, to, c->d_var[(i + 1) & 1], w, h, 1 << i, p.sigma_lum, sn2, sz2,
-                                  c->opt_denoise_lds != 0 && i < 2, c->stream));
-    cur = to;
-  }
-  if (!dst) {
-    c->denoised_w = w;
-    c->denoised_h = h;
-  }
-  return mark_shared(c);
-}
-
-// ---- temporal reprojection (pt_denoise.h reproject_pixel) --------------------
-int pt_temporal_default_params(pt_temporal_params* out) {
-  if (!out) return fail(PT_ERR_INVALID, "null argument");
-  out->max_history = 64;
-  out->alpha_min = 0.0f;
-  out->normal_min = 0.5f;
-  out->depth_rel = 0.05f;
-  return PT_OK;
-}
-
-static int temporal_params(const pt_temporal_params* in, pt_temporal_params* p) {
-  if (in)
-    *p = *in;
-  else
-    (void)pt_temporal_default_params(p);
-  if (!ptdn::temporal_params_ok(p->max_history, p->alpha_min, p->normal_min, p->depth_rel))
-    return fail(PT_ERR_INVALID,
-                "pt_temporal_params: max_history 1-65536, alpha_min in [0, 1], normal_min in [-1, 1], depth_rel finite and > 0");
-  return PT_OK;
-}
-
-// The checks pt_reproject and pt_reproject_host share: sizes, the sample count, the images' presence (the
-// history all there or all null) and that no output is an input or another output.
-static int reproject_args(const float* cam_cur, const float* cam_prev, int w, int h, uint32_t n,
-                          const pt_reproject_images* im) {
-  if (!cam_cur || !cam_prev || !im) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0 || (long long)w * h > (1ll << 31)) return fail(PT_ERR_INVALID, "bad resolution");
-  if (n < 1 || n > 65536) return fail(PT_ERR_INVALID, "pt_reproject: n takes 1 to 65536 samples");
-  if (!im->color || !im->moments || !im->guide || !im->out_color || !im->out_moments || !im->out_length ||
-      !im->out_variance)
-    return fail(PT_ERR_INVALID, "pt_reproject: null image");
-  const int nh = (im->hist_color ? 1 : 0) + (im->hist_moments ? 1 : 0) + (im->hist_length ? 1 : 0) + (im->hist_guide ? 1 : 0);
-  if (nh != 0 && nh != 4) return fail(PT_ERR_INVALID, "pt_reproject: the four history images are all given or all null");
-  const void* in[7] = {im->color, im->moments, im->guide, im->hist_color, im->hist_moments, im->hist_length, im->hist_guide};
-  const void* out[4] = {im->out_color, im->out_moments, im->out_length, im->out_variance};
-  for (int i = 0; i < 4; ++i) {
-    for (int k = 0; k < 7; ++k)
-      if (out[i] == in[k]) return fail(PT_ERR_INVALID, "pt_reproject: an output image is also an input");
-    for (int k = 0; k < i; ++k)
-      if (out[i] == out[k]) return fail(PT_ERR_INVALID, "pt_reproject: two output images are the same");
-  }
-  return PT_OK;
-}
-
-int pt_reproject_host(const float cam_cur[16], const float cam_prev[16], int w, int h, uint32_t n,
-                      const pt_reproject_images* im, const pt_temporal_params* params) {
-  const int ra = reproject_args(cam_cur, cam_prev, w, h, n, im);
-  if (ra) return ra;
-  pt_temporal_params p;
-  const int rp = temporal_params(params, &p);
-  if (rp) return rp;
-  const size_t np = (size_t)w * (size_t)h;
-  std::vector<float4> hc, hg;
-  std::vector<float2> hm;
-  ptdn::HistImages hist = {nullptr, nullptr, nullptr, nullptr};
-  if (im->hist_color) {
-    hc.resize(np);
-    hg.resize(np);
-    hm.resize(np);
-    memcpy(hc.data(), im->hist_color, np * sizeof(float4));
-    memcpy(hg.data(), im->hist_guide, np * sizeof(float4));
-    memcpy(hm.data(), im->hist_moments, np * sizeof(float2));
-    hist = {hc.data(), hm.data(), im->hist_length, hg.data()};
-  }
-  const ptdn::CamBasis B = ptdn::cam_basis(cam_cur), Bp = ptdn::cam_basis(cam_prev);
-  const ptdn::TemporalParams tp = {(float)p.max_history, p.alpha_min, p.normal_min, p.depth_rel};
-  for (int y = 0; y < h; ++y)
-    for (int x = 0; x < w; ++x) {
-      const size_t i = (size_t)y * w + x;
-      float4 c, g;
-      float2 m;
-      memcpy(&c, im->color + 4 * i, sizeof c);
-      memcpy(&g, im->guide + 4 * i, sizeof g);
-      memcpy(&m, im->moments + 2 * i, sizeof m);
-      const ptdn::ReprojOut o = ptdn::reproject_pixel(hist, B, Bp, w, h, x, y, c, m, g, (float)n, tp);
-      memcpy(im->out_color + 4 * i, &o.c, sizeof o.c);
-      memcpy(im->out_moments + 2 * i, &o.m, sizeof o.m);
-      im->out_length[i] = o.len;
-      im->out_variance[i] = o.var;
-    }
-  return PT_OK;
-}
-
-int pt_reproject(pt_context* c, const float cam_cur[16], const float cam_prev[16], int w, int h, uint32_t n,
-                 const pt_reproject_images* im, const pt_temporal_params* params) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_reproject: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  const int ra = reproject_args(cam_cur, cam_prev, w, h, n, im);
-  if (ra) return ra;
-  pt_temporal_params p;
-  const int rp = temporal_params(params, &p);
-  if (rp) return rp;
-  const uintptr_t a16 = (uintptr_t)im->color | (uintptr_t)im->guide | (uintptr_t)im->hist_color |
-                        (uintptr_t)im->hist_guide | (uintptr_t)im->out_color;
-  const uintptr_t a8 = (uintptr_t)im->moments | (uintptr_t)im->hist_moments | (uintptr_t)im->out_moments;
-  const uintptr_t a4 = (uintptr_t)im->hist_length | (uintptr_t)im->out_length | (uintptr_t)im->out_variance;
-  if ((a16 & 15) || (a8 & 7) || (a4 & 3))
-    return fail(PT_ERR_INVALID, "pt_reproject: colours and guides must be 16-B aligned, moments 8-B, lengths and variance 4-B");
-  PT_HIP(hipSetDevice(c->device));
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(ptd::launch_reproject((const float4*)im->color, (const float2*)im->moments, (const float4*)im->guide,
-                               (const float4*)im->hist_color, (const float2*)im->hist_moments, im->hist_length,
-                               (const float4*)im->hist_guide, (float4*)im->out_color, (float2*)im->out_moments,
-                               im->out_length, im->out_variance, cam_cur, cam_prev, w, h, n, p.max_history, p.alpha_min,
-                               p.normal_min, p.depth_rel, c->stream));
-  if ((float4*)im->out_color == c->d_accum) {   // the accumulation buffer given as a destination
-    c->culled_state = 0;
-    c->moments_valid = false;
-  }
-  return mark_shared(c);
-}
-
-// One image set of at least n pixels.
-static int grow_tset(pt_context* c, pt_context::TemporalSet* s, size_t n) {
-  if (s->color && s->cap >= n) return PT_OK;
-  { const int rc_ = quiesce(c); if (rc_) return rc_; }
-  dev_free(s->color);
-  dev_free(s->moments);
-  dev_free(s->length);
-  dev_free(s->variance);
-  s->cap = 0;
-  PT_HIP(hipMalloc((void**)&s->color, n * sizeof(float4)));
-  PT_HIP(hipMalloc((void**)&s->moments, n * sizeof(float2)));
-  PT_HIP(hipMalloc((void**)&s->length, n * sizeof(float)));
-  PT_HIP(hipMalloc((void**)&s->variance, n * sizeof(float)));
-  s->cap = n;
-  return PT_OK;
-}
-
-static const char* temporal_unsupported(const pt_context* c) {
-  if (c->nranks > 1) return "not on a partition of more than one rank";
-  if (c->stats_mode) return "not in stats mode";
-  if (c->opt_count) return "not with PT_OPT_COUNT_TRACED";
-  return nullptr;
-}
-
-int pt_temporal_advance(pt_context* c, const float ubo[16], uint32_t n_batches) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_advance: not on a multi-device context (pt_create_multi)");
-  if (!c || !ubo) return fail(PT_ERR_INVALID, "null argument");
-  if (const char* why = temporal_unsupported(c)) return fail(PT_ERR_UNSUPPORTED, std::string("pt_temporal_advance: ") + why);
-  if (n_batches < 1 || n_batches > 65536) return fail(PT_ERR_INVALID, "pt_temporal_advance: n_batches takes 1 to 65536");
-  if (!c->opt_moments) return fail(PT_ERR_INVALID, "pt_temporal_advance: needs PT_OPT_MOMENTS 1");
-  if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
-  if (c->n_lights < 1) return fail(PT_ERR_INVALID, "no lights uploaded");
-  if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
-  PT_HIP(hipSetDevice(c->device));
-  const int w = c->width, h = c->height;
-  const size_t n = (size_t)w * h;
-  const bool have = c->t_frames > 0 && c->t_w == w && c->t_h == h;
-  if (!have) temporal_forget(c);
-  const int dst = have ? 1 - c->t_cur : 0;
-  {
-    const int rs = grow_tset(c, &c->tset[dst], n);
-    if (rs) return rs;
-  }
-  int rc = pt_set_camera(c, ubo);
-  if (rc) return rc;
-  rc = pt_clear_accum(c);
-  if (rc) return rc;
-  c->seed_extra = c->t_samples;
-  rc = render_impl(c, 0, n_batches, nullptr);
-  c->seed_extra = 0;
-  if (rc) return rc;
-  rc = pt_render_guide(c);   // puts the last frame's guide aside first
-  if (rc) return rc;
-  const pt_context::TemporalSet& src = c->tset[c->t_cur];
-  const pt_context::TemporalSet& out = c->tset[dst];
-  const float4* hist_guide = c->t_guide_aside ? c->d_guide_prev : nullptr;
-  const bool hist = have && hist_guide;
-  pt_temporal_params p;
-  (void)pt_temporal_default_params(&p);
-  rc = order_shared(c);
-  if (rc) return rc;
-  PT_HIP(ptd::launch_reproject(c->d_accum, c->d_moments, c->d_guide, hist ? src.color : nullptr,
-                               hist ? src.moments : nullptr, hist ? src.length : nullptr, hist ? hist_guide : nullptr,
-                               out.color, out.moments, out.length, out.variance, ubo, c->t_cam, w, h, n_batches,
-                               p.max_history, p.alpha_min, p.normal_min, p.depth_rel, c->stream));
-  c->t_cur = dst;
-  c->t_frames++;
-  c->t_samples += n_batches;
-  memcpy(c->t_cam, ubo, sizeof c->t_cam);
-  c->t_w = w;
-  c->t_h = h;
-  c->t_guide_serial = c->guide_serial;
-  c->t_guide_aside = false;
-  return mark_shared(c);
-}
-
-int pt_temporal_reset(pt_context* c) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_reset: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  temporal_forget(c);
-  return PT_OK;
-}
-
-int pt_temporal_info(pt_context* c, uint32_t* frames, uint32_t* samples) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_info: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  if (frames) *frames = c->t_frames;
-  if (samples) *samples = c->t_samples;
-  return PT_OK;
-}
-
-// Whether the context holds a temporal result of the current frame size.
-static bool temporal_ready(const pt_context* c) {
-  return c->t_frames > 0 && c->t_w == c->width && c->t_h == c->height && c->tset[c->t_cur].color;
-}
-
-void* pt_temporal_device_ptr(pt_context* c, int which) {
-  if (!c || c->group || !temporal_ready(c)) return nullptr;
-  const pt_context::TemporalSet& s = c->tset[c->t_cur];
-  return which == 0 ? (void*)s.color : which == 1 ? (void*)s.moments : which == 2 ? (void*)s.length
-         : which == 3 ? (void*)s.variance : nullptr;
-}
-
-int pt_read_temporal(pt_context* c, float* rgba, float* moments, float* length) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_read_temporal: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  if (!temporal_ready(c)) return fail(PT_ERR_INVALID, "no temporal result for the current frame (pt_temporal_advance)");
-  PT_HIP(hipSetDevice(c->device));
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  const pt_context::TemporalSet& s = c->tset[c->t_cur];
-  const size_t n = (size_t)c->t_w * c->t_h;
-  if (rgba) PT_HIP(hipMemcpyAsync(rgba, s.color, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  if (moments) PT_HIP(hipMemcpyAsync(moments, s.moments, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-  if (length) PT_HIP(hipMemcpyAsync(length, s.length, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  PT_HIP(hipStreamSynchronize(c->stream));
-  return PT_OK;
-}
-
-int pt_temporal_denoise(pt_context* c, const pt_denoise_var_params* params, void* dst) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_temporal_denoise: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  pt_denoise_var_params p;
-  const int rp = denoise_var_params(params, &p);
-  if (rp) return rp;
-  if (!temporal_ready(c)) return fail(PT_ERR_INVALID, "no temporal result for the current frame (pt_temporal_advance)");
-  if (((uintptr_t)dst) & 15) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
-  const pt_context::TemporalSet& s = c->tset[c->t_cur];
-  if (dst && (float4*)dst == s.color) return fail(PT_ERR_INVALID, "pt_temporal_denoise: source and destination must differ");
-  // the frame's guide: still d_guide, or where a later pt_render_guide put it aside
-  const float4* guide = c->t_guide_aside ? c->d_guide_prev : c->guide_serial == c->t_guide_serial ? c->d_guide : nullptr;
-  if (!guide) return fail(PT_ERR_INVALID, "pt_temporal_denoise: the temporal frame's guide is gone");
-  PT_HIP(hipSetDevice(c->device));
-  const int rf = var_filter(c, p, s.color, s.variance, guide, (float4*)dst);
-  if (rf) return rf;
-  if ((float4*)dst == c->d_accum) {   // the accumulation buffer given as the destination
-    c->culled_state = 0;
-    c->moments_valid = false;
-  }
-  return PT_OK;
-}
-
-// ---- spatial variance of short histories (pt_denoise.h spatial_var_pixel) ----
-int pt_spatial_var_default_params(pt_spatial_var_params* out) {
-  if (!out) return fail(PT_ERR_INVALID, "null argument");
-  out->below = 2;
-  out->radius = 1;
-  out->sigma_normal = 1.0f;
-  out->sigma_depth = 0.5f;
-  return PT_OK;
-}
-
-static int spatial_var_params(const pt_spatial_var_params* in, pt_spatial_var_params* p) {
-  if (in)
-    *p = *in;
-  else
-    (void)pt_spatial_var_default_params(p);
-  if (!ptdn::spatial_params_ok(p->below, p->radius, p->sigma_normal, p->sigma_depth))
-    return fail(PT_ERR_INVALID,
-                "pt_spatial_var_params: below 0-65536, radius 1-3; sigmas finite, > 0 and with a finite non-zero square");
-  return PT_OK;
-}
-
-// The checks pt_spatial_variance and pt_spatial_variance_host share.
-static int spatial_var_args(const void* moments, const void* length, const void* variance, const void* guide, int w,
-                            int h, const void* out) {
-  if (!moments || !length || !variance || !guide || !out) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0 || (long long)w * h > (1ll << 31)) return fail(PT_ERR_INVALID, "bad resolution");
-  if (out == moments || out == length || out == variance || out == guide)
-    return fail(PT_ERR_INVALID, "pt_spatial_variance: the output is also an input");
-  return PT_OK;
-}
-
-int pt_spatial_variance_host(const float* moments, const float* length, const float* variance, const float* guide,
-                             int w, int h, const pt_spatial_var_params* params, float* out) {
-  const int ra = spatial_var_args(moments, length, variance, guide, w, h, out);
-  if (ra) return ra;
-  pt_spatial_var_params p;
-  const int rp = spatial_var_params(params, &p);
-  if (rp) return rp;
-  const size_t n = (size_t)w * (size_t)h;
-  std::vector<float2> m(n);
-  std::vector<float4> g(n);
-  memcpy(m.data(), moments, n * sizeof(float2));
-  memcpy(g.data(), guide, n * sizeof(float4));
-  const ptdn::SpatialImageFetch fetch = {m.data(), length, g.data(), w};
-  const float below = (float)p.below;
-  const float sn2 = p.sigma_normal * p.sigma_normal, sz2 = p.sigma_depth * p.sigma_depth;
-  for (int y = 0; y < h; ++y)
-    for (int x = 0; x < w; ++x) {
-      const size_t i = (size_t)y * w + x;
-      const float lenp = length[i];
-      out[i] = lenp < below ? ptdn::spatial_var_pixel(fetch, w, h, x, y, p.radius, sn2, sz2, g[i], lenp) : variance[i];
-    }
-  return PT_OK;
-}
-
-int pt_spatial_variance(pt_context* c, const void* moments, const void* length, const void* variance,
-                        const void* guide, int w, int h, const pt_spatial_var_params* params, void* out) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_spatial_variance: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  const int ra = spatial_var_args(moments, length, variance, guide, w, h, out);
-  if (ra) return ra;
-  pt_spatial_var_params p;
-  const int rp = spatial_var_params(params, &p);
-  if (rp) return rp;
-  if (((uintptr_t)moments & 7) || (((uintptr_t)length | (uintptr_t)variance | (uintptr_t)out) & 3) || ((uintptr_t)guide & 15))
-    return fail(PT_ERR_INVALID, "pt_spatial_variance: moments must be 8-B aligned, the guide 16-B, length, variance and out 4-B");
-  PT_HIP(hipSetDevice(c->device));
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(ptd::launch_spatial_var((const float2*)moments, (const float*)length, (const float*)variance,
-                                 (const float4*)guide, (float*)out, w, h, p.below, p.radius,
-                                 p.sigma_normal * p.sigma_normal, p.sigma_depth * p.sigma_depth, c->stream));
-  if ((float4*)out == c->d_accum) {   // the accumulation buffer given as the destination
-    c->culled_state = 0;
-    c->moments_valid = false;
-  }
-  return mark_shared(c);
-}
-
-int pt_temporal_denoise_spatial(pt_context* c, const pt_denoise_var_params* params,
-                                const pt_spatial_var_params* spatial, void* dst) {
-  if (c && c->group)
-    return fail(PT_ERR_UNSUPPORTED, "pt_temporal_denoise_spatial: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  pt_denoise_var_params p;
-  const int rp = denoise_var_params(params, &p);
-  if (rp) return rp;
-  pt_spatial_var_params sp;
-  const int rs = spatial_var_params(spatial, &sp);
-  if (rs) return rs;
-  if (!temporal_ready(c)) return fail(PT_ERR_INVALID, "no temporal result for the current frame (pt_temporal_advance)");
-  if (((uintptr_t)dst) & 15) return fail(PT_ERR_INVALID, "images must be 16-B aligned");
-  const pt_context::TemporalSet& s = c->tset[c->t_cur];
-  if (dst && (float4*)dst == s.color)
-    return fail(PT_ERR_INVALID, "pt_temporal_denoise_spatial: source and destination must differ");
-  const float4* guide = c->t_guide_aside ? c->d_guide_prev : c->guide_serial == c->t_guide_serial ? c->d_guide : nullptr;
-  if (!guide) return fail(PT_ERR_INVALID, "pt_temporal_denoise_spatial: the temporal frame's guide is gone");
-  PT_HIP(hipSetDevice(c->device));
-  const int w = c->width, h = c->height;
-  const size_t n = (size_t)w * h;
-  if (!c->d_spatial_var || c->spatial_var_cap < n) {
-    { const int rc_ = quiesce(c); if (rc_) return rc_; }
-    dev_free(c->d_spatial_var);
-    c->spatial_var_cap = 0;
-    PT_HIP(hipMalloc((void**)&c->d_spatial_var, n * sizeof(float)));
-    c->spatial_var_cap = n;
-  }
-  const int ro = order_shared(c);
-  if (ro) return ro;
-  PT_HIP(ptd::launch_spatial_var(s.moments, s.length, s.variance, guide, c->d_spatial_var, w, h, sp.below, sp.radius,
-                                 sp.sigma_normal * sp.sigma_normal, sp.sigma_depth * sp.sigma_depth, c->stream));
-  const int rm = mark_shared(c);
-  if (rm) return rm;
-  const int rf = var_filter(c, p, s.color, c->d_spatial_var, guide, (float4*)dst);
-  if (rf) return rf;
-  if ((float4*)dst == c->d_accum) {   // the accumulation buffer given as the destination
-    c->culled_state = 0;
-    c->moments_valid = false;
-  }
-  return PT_OK;
-}
-
 int pt_last_kernel(pt_context* c, int* kernel) {
   if (c && c->group) return ptg::last_kernel(c->group, kernel);
   if (!c || !kernel) return fail(PT_ERR_INVALID, "null argument");
@@ -2763,113 +1496,64 @@ int pt_last_kernel(pt_context* c, int* kernel) {
   return PT_OK;
 }
 
+// The options that are a range check and a store: value in [lo, hi] goes into
+// the field, anything else is refused with the message.
+struct IntOption {
+  int key;
+  int pt_context::* field;
+  int lo, hi;
+  const char* message;
+};
+static const IntOption kIntOptions[] = {
+    {PT_OPT_KERNEL, &pt_context::opt_kernel, 0, 3, "PT_OPT_KERNEL takes 0, 1 or 3"},   // (2: refused below)
+    {PT_OPT_WIDE, &pt_context::opt_wide, 0, 2, "PT_OPT_WIDE takes 0, 1 or 2"},
+    {PT_OPT_WF_FUSE, &pt_context::opt_wf_fuse, 0, 1, "PT_OPT_WF_FUSE takes 0 or 1"},
+    {PT_OPT_WF_TAIL, &pt_context::opt_wf_tail, -1, INT_MAX, "PT_OPT_WF_TAIL takes -1 (auto) or a ray count >= 0"},
+    {PT_OPT_WF_REFILL, &pt_context::opt_wf_refill, 0, 64, "PT_OPT_WF_REFILL takes 0 (auto) to 64 idle lanes"},
+    {PT_OPT_WF_GRID, &pt_context::opt_wf_grid, 1, 100, "PT_OPT_WF_GRID takes 1 to 100 (percent)"},
+    {PT_OPT_WF_STREAMS, &pt_context::opt_wf_streams, 1, 2, "PT_OPT_WF_STREAMS takes 1 or 2"},
+    {PT_OPT_WIDE_BUILD, &pt_context::opt_wide_build, 0, 1, "PT_OPT_WIDE_BUILD takes 0 or 1"},
+    {PT_OPT_COUNT_TRACED, &pt_context::opt_count, 0, 1, "PT_OPT_COUNT_TRACED takes 0 or 1"},
+    {PT_OPT_PRIMARY_CULL, &pt_context::opt_cull, 0, 1, "PT_OPT_PRIMARY_CULL takes 0 or 1"},
+    {PT_OPT_WF_PATHS, &pt_context::opt_wf_paths, 0, INT_MAX, "PT_OPT_WF_PATHS takes 0 or a path count"},
+    {PT_OPT_LAUNCH_TIMING, &pt_context::opt_timing, 0, INT_MAX,
+     "PT_OPT_LAUNCH_TIMING takes 0 (off) or k >= 1 (every k-th launch)"},
+    {PT_OPT_MIXED_LANES, &pt_context::opt_mixed, -1, 1000, "PT_OPT_MIXED_LANES takes -1 (auto), 0 (off) or 1-1000"},
+    {PT_OPT_ITEM_ORDER, &pt_context::opt_item_order, -1, 1, "PT_OPT_ITEM_ORDER takes -1 (auto), 0 or 1"},
+    {PT_OPT_FRESH_BATCH0, &pt_context::opt_fresh, 0, 1, "PT_OPT_FRESH_BATCH0 takes 0 or 1"},
+    {PT_OPT_SCENE_IN_LDS, &pt_context::opt_scene_lds, 0, 2, "PT_OPT_SCENE_IN_LDS takes 0, 1 or 2"},
+    {PT_OPT_DENOISE_LDS, &pt_context::opt_denoise_lds, 0, 1, "PT_OPT_DENOISE_LDS takes 0 or 1"},
+    {PT_OPT_SMALL_SWEEP, &pt_context::opt_small_sweep, -1, 1, "PT_OPT_SMALL_SWEEP takes -1 (auto), 0 or 1"},
+    {PT_OPT_CULL_TIGHT, &pt_context::opt_cull_tight, 0, 1, "PT_OPT_CULL_TIGHT takes 0 or 1"},
+    {PT_OPT_SWEEP_HULL, &pt_context::opt_sweep_hull, 0, 1, "PT_OPT_SWEEP_HULL takes 0 or 1"},
+    {PT_OPT_EXIT_SKIP, &pt_context::opt_exit_skip, 0, 1, "PT_OPT_EXIT_SKIP takes 0 or 1"},
+};
+
 int pt_set_option(pt_context* c, int key, int value) {
   if (c && c->group && key == PT_OPT_MOMENTS && value != 0)
     return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not on a multi-device context (pt_create_multi)");
   if (c && c->group && key == PT_OPT_MOMENTS) return PT_OK;
   if (c && c->group) return ptg::set_option(c->group, key, value);
   if (!c) return fail(PT_ERR_INVALID, "null context");
-  switch (key) {
+  switch (key) {   // the options that are more than a row of the table
     case PT_OPT_KERNEL:
       if (value == 2) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_KERNEL 2 (lane state machine) was removed: slower on every scene");
-      if (value < 0 || value > 3) return fail(PT_ERR_INVALID, "PT_OPT_KERNEL takes 0, 1 or 3");
-      c->opt_kernel = value;
-      return PT_OK;
-    case PT_OPT_WIDE:
-      if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "PT_OPT_WIDE takes 0, 1 or 2");
-      c->opt_wide = value;
-      return PT_OK;
+      break;
     case PT_OPT_WIDE_NODE:
       if (value == 80) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_WIDE_NODE 80 (8-wide nodes) was removed: slower on every scene");
       if (value != 64 && value != 128) return fail(PT_ERR_INVALID, "PT_OPT_WIDE_NODE takes 64 or 128");
       c->opt_wide_node = value;
       return PT_OK;
-    case PT_OPT_WF_FUSE:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_WF_FUSE takes 0 or 1");
-      c->opt_wf_fuse = value;
-      return PT_OK;
-    case PT_OPT_WF_TAIL:
-      if (value < -1) return fail(PT_ERR_INVALID, "PT_OPT_WF_TAIL takes -1 (auto) or a ray count >= 0");
-      c->opt_wf_tail = value;
-      return PT_OK;
-    case PT_OPT_WF_REFILL:
-      if (value < 0 || value > 64) return fail(PT_ERR_INVALID, "PT_OPT_WF_REFILL takes 0 (auto) to 64 idle lanes");
-      c->opt_wf_refill = value;
-      return PT_OK;
-    case PT_OPT_WF_GRID:
-      if (value < 1 || value > 100) return fail(PT_ERR_INVALID, "PT_OPT_WF_GRID takes 1 to 100 (percent)");
-      c->opt_wf_grid = value;
-      return PT_OK;
-    case PT_OPT_WF_STREAMS:
-      if (value != 1 && value != 2) return fail(PT_ERR_INVALID, "PT_OPT_WF_STREAMS takes 1 or 2");
-      c->opt_wf_streams = value;
-      return PT_OK;
-    case PT_OPT_WIDE_BUILD:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_WIDE_BUILD takes 0 or 1");
-      c->opt_wide_build = value;
-      return PT_OK;
     case PT_OPT_PAIRS:
       if (value == 1) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_PAIRS 1 (child-pair records) was removed: slower on every scene");
       if (value != 0) return fail(PT_ERR_INVALID, "PT_OPT_PAIRS takes 0");
       return PT_OK;
-    case PT_OPT_COUNT_TRACED:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_COUNT_TRACED takes 0 or 1");
-      c->opt_count = value;
-      return PT_OK;
-    case PT_OPT_PRIMARY_CULL:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_PRIMARY_CULL takes 0 or 1");
-      c->opt_cull = value;
-      return PT_OK;
-    case PT_OPT_WF_PATHS:
-      if (value < 0) return fail(PT_ERR_INVALID, "PT_OPT_WF_PATHS takes 0 or a path count");
-      c->opt_wf_paths = value;
-      return PT_OK;
     case PT_OPT_SM_BATCH:
       return fail(PT_ERR_UNSUPPORTED, "PT_OPT_SM_BATCH: the lane state-machine kernel was removed");
-    case PT_OPT_LAUNCH_TIMING:
-      if (value < 0) return fail(PT_ERR_INVALID, "PT_OPT_LAUNCH_TIMING takes 0 (off) or k >= 1 (every k-th launch)");
-      c->opt_timing = value;
-      return PT_OK;
-    case PT_OPT_MIXED_LANES:
-      if (value < -1 || value > 1000) return fail(PT_ERR_INVALID, "PT_OPT_MIXED_LANES takes -1 (auto), 0 (off) or 1-1000");
-      c->opt_mixed = value;
-      return PT_OK;
-    case PT_OPT_ITEM_ORDER:
-      if (value < -1 || value > 1) return fail(PT_ERR_INVALID, "PT_OPT_ITEM_ORDER takes -1 (auto), 0 or 1");
-      c->opt_item_order = value;
-      return PT_OK;
-    case PT_OPT_FRESH_BATCH0:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_FRESH_BATCH0 takes 0 or 1");
-      c->opt_fresh = value;
-      return PT_OK;
     case PT_OPT_SAMPLE_LANES:
       if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
         return fail(PT_ERR_INVALID, "PT_OPT_SAMPLE_LANES takes 0 (auto), 1, 2, 4 or 8");
       c->opt_sample_lanes = value;
-      return PT_OK;
-    case PT_OPT_SCENE_IN_LDS:
-      if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "PT_OPT_SCENE_IN_LDS takes 0, 1 or 2");
-      c->opt_scene_lds = value;
-      return PT_OK;
-    case PT_OPT_DENOISE_LDS:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_DENOISE_LDS takes 0 or 1");
-      c->opt_denoise_lds = value;
-      return PT_OK;
-    case PT_OPT_SMALL_SWEEP:
-      if (value < -1 || value > 1) return fail(PT_ERR_INVALID, "PT_OPT_SMALL_SWEEP takes -1 (auto), 0 or 1");
-      c->opt_small_sweep = value;
-      return PT_OK;
-    case PT_OPT_CULL_TIGHT:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_CULL_TIGHT takes 0 or 1");
-      c->opt_cull_tight = value;
-      return PT_OK;
-    case PT_OPT_SWEEP_HULL:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_SWEEP_HULL takes 0 or 1");
-      c->opt_sweep_hull = value;
-      return PT_OK;
-    case PT_OPT_EXIT_SKIP:
-      if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_EXIT_SKIP takes 0 or 1");
-      c->opt_exit_skip = value;
       return PT_OK;
     case PT_OPT_MOMENTS:
       if (value != 0 && value != 1) return fail(PT_ERR_INVALID, "PT_OPT_MOMENTS takes 0 or 1");
@@ -2884,12 +1568,19 @@ int pt_set_option(pt_context* c, int key, int value) {
     case PT_OPT_GROUP_CHECK:
       return fail(PT_ERR_UNSUPPORTED, "option " + std::to_string(key) + ": multi-device contexts only (pt_create_multi)");
     default:
-      return fail(PT_ERR_INVALID, "unknown option " + std::to_string(key));
+      break;
   }
+  for (const IntOption& o : kIntOptions) {
+    if (o.key != key) continue;
+    if (value < o.lo || value > o.hi) return fail(PT_ERR_INVALID, o.message);
+    c->*o.field = value;
+    return PT_OK;
+  }
+  return fail(PT_ERR_INVALID, "unknown option " + std::to_string(key));
 }
 
 int pt_tiles_owned(pt_context* c, int* n_tiles) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_tiles_owned: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_tiles_owned");
   if (!c || !n_tiles) return fail(PT_ERR_INVALID, "null argument");
   if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
   *n_tiles = ptd::owned_tiles(c->width, c->height, part_of(c, c->rank));
@@ -2897,7 +1588,7 @@ int pt_tiles_owned(pt_context* c, int* n_tiles) {
 }
 
 int pt_tiles_pack(pt_context* c, void* dst) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_tiles_pack: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_tiles_pack");
   if (!c || !dst) return fail(PT_ERR_INVALID, "null argument");
   if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
   PT_HIP(hipSetDevice(c->device));
@@ -2913,7 +1604,7 @@ int pt_tiles_pack(pt_context* c, void* dst) {
 }
 
 int pt_tiles_unpack(pt_context* c, const void* src, int src_rank, void* frame) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_tiles_unpack: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_tiles_unpack");
   if (!c || !src || !frame) return fail(PT_ERR_INVALID, "null argument");
   if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer (it sets the frame size)");
   if (src_rank < 0 || src_rank >= c->nranks) return fail(PT_ERR_INVALID, "src_rank out of range");
@@ -2932,7 +1623,7 @@ int pt_tiles_unpack(pt_context* c, const void* src, int src_rank, void* frame) {
 // ---- sparse tile exchange (live items only) --------------------------------
 
 int pt_items_live(pt_context* c, int rank, int* n_items, int* item_pixels) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_items_live: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_items_live");
   if (!c || !n_items || !item_pixels) return fail(PT_ERR_INVALID, "null argument");
   if (!c->last_valid) return fail(PT_ERR_INVALID, "no path-recursive pt_render yet");
   if (rank < 0 || rank >= c->last.nranks || rank >= (int)c->slots.size()) return fail(PT_ERR_INVALID, "rank out of range");
@@ -2944,7 +1635,7 @@ int pt_items_live(pt_context* c, int rank, int* n_items, int* item_pixels) {
 }
 
 int pt_items_pack(pt_context* c, void* dst) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_items_pack: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_items_pack");
   if (!c || !dst) return fail(PT_ERR_INVALID, "null argument");
   if (!c->last_valid || !c->d_accum) return fail(PT_ERR_INVALID, "no path-recursive pt_render yet");
   PT_HIP(hipSetDevice(c->device));
@@ -2966,7 +1657,7 @@ int pt_items_pack(pt_context* c, void* dst) {
 }
 
 int pt_items_unpack_all(pt_context* c, const void* src, size_t slot_floats, void* frame) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_items_unpack_all: not on a multi-device context (pt_create_multi)");
+  PT_SINGLE(c, "pt_items_unpack_all");
   if (!c || !src || !frame) return fail(PT_ERR_INVALID, "null argument");
   if (!c->last_valid) return fail(PT_ERR_INVALID, "no path-recursive pt_render yet");
   if (c->last.first_batch != 0)
@@ -3143,341 +1834,6 @@ int pt_selftest_exhaustive(int device, int fn, unsigned long long* mismatches, u
   return PT_OK;
 }
 
-// ---------------------------------------------------------------- scene ----
-
-int pt_scene_load_obj(const char* path, pt_scene** out) {
-  if (!path || !out) return fail(PT_ERR_INVALID, "null argument");
-  pt_scene* s = new pt_scene();
-  std::string err;
-  if (pt::load_obj_file(path, &s->obj, &err) != 0) {
-    delete s;
-    return fail(PT_ERR_IO, err);
-  }
-  *out = s;
-  return PT_OK;
-}
-
-int pt_scene_parse_obj(const char* text, size_t len, pt_scene** out) {
-  if (!text || !out) return fail(PT_ERR_INVALID, "null argument");
-  pt_scene* s = new pt_scene();
-  std::string err;
-  if (pt::parse_obj(text, len, &s->obj, &err) != 0) {
-    delete s;
-    return fail(PT_ERR_IO, err);
-  }
-  *out = s;
-  return PT_OK;
-}
-
-int pt_scene_from_arrays(const float* v, size_t nvf, const uint32_t* idx, size_t ni, pt_scene** out) {
-  if (!out || (nvf && !v) || (ni && !idx)) return fail(PT_ERR_INVALID, "null argument");
-  if (nvf % 3 || ni % 3) return fail(PT_ERR_SCENE, "sizes must be multiples of 3");
-  pt_scene* s = new pt_scene();
-  s->obj.vertices.assign(v, v + nvf);
-  s->obj.indices.assign(idx, idx + ni);
-  s->obj.materialIds.assign(ni / 3, 0u);
-  *out = s;
-  return PT_OK;
-}
-
-int pt_scene_build_bvh(pt_scene* s, uint32_t flags, int threads) {
-  if (!s) return fail(PT_ERR_INVALID, "null scene");
-  const size_t ni = s->obj.indices.size();
-  if (ni == 0 || ni % 3) return fail(PT_ERR_SCENE, "scene has no triangles");
-  pt::BVHOptions o;
-  o.encoding = (flags & PT_NODES_INT_BITS) ? pt::BVHEncoding::kIntBits : pt::BVHEncoding::kFloat;
-  o.threads = threads;
-  s->bvh_indices.assign(ni, 0);
-  s->nodes.assign(2 * (ni / 3) - 1, pt::BVHNode{});
-  std::string err;
-  if (pt::build_bvh(s->obj.vertices.data(), s->obj.vertices.size(), s->obj.indices.data(), ni,
-                    s->bvh_indices.data(), s->nodes.data(), o, &err) != 0) {
-    s->bvh_indices.clear();
-    s->nodes.clear();
-    return fail(PT_ERR_SCENE, err);
-  }
-  s->flags = flags;
-  return PT_OK;
-}
-
-int pt_scene_counts(const pt_scene* s, size_t* nvf, size_t* ni, size_t* nn, size_t* nuv, size_t* nmat) {
-  if (!s) return fail(PT_ERR_INVALID, "null scene");
-  if (nvf) *nvf = s->obj.vertices.size();
-  if (ni) *ni = s->obj.indices.size();
-  if (nn) *nn = s->nodes.size();
-  if (nuv) *nuv = s->obj.texcoords.size();
-  if (nmat) *nmat = s->obj.materialIds.size();
-  return PT_OK;
-}
-
-int pt_scene_copy(const pt_scene* s, float* v, uint32_t* idx, pt_bvh_node* nodes, float* uvs, uint32_t* mat) {
-  if (!s) return fail(PT_ERR_INVALID, "null scene");
-  if (v) memcpy(v, s->obj.vertices.data(), s->obj.vertices.size() * 4);
-  if (idx) {
-    const auto& src = s->nodes.empty() ? s->obj.indices : s->bvh_indices;   // BVH order once built
-    memcpy(idx, src.data(), src.size() * 4);
-  }
-  if (nodes) memcpy(nodes, s->nodes.data(), s->nodes.size() * sizeof(pt_bvh_node));
-  if (uvs) memcpy(uvs, s->obj.texcoords.data(), s->obj.texcoords.size() * 4);
-  if (mat) memcpy(mat, s->obj.materialIds.data(), s->obj.materialIds.size() * 4);
-  return PT_OK;
-}
-
-int pt_scene_upload(pt_context* c, const pt_scene* s) {
-  if (!c || !s) return fail(PT_ERR_INVALID, "null argument");
-  if (s->nodes.empty()) return fail(PT_ERR_INVALID, "build the BVH first (pt_scene_build_bvh)");
-  return pt_upload_scene(c, s->obj.vertices.data(), s->obj.vertices.size(), s->bvh_indices.data(),
-                         s->bvh_indices.size(), (const pt_bvh_node*)s->nodes.data(), s->nodes.size(),
-                         s->obj.texcoords.data(), s->obj.texcoords.size(), s->obj.materialIds.data(),
-                         s->obj.materialIds.size(), s->flags);
-}
-
-// ---- binary scene cache ---------------------------------
-// Skips OBJ parsing and the BVH build for large meshes.  Layout: "PTSCENE1",
-// u32 version, u32 flags (PT_NODES_INT_BITS), u64 counts of vertex floats,
-// OBJ indices, BVH-order indices, nodes, uv floats, material ids, u64 shapes,
-// then the six arrays, then a u64 FNV-1a hash of everything before it (taken
-// over 8-byte words, the tail bytewise).
-namespace {
-constexpr char kCacheMagic[8] = {'P', 'T', 'S', 'C', 'E', 'N', 'E', '1'};
-constexpr uint32_t kCacheVersion = 1;
-
-struct Fnv {
-  uint64_t h = 1469598103934665603ull;
-  void add(const void* p, size_t n) {
-    const unsigned char* b = (const unsigned char*)p;
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-      uint64_t w;
-      memcpy(&w, b + i, 8);
-      h = (h ^ w) * 1099511628211ull;
-    }
-    for (; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-  }
-};
-}  // namespace
-
-int pt_scene_save(const pt_scene* s, const char* path) {
-  if (!s || !path) return fail(PT_ERR_INVALID, "null argument");
-  if (s->nodes.empty()) return fail(PT_ERR_INVALID, "build the BVH first (pt_scene_build_bvh)");
-  FILE* f = fopen(path, "wb");
-  if (!f) return fail(PT_ERR_IO, std::string("cannot create ") + path);
-  Fnv h;
-  bool ok = true;
-  auto put = [&](const void* p, size_t n) {
-    if (n && ok) ok = fwrite(p, 1, n, f) == n;
-    h.add(p, n);
-  };
-  const uint64_t counts[7] = {s->obj.vertices.size(), s->obj.indices.size(), s->bvh_indices.size(), s->nodes.size(),
-                              s->obj.texcoords.size(), s->obj.materialIds.size(), (uint64_t)s->obj.shapes};
-  put(kCacheMagic, 8);
-  put(&kCacheVersion, 4);
-  put(&s->flags, 4);
-  put(counts, sizeof counts);
-  put(s->obj.vertices.data(), counts[0] * 4);
-  put(s->obj.indices.data(), counts[1] * 4);
-  put(s->bvh_indices.data(), counts[2] * 4);
-  put(s->nodes.data(), counts[3] * sizeof(pt::BVHNode));
-  put(s->obj.texcoords.data(), counts[4] * 4);
-  put(s->obj.materialIds.data(), counts[5] * 4);
-  const uint64_t digest = h.h;
-  if (ok) ok = fwrite(&digest, 1, 8, f) == 8;
-  if (fclose(f) != 0) ok = false;
-  if (!ok) return fail(PT_ERR_IO, std::string("write failed: ") + path);
-  return PT_OK;
-}
-
-int pt_scene_load_cache(const char* path, pt_scene** out) {
-  if (!path || !out) return fail(PT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  FILE* f = fopen(path, "rb");
-  if (!f) return fail(PT_ERR_IO, std::string("cannot open ") + path);
-  Fnv h;
-  bool ok = true;
-  auto get = [&](void* p, size_t n) {
-    if (n && ok) ok = fread(p, 1, n, f) == n;
-    if (ok) h.add(p, n);
-  };
-  char magic[8];
-  uint32_t version = 0, flags = 0;
-  uint64_t counts[7] = {0};
-  get(magic, 8);
-  get(&version, 4);
-  get(&flags, 4);
-  get(counts, sizeof counts);
-  if (!ok || memcmp(magic, kCacheMagic, 8) != 0 || version != kCacheVersion) {
-    fclose(f);
-    return fail(PT_ERR_IO, std::string("not a scene cache (or another version): ") + path);
-  }
-  const uint64_t nt = counts[1] / 3;
-  if (counts[0] % 3 || counts[1] % 3 || counts[1] == 0 || counts[2] != counts[1] || counts[3] != 2 * nt - 1 ||
-      counts[5] > (1ull << 34) || counts[0] > (1ull << 36) || counts[4] > (1ull << 36)) {
-    fclose(f);
-    return fail(PT_ERR_IO, std::string("inconsistent scene cache header: ") + path);
-  }
-  pt_scene* s = new pt_scene();
-  s->flags = flags;
-  s->obj.vertices.resize(counts[0]);
-  s->obj.indices.resize(counts[1]);
-  s->bvh_indices.resize(counts[2]);
-  s->nodes.resize(counts[3]);
-  s->obj.texcoords.resize(counts[4]);
-  s->obj.materialIds.resize(counts[5]);
-  s->obj.shapes = (size_t)counts[6];
-  get(s->obj.vertices.data(), counts[0] * 4);
-  get(s->obj.indices.data(), counts[1] * 4);
-  get(s->bvh_indices.data(), counts[2] * 4);
-  get(s->nodes.data(), counts[3] * sizeof(pt::BVHNode));
-  get(s->obj.texcoords.data(), counts[4] * 4);
-  get(s->obj.materialIds.data(), counts[5] * 4);
-  uint64_t digest = 0;
-  const uint64_t want = h.h;
-  if (ok) ok = fread(&digest, 1, 8, f) == 8;
-  fclose(f);
-  if (!ok || digest != want) {
-    delete s;
-    return fail(PT_ERR_IO, std::string("scene cache truncated or corrupt: ") + path);
-  }
-  *out = s;
-  return PT_OK;
-}
-
-// ---- image output ----------------------------------------
-namespace {
-uint32_t crc32_update(uint32_t crc, const unsigned char* p, size_t n) {
-  static uint32_t table[256];
-  static bool init = false;
-  if (!init) {
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-      table[i] = c;
-    }
-    init = true;
-  }
-  for (size_t i = 0; i < n; ++i) crc = table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
-  return crc;
-}
-
-void put_be32(std::vector<unsigned char>* o, uint32_t v) {
-  for (int s = 24; s >= 0; s -= 8) o->push_back((unsigned char)(v >> s));
-}
-
-void png_chunk(FILE* f, const char* type, const std::vector<unsigned char>& data, bool* ok) {
-  std::vector<unsigned char> buf;
-  put_be32(&buf, (uint32_t)data.size());
-  buf.insert(buf.end(), type, type + 4);
-  buf.insert(buf.end(), data.begin(), data.end());
-  const uint32_t crc = crc32_update(0xffffffffu, buf.data() + 4, buf.size() - 4) ^ 0xffffffffu;
-  put_be32(&buf, crc);
-  if (*ok) *ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-}
-
-// linear -> 8-bit sRGB after clamping to [0,1]: what an sRGB swapchain shows
-// for the reference's RGBA32F image (VulkanRenderer copies it to a texture
-// that color_frag.frag outputs unchanged)
-unsigned char srgb8(float x) {
-  if (!(x > 0.0f)) return 0;
-  if (x >= 1.0f) return 255;
-  const double e = x <= 0.0031308f ? 12.92 * x : 1.055 * pow((double)x, 1.0 / 2.4) - 0.055;
-  return (unsigned char)(e * 255.0 + 0.5);
-}
-}  // namespace
-
-int pt_write_image(const char* path, const float* rgba, int w, int h, int format) {
-  if (!path || !rgba) return fail(PT_ERR_INVALID, "null argument");
-  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
-  if (format != PT_IMAGE_PFM && format != PT_IMAGE_PNG) return fail(PT_ERR_INVALID, "unknown image format");
-  FILE* f = fopen(path, "wb");
-  if (!f) return fail(PT_ERR_IO, std::string("cannot create ") + path);
-  bool ok = true;
-  if (format == PT_IMAGE_PFM) {
-    // rows bottom-to-top: row y = 0 of the accumulation buffer is written first
-    ok = fprintf(f, "PF\n%d %d\n-1.0\n", w, h) > 0;
-    std::vector<float> rgb((size_t)w * 3);
-    for (int y = 0; y < h && ok; ++y) {
-      for (int x = 0; x < w; ++x)
-        for (int c = 0; c < 3; ++c) rgb[(size_t)x * 3 + c] = rgba[((size_t)y * w + x) * 4 + c];
-      ok = fwrite(rgb.data(), 4, rgb.size(), f) == rgb.size();
-    }
-  } else {
-    // 8-bit RGB PNG, zlib stream of stored (uncompressed) deflate blocks;
-    // rows top-to-bottom, so the accumulation buffer's last row comes first
-    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    ok = fwrite(sig, 1, 8, f) == 8;
-    std::vector<unsigned char> ihdr;
-    put_be32(&ihdr, (uint32_t)w);
-    put_be32(&ihdr, (uint32_t)h);
-    ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});   // 8-bit, truecolour, deflate, filter 0, no interlace
-    png_chunk(f, "IHDR", ihdr, &ok);
-    std::vector<unsigned char> raw;
-    raw.reserve((size_t)h * (1 + 3 * (size_t)w));
-    for (int y = h - 1; y >= 0; --y) {
-      raw.push_back(0);   // filter: none
-      for (int x = 0; x < w; ++x)
-        for (int c = 0; c < 3; ++c) raw.push_back(srgb8(rgba[((size_t)y * w + x) * 4 + c]));
-    }
-    std::vector<unsigned char> z = {0x78, 0x01};
-    uint32_t a = 1, b = 0;   // Adler-32
-    for (size_t i = 0; i < raw.size(); ++i) {
-      a = (a + raw[i]) % 65521u;
-      b = (b + a) % 65521u;
-    }
-    for (size_t off = 0; off < raw.size() || off == 0; off += 65535) {
-      const size_t n = std::min<size_t>(65535, raw.size() - off);
-      z.push_back(off + n >= raw.size() ? 1 : 0);
-      z.push_back((unsigned char)(n & 0xff));
-      z.push_back((unsigned char)(n >> 8));
-      z.push_back((unsigned char)(~n & 0xff));
-      z.push_back((unsigned char)((~n >> 8) & 0xff));
-      z.insert(z.end(), raw.begin() + (long)off, raw.begin() + (long)(off + n));
-      if (raw.empty()) break;
-    }
-    put_be32(&z, (b << 16) | a);
-    png_chunk(f, "IDAT", z, &ok);
-    png_chunk(f, "IEND", {}, &ok);
-  }
-  if (fclose(f) != 0) ok = false;
-  if (!ok) return fail(PT_ERR_IO, std::string("write failed: ") + path);
-  return PT_OK;
-}
-
-int pt_scene_free(pt_scene* s) {
-  delete s;
-  return PT_OK;
-}
-
-int pt_pack_light(const float pos[3], const float nrm[3], const float inten[3], const float size[2],
-                  pt_area_light* out) {
-  if (!pos || !nrm || !inten || !size || !out) return fail(PT_ERR_INVALID, "null argument");
-  pt::Light l({{pos[0], pos[1], pos[2]}}, {{nrm[0], nrm[1], nrm[2]}}, {{inten[0], inten[1], inten[2]}},
-              {{size[0], size[1]}});
-  memcpy(out, &l.getLights()[0], sizeof *out);
-  return PT_OK;
-}
-
-int pt_primary_cull_rects(const float cam[16], int w, int h, const float root_min[3], const float root_max[3],
-                          const pt_area_light* lights, int n_lights, float* rects, int max_rects, int* n_rects) {
-  if (!cam || !root_min || !root_max || !rects || !n_rects || (n_lights > 0 && !lights))
-    return fail(PT_ERR_INVALID, "null argument");
-  if (max_rects < 1) return fail(PT_ERR_INVALID, "max_rects must be >= 1");
-  *n_rects = cull_rects(cam, w, h, root_min, root_max, lights, n_lights, rects, max_rects);
-  return PT_OK;
-}
-
-int pt_primary_cull_rects_r(const float cam[16], int w, int h, const float root_min[3], const float root_max[3],
-                            const pt_area_light* lights, int n_lights, double radius_bound, float* rects,
-                            int max_rects, int* n_rects, float* u0) {
-  if (!cam || !root_min || !root_max || !rects || !n_rects || (n_lights > 0 && !lights))
-    return fail(PT_ERR_INVALID, "null argument");
-  if (max_rects < 1) return fail(PT_ERR_INVALID, "max_rects must be >= 1");
-  const double R = radius_bound < 0.0 ? ptd::kCullTightR : radius_bound;
-  if (!(R <= ptd::kGaussR)) return fail(PT_ERR_INVALID, "radius bound above 13.25");
-  *n_rects = cull_rects(cam, w, h, root_min, root_max, lights, n_lights, rects, max_rects, R);
-  if (u0) *u0 = ptd::kCullTightU0;
-  return PT_OK;
-}
-
 int pt_partition_items(int w, int h, int spl, int nranks, int rank, const int* slots, const float* cull_rects,
                        int n_cull, int item_order, int* live, size_t* n_live, int* culled, size_t* n_culled,
                        int* pixel_of) {
@@ -3506,7 +1862,7 @@ int pt_partition_items(int w, int h, int spl, int nranks, int rank, const int* s
   for (int r = 0; r < n_cull; ++r)
     for (int k = 0; k < 4; ++k) p.cull[r][k] = cull_rects[4 * r + k];
   p.item_order = item_order;
-  const ptd::Part pt = part_of_slots(sl, rank);
+  const ptd::Part pt = parts_of_slots(sl)[(size_t)rank];
   std::vector<int> lv, cu;
   item_lists(p, pt, &lv, &cu);
   if ((live && *n_live < lv.size()) || (culled && *n_culled < cu.size()))
@@ -3529,422 +1885,6 @@ int pt_partition_items(int w, int h, int spl, int nranks, int rank, const int* s
   }
   *n_live = lv.size();
   *n_culled = cu.size();
-  return PT_OK;
-}
-
-int pt_default_camera(float ubo[16]) {
-  if (!ubo) return fail(PT_ERR_INVALID, "null argument");
-  pt::Camera cam;
-  cam.toUBO(ubo);
-  return PT_OK;
-}
-
-}  // extern "C"
-
-// ===========================================================================
-// Native multi-GPU step loop: the tile split's frames with the
-// RCCL gather issued from C++, so a run of frames costs no Python per frame.
-// bench.py's Python step (render_packed + torch.distributed.gather + stream
-// switches) costs ~40-50 us of host time per frame, more than the ~40-us GPU
-// step of a 1/8 box.obj share; here one frame is a render_packed launch, two
-// event operations and one grouped send/recv.
-// ===========================================================================
-namespace {
-struct RcclApi {
-  void* h = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommCount)(ncclComm_t, int*) = nullptr;   // optional (the tests' stand-in may lack it)
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*CommAbort)(ncclComm_t) = nullptr;
-  ncclResult_t (*GroupStart)() = nullptr;
-  ncclResult_t (*GroupEnd)() = nullptr;
-  ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-// RCCL is loaded only when the multi-GPU loop is used: the one already in
-// the process (torch's) if there is one, else the system's.  PT_RCCL_LIB
-// names another library with the same nine entry points instead, and then
-// only that one is tried (the tests' one-GPU stand-in, tests/dist_shim.cpp,
-// which moves the point-to-point bytes between processes sharing a device).
-const RcclApi* rccl_api() {
-  static RcclApi api;
-  static bool tried = false;
-  if (!tried) {
-    tried = true;
-    const char* alt = getenv("PT_RCCL_LIB");
-    void* h = nullptr;
-    if (alt && *alt) {
-      h = dlopen(alt, RTLD_NOW | RTLD_LOCAL);
-    } else {
-      h = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-      if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-      if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    }
-    if (h) {
-      api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(h, "ncclGetUniqueId");
-      api.CommInitRank = (decltype(api.CommInitRank))dlsym(h, "ncclCommInitRank");
-      api.CommCount = (decltype(api.CommCount))dlsym(h, "ncclCommCount");
-      api.CommDestroy = (decltype(api.CommDestroy))dlsym(h, "ncclCommDestroy");
-      api.CommAbort = (decltype(api.CommAbort))dlsym(h, "ncclCommAbort");
-      api.GroupStart = (decltype(api.GroupStart))dlsym(h, "ncclGroupStart");
-      api.GroupEnd = (decltype(api.GroupEnd))dlsym(h, "ncclGroupEnd");
-      api.Send = (decltype(api.Send))dlsym(h, "ncclSend");
-      api.Recv = (decltype(api.Recv))dlsym(h, "ncclRecv");
-      api.GetErrorString = (decltype(api.GetErrorString))dlsym(h, "ncclGetErrorString");
-      if (api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.CommAbort && api.GroupStart && api.GroupEnd && api.Send &&
-          api.Recv && api.GetErrorString)
-        api.h = h;
-    }
-  }
-  return api.h ? &api : nullptr;
-}
-#define PT_NCCL(call)                                                                                   \
-  do {                                                                                                  \
-    ncclResult_t r_ = (call);                                                                           \
-    if (r_ != ncclSuccess) return fail(PT_ERR_HIP, std::string(#call ": ") + R->GetErrorString(r_));    \
-  } while (0)
-
-// Slot size and buffers for the layout of the last rendered frame (c->last).
-int dist_layout(pt_context* c) {
-  DistState* d = c->dist;
-  std::vector<float> key;
-  frame_key(c, c->last, &key);
-  // (the root has no send slots: its layout is valid once any buffer was
-  // sized for it; testing send[0] made the root rebuild every rank's item
-  // lists on every call, ~0.45 ms of host time per call at N = 8)
-  if (key == d->layout_key && d->cap_floats > 0) return PT_OK;
-  size_t live_max = 0;
-  std::vector<int> live, culled;
-  for (int r = 0; r < c->nranks; ++r) {
-    item_lists(c->last, part_of(c, r), &live, &culled);
-    live_max = std::max(live_max, live.size());
-  }
-  const size_t slot = std::max<size_t>(4, live_max * (size_t)(256 / c->last.spl) * 4);
-  const size_t nslots = (size_t)c->nranks;   // the partition's ranks (emulation: > d->nranks)
-  if (slot > d->cap_floats) {
-    for (int b = 0; b < kDistStreams; ++b)
-      for (hipStream_t s : {d->streams[b], d->comm_stream}) PT_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < kDistStreams; ++b) dev_free(d->send[b]);
-    for (int b = 0; b < kDistSets; ++b) dev_free(d->recv[b]);
-    dev_free(d->ingest);
-    d->cap_floats = 0;
-    for (int b = 0; b < kDistStreams && d->rank != 0; ++b) {
-      PT_HIP(hipMalloc((void**)&d->send[b], slot * sizeof(float)));
-      PT_HIP(hipMemset(d->send[b], 0, slot * sizeof(float)));
-    }
-    for (int b = 0; b < kDistSets && d->rank == 0; ++b) {
-      PT_HIP(hipMalloc((void**)&d->recv[b], nslots * slot * sizeof(float)));
-      PT_HIP(hipMemset(d->recv[b], 0, nslots * slot * sizeof(float)));
-    }
-    if (d->nranks == 1 && nslots > 1) {
-      PT_HIP(hipMalloc((void**)&d->ingest, (nslots - 1) * slot * sizeof(float)));
-      PT_HIP(hipMemset(d->ingest, 0, (nslots - 1) * slot * sizeof(float)));
-    }
-    d->cap_floats = slot;
-  }
-  d->slot_floats = slot;
-  d->layout_key = key;
-  return PT_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int pt_dist_unique_id(void* id, size_t id_bytes) {
-  if (!id || id_bytes < sizeof(ncclUniqueId)) return fail(PT_ERR_INVALID, "id buffer must hold 128 bytes");
-  const RcclApi* R = rccl_api();
-  if (!R) return fail(PT_ERR_UNSUPPORTED, "RCCL (librccl.so.1) could not be loaded");
-  ncclUniqueId u;
-  PT_NCCL(R->GetUniqueId(&u));
-  memcpy(id, &u, sizeof u);
-  return PT_OK;
-}
-
-int pt_dist_init(pt_context* c, const void* id, int nranks, int rank) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_init: not on a multi-device context (pt_create_multi)");
-  if (!c || !id) return fail(PT_ERR_INVALID, "null argument");
-  const bool emulated = nranks == 1 && rank == 0 && c->rank == 0 && c->nranks > 1;
-  if (!emulated && (nranks != c->nranks || rank != c->rank))
-    return fail(PT_ERR_INVALID, "pt_dist_init: set the same partition first (pt_set_partition / _slots)");
-  const RcclApi* R = rccl_api();
-  if (!R) return fail(PT_ERR_UNSUPPORTED, "RCCL (librccl.so.1) could not be loaded");
-  if (c->dist) pt_dist_finalize(c);
-  PT_HIP(hipSetDevice(c->device));
-  DistState* d = new DistState();
-  c->dist = d;
-  d->nranks = nranks;
-  d->rank = rank;
-  int lo = 0, hi = 0;
-  PT_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  PT_HIP(hipStreamCreateWithPriority(&d->own[kDistStreams], hipStreamNonBlocking, hi));   // gathers take CUs first
-  // the two render streams at the least priority: the HIP runtime gives each
-  // priority its own pool of GPU_MAX_HW_QUEUES hardware queues, so these two
-  // get a queue each instead of sharing one with the process's other streams
-  // (two frames on one queue do not overlap)
-  for (int b = 0; b < kDistStreams; ++b) {
-    PT_HIP(hipStreamCreateWithPriority(&d->own[b], hipStreamNonBlocking, lo));
-    d->streams[b] = d->own[b];
-  }
-  d->comm_stream = d->own[kDistStreams];
-  for (int b = 0; b < kDistSets; ++b) {
-    PT_HIP(hipEventCreateWithFlags(&d->render_done[b], hipEventDisableTiming));
-    PT_HIP(hipEventCreateWithFlags(&d->gather_done[b], hipEventDisableTiming));
-  }
-  for (hipEvent_t& e : d->entry) PT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  ncclUniqueId u;
-  memcpy(&u, id, sizeof u);
-  PT_NCCL(R->CommInitRank(&d->comm, nranks, u, rank));
-  if (R->CommCount) {
-    int cnt = -1;
-    if (R->CommCount(d->comm, &cnt) == ncclSuccess) d->comm_count = cnt;
-  }
-  d->ready = true;
-  return PT_OK;
-}
-
-int pt_dist_info(pt_context* c, int* comm_ranks, int* nranks, int* rank) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_info: not on a multi-device context (pt_create_multi)");
-  if (!c || !c->dist) return fail(PT_ERR_INVALID, "pt_dist_info: no communicator (pt_dist_init)");
-  if (comm_ranks) *comm_ranks = c->dist->comm_count;
-  if (nranks) *nranks = c->dist->nranks;
-  if (rank) *rank = c->dist->rank;
-  return PT_OK;
-}
-
-// Whether frame buffer `frame` already holds a whole assembled frame of the
-// layout `key` (its culled items' constant included).
-static bool dist_assembled(const DistState* d, const void* frame, const std::vector<float>& key) {
-  for (const auto& e : d->assembled)
-    if (e.first == frame) return e.second == key;
-  return false;
-}
-static void dist_mark_assembled(DistState* d, const void* frame, const std::vector<float>& key) {
-  for (auto& e : d->assembled)
-    if (e.first == frame) {
-      e.second = key;
-      return;
-    }
-  d->assembled.push_back({frame, key});
-}
-
-int pt_dist_run(pt_context* c, uint32_t n_batches, int n_frames, int n_streams, void* frames, int n_frame_bufs) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_run: not on a multi-device context (pt_create_multi)");
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  if (c->opt_moments) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with pt_dist_run");
-  DistState* d = c->dist;
-  if (!d || !d->ready) return fail(PT_ERR_INVALID, "pt_dist_run: no communicator (pt_dist_init)");
-  if (n_frames < 0 || n_batches == 0) return fail(PT_ERR_INVALID, "pt_dist_run: bad frame or batch count");
-  if (d->rank == 0 && (!frames || n_frame_bufs < 1 || (((uintptr_t)frames) & 15)))
-    return fail(PT_ERR_INVALID, "pt_dist_run: the root needs 16-B aligned frame buffers");
-  if (n_streams < 1 || n_streams > kDistStreams) return fail(PT_ERR_INVALID, "pt_dist_run: 1 to 3 streams");
-  if (d->caller_streams && n_streams > 2)
-    return fail(PT_ERR_INVALID, "pt_dist_run: 3 streams with caller render streams (pt_dist_set_streams sets two)");
-  const bool emulated = d->nranks == 1 && c->nranks > 1;
-  if ((d->nranks != c->nranks && !emulated) || d->rank != c->rank)
-    return fail(PT_ERR_INVALID, "partition changed since pt_dist_init");
-  if (!c->last_valid) return fail(PT_ERR_INVALID, "pt_dist_run: render one frame with pt_render first (item layout)");
-  const RcclApi* R = rccl_api();
-  PT_HIP(hipSetDevice(c->device));
-  {
-    const int rc = dist_layout(c);
-    if (rc) return rc;
-  }
-  const size_t slot = d->slot_floats;
-  const size_t frame_f = (size_t)c->width * c->height * 4;
-  hipStream_t saved = c->stream;
-  int rc = PT_OK;
-  // D = max(2, streams) frames in flight.  Frame k runs on stream k % S
-  // with buffer set k % 2D.  Its launch (pt_render_packed) writes this rank's
-  // live items -- on the root straight into its own slot of receive set
-  // k % 2D, elsewhere into send slot k % D -- and, on the root, assembles
-  // frame k-D from receive set (k-D) % 2D, after waiting for that frame's
-  // gather.  Hazards: the gather of frame k (comm stream, after frame k's
-  // launch) overwrites set k % 2D, which frame k-D's launch read -- earlier
-  // on frame k's own stream (S divides D: S = 1 or D); a send slot is read by
-  // the gather of frame k-D, which frame k's launch waits for.
-  const int D = std::max(2, n_streams), nsets = 2 * D;
-  // Those hazards hold within a call.  Across calls, frame k < D of this call
-  // has no gather_done to wait for: a previous call's last sends (comm stream)
-  // may still read send slot k % D, and its trailing assemblies (other render
-  // streams) may still write the frame buffers.  So every render stream
-  // starts behind every stream's last work of the previous call.
-  {
-    hipStream_t all[kDistStreams + 1];
-    for (int s = 0; s < kDistStreams; ++s) all[s] = d->streams[s];
-    all[kDistStreams] = d->comm_stream;
-    for (int s = 0; s <= kDistStreams; ++s) PT_HIP(hipEventRecord(d->entry[s], all[s]));
-    for (int s = 0; s < n_streams; ++s)
-      for (int e = 0; e <= kDistStreams; ++e)
-        if (all[e] != d->streams[s]) PT_HIP(hipStreamWaitEvent(d->streams[s], d->entry[e], 0));
-  }
-  c->in_dist = true;
-  const bool self_p2p = emulated && getenv("PT_DIST_EMU_P2P") && atoi(getenv("PT_DIST_EMU_P2P")) == 1;
-  // frames after the first of each kind (with and without an assembly) reuse
-  // its launch parameters: nothing but the output and the assembled frame
-  // change within a call (relaunch)
-  Launched tmpl[2];
-  for (int k = 0; k < n_frames && rc == PT_OK; ++k) {
-    const int b = k % nsets;
-    c->stream = d->streams[k % n_streams];
-    Assembly as;
-    if (k >= D) {
-      const int pb = (k - D) % nsets;
-      PT_HIP(hipStreamWaitEvent(c->stream, d->gather_done[pb], 0));
-      if (d->rank == 0) {
-        as.src = d->recv[pb];
-        as.slot_floats = slot;
-        as.frame = (float*)frames + (size_t)((k - D) % n_frame_bufs) * frame_f;
-      }
-    }
-    float4* out = (float4*)(d->rank == 0 ? d->recv[b] : d->send[k % D]);
-    Launched& t = tmpl[as.src ? 1 : 0];
-    if (t.valid) {
-      ptd::RenderParams p = t.p;
-      p.pack_out = out;
-      p.unpack_src = (const float4*)as.src;
-      p.unpack_frame = (float4*)as.frame;
-      if (as.src && dist_assembled(d, as.frame, c->unpack_key)) {   // live items only
-        p.unpack_table = c->d_unpack_live;
-        p.n_unpack = c->n_unpack_live;
-      } else if (as.src) {
-        p.unpack_table = c->d_unpack;
-        p.n_unpack = c->n_unpack;
-        dist_mark_assembled(d, as.frame, c->unpack_key);
-      }
-      rc = relaunch(c, p, t.lds, t.cnt);
-    } else {
-      rc = render_impl(c, 0, n_batches, out, as, &t);   // a whole assembly (the full table)
-      if (rc == PT_OK && as.src) dist_mark_assembled(d, as.frame, c->unpack_key);
-    }
-    if (rc) break;
-    PT_HIP(hipEventRecord(d->render_done[b], c->stream));
-    PT_HIP(hipStreamWaitEvent(d->comm_stream, d->render_done[b], 0));
-    if (emulated && self_p2p) {
-      // measurement (PT_DIST_EMU_P2P=1): the other ranks' slots through
-      // RCCL itself -- one grouped self send/recv per emulated rank, the
-      // calls the root's real gather makes -- so the emulated step carries
-      // RCCL's host and device cost per frame
-      PT_NCCL(R->GroupStart());
-      for (int r = 1; r < c->nranks; ++r) {
-        PT_NCCL(R->Send(d->ingest + (size_t)(r - 1) * slot, slot, ncclFloat32, 0, d->comm, d->comm_stream));
-        PT_NCCL(R->Recv(d->recv[b] + (size_t)r * slot, slot, ncclFloat32, 0, d->comm, d->comm_stream));
-      }
-      PT_NCCL(R->GroupEnd());
-    } else if (emulated) {   // the other ranks' slots: the bytes a real gather would write here
-      PT_HIP(hipMemcpyAsync(d->recv[b] + slot, d->ingest, (size_t)(c->nranks - 1) * slot * sizeof(float),
-                            hipMemcpyDeviceToDevice, d->comm_stream));
-    }
-    if (d->nranks > 1) {
-      PT_NCCL(R->GroupStart());
-      if (d->rank == 0)
-        for (int r = 1; r < d->nranks; ++r)
-          PT_NCCL(R->Recv(d->recv[b] + (size_t)r * slot, slot, ncclFloat32, r, d->comm, d->comm_stream));
-      else
-        PT_NCCL(R->Send(d->send[k % D], slot, ncclFloat32, 0, d->comm, d->comm_stream));
-      PT_NCCL(R->GroupEnd());
-    }
-    PT_HIP(hipEventRecord(d->gather_done[b], d->comm_stream));
-  }
-  c->in_dist = false;
-  // the root assembles the last (up to) D frames in launches of their own
-  if (rc == PT_OK && d->rank == 0) {
-    frame_key(c, c->last, &c->key_scratch);
-    rc = unpack_table(c, c->last, c->key_scratch);
-    for (int k = std::max(0, n_frames - D); k < n_frames && rc == PT_OK; ++k) {
-      const int b = k % nsets;
-      c->stream = d->streams[k % n_streams];
-      PT_HIP(hipStreamWaitEvent(c->stream, d->gather_done[b], 0));
-      float4* out = (float4*)((float*)frames + (size_t)(k % n_frame_bufs) * frame_f);
-      const bool live_only = dist_assembled(d, out, c->unpack_key);
-      PT_HIP(ptd::launch_items_unpack(c->last, out, (const float4*)d->recv[b], slot / 4,
-                                      live_only ? c->d_unpack_live : c->d_unpack,
-                                      live_only ? c->n_unpack_live : c->n_unpack, c->stream));
-      if (!live_only) dist_mark_assembled(d, out, c->unpack_key);
-    }
-  }
-  // one use event per stream for the whole run (the launches above skip theirs)
-  for (int sidx = 0; sidx < n_streams && rc == PT_OK; ++sidx) {
-    c->stream = d->streams[sidx];
-    rc = note_use(c);
-  }
-  c->stream = saved;
-  return rc;
-}
-
-int pt_dist_set_streams(pt_context* c, void* render0, void* render1, void* comm) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_set_streams: not on a multi-device context (pt_create_multi)");
-  if (!c || !c->dist) return fail(PT_ERR_INVALID, "pt_dist_set_streams: no communicator (pt_dist_init)");
-  DistState* d = c->dist;
-  PT_HIP(hipSetDevice(c->device));
-  for (hipStream_t s : {d->streams[0], d->streams[1], d->streams[2], d->comm_stream}) PT_HIP(hipStreamSynchronize(s));
-  d->streams[0] = render0 ? (hipStream_t)render0 : d->own[0];
-  d->streams[1] = render1 ? (hipStream_t)render1 : d->own[1];
-  d->caller_streams = render0 || render1;
-  d->comm_stream = comm ? (hipStream_t)comm : d->own[kDistStreams];
-  return PT_OK;
-}
-
-int pt_dist_slot_floats(pt_context* c, size_t* slot_floats) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_slot_floats: not on a multi-device context (pt_create_multi)");
-  if (!c || !slot_floats) return fail(PT_ERR_INVALID, "null argument");
-  if (!c->dist || !c->dist->slot_floats) return fail(PT_ERR_INVALID, "no pt_dist_run yet");
-  *slot_floats = c->dist->slot_floats;
-  return PT_OK;
-}
-
-int pt_dist_wait(pt_context* c, int timeout_ms) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_wait: not on a multi-device context (pt_create_multi)");
-  if (!c || !c->dist) return fail(PT_ERR_INVALID, "pt_dist_wait: no communicator");
-  DistState* d = c->dist;
-  PT_HIP(hipSetDevice(c->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    bool done = true;
-    for (hipStream_t s : {d->streams[0], d->streams[1], d->streams[2], d->comm_stream}) {
-      const hipError_t q = hipStreamQuery(s);
-      if (q == hipErrorNotReady) done = false;
-      else if (q != hipSuccess) return fail(PT_ERR_HIP, std::string("pt_dist_wait: ") + hipGetErrorString(q));
-    }
-    if (done) return PT_OK;
-    const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-    if (timeout_ms >= 0 && ms > timeout_ms) return fail(PT_ERR_HIP, "pt_dist_wait: timed out (gather not complete)");
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-  }
-}
-
-int pt_dist_abort(pt_context* c) {
-  if (c && c->group) return fail(PT_ERR_UNSUPPORTED, "pt_dist_abort: not on a multi-device context (pt_create_multi)");
-  if (!c || !c->dist) return PT_OK;
-  const RcclApi* R = rccl_api();
-  if (c->dist->comm && R) (void)R->CommAbort(c->dist->comm);   // ends outstanding transfers
-  c->dist->comm = nullptr;
-  return pt_dist_finalize(c);
-}
-
-int pt_dist_finalize(pt_context* c) {
-  if (!c) return fail(PT_ERR_INVALID, "null context");
-  DistState* d = c->dist;
-  if (!d) return PT_OK;
-  (void)hipSetDevice(c->device);
-  for (hipStream_t s : {d->streams[0], d->streams[1], d->streams[2], d->comm_stream})
-    if (s) (void)hipStreamSynchronize(s);
-  const RcclApi* R = rccl_api();
-  if (d->comm && R) (void)R->CommDestroy(d->comm);
-  dev_free(d->ingest);
-  for (int b = 0; b < kDistStreams; ++b) dev_free(d->send[b]);
-  for (hipStream_t s : d->own)
-    if (s) (void)hipStreamDestroy(s);
-  for (int b = 0; b < kDistSets; ++b) {
-    dev_free(d->recv[b]);
-    if (d->render_done[b]) (void)hipEventDestroy(d->render_done[b]);
-    if (d->gather_done[b]) (void)hipEventDestroy(d->gather_done[b]);
-  }
-  for (hipEvent_t e : d->entry)
-    if (e) (void)hipEventDestroy(e);
-  delete d;
-  c->dist = nullptr;
   return PT_OK;
 }
 

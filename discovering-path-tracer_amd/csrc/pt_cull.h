@@ -1,8 +1,10 @@
 // pt_cull.h — the radius bounds of primary-ray culling, shared by the host
-// derivation (pt_api.cpp cull_rects), the render kernel's per-sample test
+// derivation (pt_cull.cpp cull_rects), the render kernel's per-sample test
 // (pt_device.hip) and tests/cull_radius_check.cpp.
 #pragma once
 #include "pt_math.h"
+
+struct pt_area_light;   // include/pathtracer.h
 
 namespace ptd {
 
@@ -30,5 +32,13 @@ PT_FN float cull_radius(float u) { return ptm::sqrt_(-2.0f * ptm::log_(ptm::fmax
 // below it gives 4.25000048).  A draw u1 >= kCullTightU0 has its radius within
 // the tight bound.
 constexpr float kCullTightU0 = PT_CULL_TIGHT_U0;
+
+// The cull rectangles of a frame (pt_cull.cpp, host only): {x0, x1, y0, y1} in
+// NDC for the root box lo..hi, then for each light.  Returns the rectangle
+// count (>= 0) or -1 when no guarantee is derived.  Rg: the bound on the
+// Box-Muller radii the rectangles hold for.
+__attribute__((visibility("hidden"))) int cull_rects(const float cam[16], int W, int H, const float* lo,
+                                                     const float* hi, const pt_area_light* lights, int n_lights,
+                                                     float* rects, int max_rects, double Rg = kGaussR);
 
 }  // namespace ptd

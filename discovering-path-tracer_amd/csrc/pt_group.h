@@ -1,5 +1,6 @@
-// pt_group.h — internal interface between the C-ABI shim (pt_api.cpp) and
-// the single-process multi-device context (pt_group.cpp, pt_create_multi).
+// pt_group.h — internal interface between the C-ABI shim (pt_api.cpp and the
+// files beside it, pt_context.h) and the single-process multi-device context
+// (pt_group.cpp, pt_create_multi).
 //
 // A group is a pt_context whose calls the shim forwards here.  The group
 // drives one ordinary context per member device through the public C ABI,

@@ -4,8 +4,8 @@
 //
 //   S="-O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off \
 //      -fno-fast-math -D__HIP_PLATFORM_AMD__ -Iinclude -Idiscovering-path-tracer_amd/csrc"
-//   for f in tests/denoise_var_check.cpp discovering-path-tracer_amd/csrc/pt_api.cpp \
-//            discovering-path-tracer_amd/csrc/pt_group.cpp discovering-path-tracer_amd/csrc/scene/*.cpp; do
+//   for f in tests/denoise_var_check.cpp discovering-path-tracer_amd/csrc/*.cpp \
+//            discovering-path-tracer_amd/csrc/scene/*.cpp; do
 //     hipcc $S -c $f -o san/$(basename $f .cpp).o; done          # host objects, instrumented
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined san/*.o \
 //     discovering-path-tracer_amd/build/pt_device.o discovering-path-tracer_amd/build/pt_denoise.o \

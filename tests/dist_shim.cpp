@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE, not product code.  A stand-in for the nine RCCL entry
-// points pt_api.cpp's rccl_api() resolves (loaded through PT_RCCL_LIB), so
+// points pt_dist.cpp's rccl_api() resolves (loaded through PT_RCCL_LIB), so
 // pt_dist_run's N > 1 schedule -- the grouped ncclSend/ncclRecv of every
 // frame, the per-rank send slots, the root's receive sets and its fused
 // assembly -- runs with several processes on ONE GPU.  Real RCCL refuses two

@@ -186,7 +186,7 @@ def test_negative_zero_is_the_additive_identity():
 def test_rccl_standin_exports_the_entry_points_pt_dist_resolves():
     """tests/dist_shim.cpp (loaded by libptamd through PT_RCCL_LIB in the
     two-process GPU test of pt_dist_run) defines every RCCL entry point
-    rccl_api() resolves (pt_api.cpp), and libptamd names that variable."""
+    rccl_api() resolves (pt_dist.cpp), and libptamd names that variable."""
     import ctypes
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -196,7 +196,7 @@ def test_rccl_standin_exports_the_entry_points_pt_dist_resolves():
     for name in ("ncclGetUniqueId", "ncclCommInitRank", "ncclCommDestroy", "ncclCommAbort", "ncclGroupStart",
                  "ncclGroupEnd", "ncclSend", "ncclRecv", "ncclGetErrorString"):
         assert hasattr(lib, name), name
-    api = open(os.path.join(root, "discovering-path-tracer_amd", "csrc", "pt_api.cpp")).read()
+    api = open(os.path.join(root, "discovering-path-tracer_amd", "csrc", "pt_dist.cpp")).read()
     assert 'getenv("PT_RCCL_LIB")' in api
     uid = ctypes.create_string_buffer(128)
     assert lib.ncclGetUniqueId(uid) == 0 and uid.value.startswith(b"/ptshim-")
