@@ -23,6 +23,7 @@
 #include "pt_denoise.h"
 #include "pt_isect.h"
 #include "pt_math.h"
+#include "pt_plan.h"
 #include "scene/small_sweep.h"
 #include "scene/threaded_bvh.h"
 #include "scene/wide_bvh.h"
@@ -30,18 +31,6 @@
 namespace {
 
 thread_local std::string g_err;   // pt_last_error(): its one definition (pt_fail_internal sets it)
-
-// The sweep walk's enabling bound (PT_OPT_SMALL_SWEEP -1, the default): a
-// scene that has a sweep table (at most pt::kSweepMaxLeaves triangles) is
-// walked by it when the table holds at most this many distinct boxes -- the
-// largest size at which the sweep did not lose to the threaded walk by the
-// mean and by the fastest launch alike (profiles/sweep/sweep_sizes.log,
-// 512x512 8 spp, on / off by mean and by minimum: 7 boxes 0.79-0.94 and
-// 0.78-0.97, 15 boxes 0.98 and 0.96; 21 boxes 0.79 by the mean but 1.04 by
-// the minimum, the threaded walk's launches scattering widely there; 31
-// boxes 1.11-1.17 and 1.18-1.22, 63 boxes 1.68 and 1.72).  The slab tests set
-// the cost: 32 leaves over 31 boxes lose like 16 leaves over 31.
-constexpr int kSweepAutoBoxes = 15;
 
 // The threaded arrays of the exact walk (scene/threaded_bvh.h) as float4 pairs.
 std::vector<float4> as_float4(const std::vector<float>& f) {
@@ -351,7 +340,7 @@ static int mix_feedback(pt_context* c, const ptd::RenderParams& p, uint32_t n_ba
   return PT_OK;
 }
 
-// How a launch mixes lane counts (render_impl): PT_OPT_MIXED_LANES k > 0, a
+// How a launch mixes lane counts (cull_and_items): PT_OPT_MIXED_LANES k > 0, a
 // static budget of whole tiles (mixed_origins); -1, uniform lanes until the
 // part costs are measured, then the measured schedule (measured_origins).
 struct MixPlan {
@@ -473,8 +462,6 @@ int unpack_table(pt_context* c, const ptd::RenderParams& p, const std::vector<fl
 // 65 times per frame instead of 520 -- 767 -> 560 ms (2^26: 591).  More
 // batches run in chunks of that size; an allocation that fails halves it.
 constexpr long long kWfMaxPaths = 1ll << 27;
-constexpr int kWfAutoTris = 32768;
-constexpr int kWfWideAutoTris = 16384;   // ... with the culled wide walk (render_impl)
 static int wf_reserve(pt_context* c, long long pixels, uint32_t batches, long long* chunk_paths) {
   const long long limit = c->opt_wf_paths > 0 ? c->opt_wf_paths : kWfMaxPaths;
   long long want = std::max(pixels, std::min(pixels * (long long)batches, limit));
@@ -545,7 +532,7 @@ int wide_params(pt_context* c, ptd::RenderParams* p) {
     c->wide_ovf_stack = stack;
   }
   // closest hits come back as leaf ranks
-  p->wide_qn = c->opt_wide_node == 64 ? 1 : 0;
+  p->wide_qn = wide_layout_qn(*c);
   p->wide = p->wide_qn ? c->d_wide_q : c->d_wide;
   p->wide_leafbox = c->d_wide_leafbox;
   p->wide_tris = c->d_wide_tris;
@@ -557,333 +544,359 @@ int wide_params(pt_context* c, ptd::RenderParams* p) {
   return PT_OK;
 }
 
-// Whether the context's launches walk the scene's sweep table (PT_OPT_SMALL_SWEEP): the
-// option admits the scene, and the launch is the plain LDS-staged path-recursive kernel
-// (a scene with a table always fits in LDS; the auto kernel choice is path-recursive for it).
-static bool sweep_in_force(const pt_context* c) {
-  const bool wanted =
-      c->d_sweep && (c->opt_small_sweep == 1 || (c->opt_small_sweep < 0 && c->sweep_boxes <= kSweepAutoBoxes));
-  return wanted && c->opt_scene_lds != 0 && c->opt_kernel != 3 && !c->stats_mode && c->opt_count == 0;
+// ---- a render, step by step (render_impl below puts them in order) ------------------------------
+
+// The launch-timing ring (PT_OPT_LAUNCH_TIMING): an event pair around every
+// k-th render launch, render_impl's and relaunch's alike.
+struct LaunchTimer {
+  int slot = 0;
+  bool timed = false;
+};
+static int timing_begin(pt_context* c, LaunchTimer* t) {
+  t->slot = c->ring_n % pt_context::kRing;
+  t->timed = c->opt_timing > 0 && c->launch_n % c->opt_timing == 0;
+  if (t->timed) PT_HIP(hipEventRecord(c->ring[t->slot][0], c->stream));
+  return PT_OK;
 }
-// One path-recursive launch of prepared parameters, timed as render_impl
-// times its launches (PT_OPT_LAUNCH_TIMING).
-int relaunch(pt_context* c, const ptd::RenderParams& p, bool lds, bool cnt) {
-  const int slot = c->ring_n % pt_context::kRing;
-  const bool timed = c->opt_timing > 0 && c->launch_n % c->opt_timing == 0;
-  if (timed) PT_HIP(hipEventRecord(c->ring[slot][0], c->stream));
-  PT_HIP(ptd::launch_render(p, false, lds, c->stream, cnt));
-  if (timed) {
-    PT_HIP(hipEventRecord(c->ring[slot][1], c->stream));
-    c->ring_launch[slot] = c->launch_n;
-    c->last_slot = slot;
+static int timing_end(pt_context* c, const LaunchTimer& t) {
+  if (t.timed) {
+    PT_HIP(hipEventRecord(c->ring[t.slot][1], c->stream));
+    c->ring_launch[t.slot] = c->launch_n;
+    c->last_slot = t.slot;
     c->ring_n++;
     c->timed = true;
   }
   c->launch_n++;
   return PT_OK;
 }
-// pt_render / pt_render_packed (pack_out != null: fresh frame, live items
-// written to pack_out in the pt_items_pack layout).
-int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4* pack_out, const Assembly& as,
-                Launched* launched) {
+
+// One path-recursive launch of prepared parameters, timed as render_impl
+// times its launches.
+int relaunch(pt_context* c, const ptd::RenderParams& p, bool lds, bool cnt) {
+  LaunchTimer timer;
+  { const int rc = timing_begin(c, &timer); if (rc) return rc; }
+  PT_HIP(ptd::launch_render(p, false, lds, c->stream, cnt));
+  return timing_end(c, timer);
+}
+
+static int render_ready(const pt_context* c) {
   if (!c) return fail(PT_ERR_INVALID, "null context");
   if (!c->has_scene) return fail(PT_ERR_INVALID, "no scene uploaded");
   if (!c->has_camera) return fail(PT_ERR_INVALID, "no camera set");
   if (!c->d_accum) return fail(PT_ERR_INVALID, "no accumulation buffer");
-  // PT_OPT_MOMENTS: the launches below fold the luminance moments too; the image counts as valid
-  // (batches 0..n-1, in order) when this render starts at 0 or continues at n
-  bool fold_moments = false, moments_cont = false;
-  if (c->opt_moments) {
-    if (pack_out) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with pt_render_packed or pt_dist_run");
-    if (c->nranks > 1) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not on a partition of more than one rank");
-    if (c->stats_mode) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not in stats mode");
-    if (c->opt_count) return fail(PT_ERR_UNSUPPORTED, "PT_OPT_MOMENTS: not with PT_OPT_COUNT_TRACED");
-    const size_t n = (size_t)c->width * c->height;
-    if (n_batches > 0) {
-      if (!c->d_moments || c->moments_cap < n) {
-        c->moments_valid = false;
-        PT_HIP(hipSetDevice(c->device));
-        const int rg = grow_dev(c, &c->d_moments, &c->moments_cap, n);
-        if (rg) return rg;
-        PT_HIP(hipMemsetAsync(c->d_moments, 0, n * sizeof(float2), c->stream));
-      }
-      fold_moments = true;
-      moments_cont = first_batch == 0 || (c->moments_valid && first_batch == c->moments_n);
-      c->moments_valid = false;   // until the launch is enqueued
-    }
-  } else if (n_batches > 0 && !pack_out) {
-    c->moments_valid = false;   // the accumulator moves on without them
+  return PT_OK;
+}
+
+// PT_OPT_MOMENTS: the launches of a render fold the luminance moments too; the image counts as valid
+// (batches 0..n-1, in order) when this render starts at 0 or continues at n.  What the option refuses
+// (a packed render, a partition, stats mode, counting) the plan has refused already.
+struct Moments {
+  bool fold = false, cont = false;
+};
+static int moments_open(pt_context* c, uint32_t first_batch, uint32_t n_batches, bool packed, Moments* m) {
+  if (!c->opt_moments) {
+    if (n_batches > 0 && !packed) c->moments_valid = false;   // the accumulator moves on without them
+    return PT_OK;
   }
-  ptd::RenderParams p{};   // what is not set below is 0 or null: no wide walk, item list, packed output, assembly
-  p.moments = fold_moments ? c->d_moments : nullptr;
-  p.wf_grid = c->opt_wf_grid;
-  // PT_OPT_WF_REFILL auto: 16 idle lanes on a full grid, 8 on a split one
-  // (more rays per lane per round; the refill's cost is shared by fewer
-  // concurrent waves: profiles/r05i)
-  p.wide_refill = c->opt_wf_refill > 0 ? c->opt_wf_refill : (c->opt_wf_grid < 100 ? 8 : 16);
-  p.nodes = c->stats_mode ? c->d_nodes_full : c->d_nodes;
-  p.tris = c->d_tris;
-  p.hit_tris = c->d_tris;
-  p.lights = c->d_lights_dev;
-  p.accum = c->d_accum;
-  p.stats = c->d_stats;
-  p.n_nodes = c->stats_mode ? c->n_nodes_full : c->n_nodes;
-  p.n_tris = c->n_tris;
-  p.n_lights = c->n_lights;
-  p.width = c->width;
-  p.height = c->height;
-  p.first_batch = first_batch;
-  p.n_batches = n_batches;
-  p.seed_base = c->opt_seed_base + c->seed_extra;   // PT_OPT_SEED_BASE (mod 2^32)
-  p.max_depth = c->params.max_depth;
-  p.sss_bounces = c->params.sss_bounces;
-  // the exit skip (PT_OPT_EXIT_SKIP): only where it can fire and rad is finite
-  p.exit_skip = c->opt_exit_skip && c->exit_normals && !c->stats_mode ? 1 : 0;
-  for (int i = 0; i < c->n_lights && p.exit_skip; ++i)
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(c->lights_host[(size_t)i].intensity[k])) p.exit_skip = 0;
-  memcpy(p.root_lo, c->root_lo, sizeof p.root_lo);
-  memcpy(p.root_hi, c->root_hi, sizeof p.root_hi);
-  camera_params(c->cam, &p);
-  p.blocks_x = (c->width + 15) / 16;
-  p.blocks_total = p.blocks_x * ((c->height + 15) / 16);
-  p.nranks = c->nranks;
-  p.rank = c->rank;
+  if (n_batches == 0) return PT_OK;
+  const size_t n = (size_t)c->width * c->height;
+  if (!c->d_moments || c->moments_cap < n) {
+    c->moments_valid = false;
+    PT_HIP(hipSetDevice(c->device));
+    const int rg = grow_dev(c, &c->d_moments, &c->moments_cap, n);
+    if (rg) return rg;
+    PT_HIP(hipMemsetAsync(c->d_moments, 0, n * sizeof(float2), c->stream));
+  }
+  m->fold = true;
+  m->cont = first_batch == 0 || (c->moments_valid && first_batch == c->moments_n);
+  c->moments_valid = false;   // until the launch is enqueued
+  return PT_OK;
+}
+static void moments_close(pt_context* c, const Moments& m, uint32_t first_batch, uint32_t n_batches) {
+  if (!m.fold) return;
+  c->moments_valid = m.cont;
+  c->moments_n = m.cont ? first_batch + n_batches : 0;
+}
+
+// The scene, frame and camera fields of a launch's parameters: all that the guide's launch takes
+// (pt_render_guide).  full_nodes: every reference node (stats mode).
+void frame_params(const pt_context* c, bool full_nodes, ptd::RenderParams* p) {
+  p->nodes = full_nodes ? c->d_nodes_full : c->d_nodes;
+  p->n_nodes = full_nodes ? c->n_nodes_full : c->n_nodes;
+  p->tris = c->d_tris;
+  p->hit_tris = c->d_tris;
+  p->n_tris = c->n_tris;
+  p->width = c->width;
+  p->height = c->height;
+  camera_params(c->cam, p);
+  p->blocks_x = (c->width + 15) / 16;
+  p->blocks_total = p->blocks_x * ((c->height + 15) / 16);
+}
+
+// ... and what a render adds: lights and buffers, the batches, what the plan chose, this rank's partition
+// (uploaded here when it changed).
+static int render_params(pt_context* c, const LaunchPlan& plan, uint32_t first_batch, uint32_t n_batches, bool packed,
+                         ptd::RenderParams* p) {
+  p->wf_grid = c->opt_wf_grid;
+  p->wide_refill = plan.wide_refill;
+  p->lights = c->d_lights_dev;
+  p->accum = c->d_accum;
+  p->stats = c->d_stats;
+  p->n_lights = c->n_lights;
+  p->first_batch = first_batch;
+  p->n_batches = n_batches;
+  p->seed_base = c->opt_seed_base + c->seed_extra;   // PT_OPT_SEED_BASE (mod 2^32)
+  p->max_depth = c->params.max_depth;
+  p->sss_bounces = c->params.sss_bounces;
+  p->exit_skip = plan.exit_skip;
+  memcpy(p->root_lo, c->root_lo, sizeof p->root_lo);
+  memcpy(p->root_hi, c->root_hi, sizeof p->root_hi);
+  p->nranks = c->nranks;
+  p->rank = c->rank;
   const ptd::Part& hpart = part_of(c, c->rank);
   {
     const int rc = sync_parts(c);
     if (rc) return rc;
   }
-  p.part_m = hpart.m;
-  p.part_cnt = hpart.cnt;
-  p.part_pos = c->d_parts + (size_t)c->rank * ptd::kMaxSlots;
-  p.n_tiles = ptd::part_count(hpart, p.blocks_total);
-  p.fresh = pack_out ? 1 : c->opt_fresh;
-  if (c->opt_sample_lanes) {
-    p.spl = c->opt_sample_lanes;
-  } else {
-    // auto: 4 sample lanes per pixel for an LDS-resident scene on up to 7
-    // ranks, else 8 — on a share of the frame each GPU's share shrinks while
-    // its heaviest workgroup does not, and on big scenes the samples of one
-    // pixel walk nearly the same nodes, so their loads coalesce.  Measured
-    // at 1080p 8spp with culling and compact launch: box spl 1/2/4/8 =
-    // 0.499/0.408/0.375/0.416 ms (whole frame), 0.354/0.264/0.225/0.221
-    // (1/2), 0.271/0.156/0.094/0.085 (1/8); displaced sphere 828/645/582/563;
-    // 1M cloud 968/930/927/923.  Never more lanes than samples.
-    // With frames alternating between two streams (bench.py N > 1), the
-    // 1/2 and 1/4 shares favour 4 lanes (0.187 vs 0.210, 0.101 vs 0.110 ms
-    // per step) and the 1/8 share 8 (0.062 vs 0.069).  Round 3's kernels,
-    // the emulated root step on the native loop (DESIGN Appendix A, round-3 share options;
-    // two runs each): 1/2 share spl 2/4 = 0.1175/0.1225 ms, 1/4 share 4/8 =
-    // 0.069/0.082, 1/8 share 4/8 = 0.046/0.042.  Round 5's kernels (the
-    // build without the SLP vectorizer, profiles/r05zc/spl.log, 200 frames):
-    // 1/2 share spl 1/2/4/8 = 0.1066/0.1067/0.118/0.1411 ms, 1/4 share
-    // 0.0811/0.0594/0.0603/0.0692, 1/8 share 0.0725/0.0465/0.0348/0.0374.
-    const bool small = ptd::scene_lds_bytes(p) <= ptd::kMaxSceneLds;
-    int want = !small ? 8 : c->nranks >= 8 ? 4 : c->nranks >= 2 ? 2 : 4;
-    while (want > 1 && (uint32_t)want > n_batches) want >>= 1;
-    p.spl = want;
+  p->part_m = hpart.m;
+  p->part_cnt = hpart.cnt;
+  p->part_pos = c->d_parts + (size_t)c->rank * ptd::kMaxSlots;
+  p->n_tiles = ptd::part_count(hpart, p->blocks_total);
+  p->fresh = packed ? 1 : c->opt_fresh;
+  p->spl = plan.spl;
+  if (plan.sweep) {
+    p->sweep = c->opt_sweep_hull ? c->d_sweep : c->d_sweep_plain;
+    p->sweep_hull = plan.sweep_hull;
+    p->sweep_boxes = c->sweep_boxes;
+    p->sweep_leaves = c->sweep_leaves;
   }
-  PT_HIP(hipSetDevice(c->device));
-  const int slot = c->ring_n % pt_context::kRing;
-  const bool timed = c->opt_timing > 0 && c->launch_n % c->opt_timing == 0;
-  if (timed) PT_HIP(hipEventRecord(c->ring[slot][0], c->stream));
-  const bool fits = ptd::scene_lds_bytes(p) <= ptd::kMaxSceneLds;
-  if (c->opt_scene_lds == 2 && !fits) return fail(PT_ERR_UNSUPPORTED, "scene too large for the LDS variant");
-  const bool lds = c->opt_scene_lds == 2 || (c->opt_scene_lds == 1 && fits);
-  // auto: the wavefront pipeline for scenes of at least kWfAutoTris triangles
-  // (not LDS-resident) when the launch holds enough paths to keep its node
-  // loads in flight, the path-recursive kernel otherwise.  Measured at 1080p
-  // (ms, recursive with paired walks -> wavefront): 1 spp (2M paths):
-  // displaced sphere 82K tris 101 -> 108, 10M cloud 735 -> 669; 8 spp (16.6M):
-  // sphere 550 -> 465, 100K cloud 113 -> 77; 1M cloud 2 spp 225 -> 236; a 1/8
-  // tile share of the 10M cloud: 1 spp (259K paths) 147 -> 273, 8 spp (2M)
-  // 742 -> 669; box 0.38 -> 8.4.
-  // With the culled wide walk (PT_OPT_WIDE) the wavefront pipeline wins from
-  // 2^20 paths on (1080p, ms recursive -> wavefront): displaced sphere 82K
-  // 1 spp 89.9 -> 39.6, 8 spp 498 -> 139, its 1/8 tile share 89.0 -> 39.1;
-  // 20K sphere 2 spp 29.6 -> 23.3; 1M cloud 1 spp 108 -> 47.5; a sparse 100K
-  // cloud at 1 spp (most rays miss) loses 14.3 -> 15.9.
-  const long long paths = (long long)p.n_tiles * 256 * n_batches;
-  const bool wide_walk = c->opt_wide && c->n_wide > 0;
-  const bool wf_auto = wide_walk ? c->n_tris >= kWfWideAutoTris && paths >= (1ll << 20)
-                                 : c->n_tris >= kWfAutoTris && paths >= (1ll << 20) &&
-                                       (c->n_tris >= (1 << 20) || paths >= (1ll << 23));
-  const bool wf = c->opt_kernel == 3 || (c->opt_kernel == 0 && !lds && !c->stats_mode && wf_auto);
-  if (wf && c->stats_mode) return fail(PT_ERR_UNSUPPORTED, "stats mode runs the path-recursive kernel only");
-  const bool cnt = c->opt_count != 0 && !c->stats_mode;
-  // the sweep walk (PT_OPT_SMALL_SWEEP): the plain LDS kernel of a scene with a table
-  const bool sweep = lds && !wf && !cnt && sweep_in_force(c);
-  if (sweep) {
-    p.sweep = c->opt_sweep_hull ? c->d_sweep : c->d_sweep_plain;
-    p.sweep_hull = c->opt_sweep_hull && c->sweep_hull > 0;
-    p.sweep_boxes = c->sweep_boxes;
-    p.sweep_leaves = c->sweep_leaves;
-  }
-  // PT_OPT_ITEM_ORDER auto: scan order for a whole frame on the path-recursive
-  // kernel (box 1080p8 at 4 lanes, one context: 0.2403 against 0.2463 ms
-  // heaviest first, profiles/r06b), heaviest first on a share of the frame
-  // and on the wavefront pipeline
-  p.item_order = c->opt_item_order >= 0 ? c->opt_item_order : (!wf && c->nranks == 1 ? 0 : 1);
-  p.n_cull = -1;
+  p->item_order = plan.item_order;
+  return PT_OK;
+}
+
+// The cull rectangles and the item lists of the frame; mixed lanes where the plan admits them and the
+// frame has rectangles.  (Stats mode derives no rectangles, so its launches never mix lanes.)
+static int cull_and_items(pt_context* c, const LaunchPlan& plan, uint32_t n_batches, ptd::RenderParams* p) {
+  p->n_cull = -1;
   c->last_mix = 0;
   if (c->opt_cull && !c->stats_mode)
-    p.n_cull = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
-                          c->n_lights, &p.cull[0][0], ptd::kMaxCullRects);
+    p->n_cull = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
+                                c->n_lights, &p->cull[0][0], ptd::kMaxCullRects);
   // the tight rectangles (PT_OPT_CULL_TIGHT): the kernel's per-sample skip; every host-side use of the
   // rectangles (items, fills, partitions) keeps the loose ones.  Off (-1, "never skip") unless both derive
-  p.n_cull_tight = -1;
-  p.cull_u0 = ptd::kCullTightU0;
-  if (p.n_cull >= 0 && c->opt_cull_tight) {
-    p.n_cull_tight = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
-                                c->n_lights, &p.cull_tight[0][0], ptd::kMaxCullRects, ptd::kCullTightR);
-    if (p.n_cull_tight != p.n_cull) p.n_cull_tight = -1;
+  p->n_cull_tight = -1;
+  p->cull_u0 = ptd::kCullTightU0;
+  if (p->n_cull >= 0 && c->opt_cull_tight) {
+    p->n_cull_tight = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
+                                      c->n_lights, &p->cull_tight[0][0], ptd::kMaxCullRects, ptd::kCullTightR);
+    if (p->n_cull_tight != p->n_cull) p->n_cull_tight = -1;
   }
-  if (p.n_cull >= 0) {
-    // mixed lanes (PT_OPT_MIXED_LANES): one rank, LDS-staged path-recursive
-    // launches that render into the accumulation buffer
-    MixPlan plan;
-    bool mixed = false;
-    // (one lane per pixel: the measured schedule only orders whole tiles)
-    if (c->opt_mixed != 0 && !wf && lds && c->nranks == 1 && !pack_out && (p.spl > 1 || c->opt_mixed < 0) &&
-        !cnt) {
-      mixed = true;
-      const size_t lds_b = sweep ? ptd::sweep_lds_bytes(p) : ptd::scene_lds_bytes(p);
-      if (c->render_slots < 0 || c->render_slots_lds != lds_b || c->render_slots_sweep != sweep) {
-        c->render_slots_sweep = sweep;
-        c->render_slots = ptd::render_slots(lds_b, sweep);
-        c->render_slots_lds = lds_b;
-      }
-      // auto: every item at PT_OPT_SAMPLE_LANES until the block costs are
-      // measured -- the measuring launches then run a uniform schedule, whose
-      // workgroups nearly all run at full occupancy (a mixed one measured its
-      // drain's parts at low occupancy, too short: profiles/r06g)
-      plan.budget = c->opt_mixed > 0 ? std::max(1ll, c->render_slots * c->opt_mixed / 100) : 0;
-      if (c->opt_mixed < 0) {
-        const int rm = mix_feedback(c, p, n_batches);
-        if (rm) return rm;
-        if (c->cost_ready) {
-          plan.cost = &c->block_cost;
-          plan.gen = c->cost_gen;
-        }
+  if (p->n_cull < 0) return PT_OK;
+  MixPlan mix;
+  const bool mixed = plan.mixed_eligible;
+  if (mixed) {
+    const size_t lds_b = plan.sweep ? ptd::sweep_lds_bytes(*p) : ptd::scene_lds_bytes(*p);
+    if (c->render_slots < 0 || c->render_slots_lds != lds_b || c->render_slots_sweep != plan.sweep) {
+      c->render_slots_sweep = plan.sweep;
+      c->render_slots = ptd::render_slots(lds_b, plan.sweep);
+      c->render_slots_lds = lds_b;
+    }
+    // auto: every item at PT_OPT_SAMPLE_LANES until the block costs are
+    // measured -- the measuring launches then run a uniform schedule, whose
+    // workgroups nearly all run at full occupancy (a mixed one measured its
+    // drain's parts at low occupancy, too short: profiles/r06g)
+    mix.budget = c->opt_mixed > 0 ? std::max(1ll, c->render_slots * c->opt_mixed / 100) : 0;
+    if (c->opt_mixed < 0) {
+      const int rm = mix_feedback(c, *p, n_batches);
+      if (rm) return rm;
+      if (c->cost_ready) {
+        mix.cost = &c->block_cost;
+        mix.gen = c->cost_gen;
       }
     }
-    const int rc = compact_items(c, &p, mixed ? &plan : nullptr);
+  }
+  const int rc = compact_items(c, p, mixed ? &mix : nullptr);
+  if (rc) return rc;
+  c->last_mix = !mixed || !c->items_mixed ? 0 : mix.cost ? 2 : 1;
+  if (mixed && c->opt_mixed < 0 && c->cost_measure) {
+    // this launch measures its blocks' costs (mix_feedback)
+    PT_HIP(hipMemsetAsync(c->d_cost, 0, (size_t)p->blocks_total * 4 * sizeof(unsigned), c->stream));
+    p->cost_out = c->d_cost;
+    c->cost_lanes = c->block_lanes;
+  }
+  return PT_OK;
+}
+
+// Culled items written once (culled_state): a launch whose culled items
+// already hold (0,0,0,1) in this buffer under this item layout -- a fold of
+// (0,0,0,1) samples into (0,0,0,1) is (0,0,0,1), whatever the batch --
+// skips their fill workgroups (23 MB of writes per box 1080p frame).
+// culled_before says whether the launch fills culled items of the accumulation
+// buffer at all and skips the fill where it can; culled_after records what
+// they hold once the launch is enqueued.
+struct Culled {
+  bool launch = false, skipped = false;
+};
+static bool culled_hold(const pt_context* c) {
+  return c->culled_state == 2 && c->culled_buf == c->d_accum && c->culled_key == c->items_key;
+}
+static Culled culled_before(pt_context* c, ptd::RenderParams* p, bool packed, uint32_t n_batches) {
+  Culled cu;
+  cu.launch = p->n_cull >= 0 && p->items && !packed && !c->stats_mode && n_batches > 0;
+  if (cu.launch && culled_hold(c)) {
+    p->n_culled_items = 0;
+    cu.skipped = true;
+  }
+  return cu;
+}
+static void culled_after(pt_context* c, const Culled& cu, bool packed, bool fresh, uint32_t first_batch,
+                         uint32_t n_batches) {
+  if (cu.launch && !cu.skipped) {
+    const bool exact = (fresh && first_batch == 0) || culled_hold(c) ||
+                       (first_batch == 0 && c->culled_state == 1 && c->culled_buf == c->d_accum);
+    c->culled_state = exact ? 2 : 0;
+    c->culled_key = c->items_key;
+    c->culled_buf = c->d_accum;
+  } else if (!cu.launch && !packed && n_batches > 0) {
+    c->culled_state = 0;   // every pixel rendered (no culling, stats mode): not tracked
+  }
+}
+
+// pt_render_packed's optional assembly of a gathered frame by the launch's trailing workgroups.
+static int assembly_params(pt_context* c, const Assembly& as, ptd::RenderParams* p) {
+  if (!as.src) return PT_OK;
+  const int rc = unpack_table(c, *p, c->key_scratch);
+  if (rc) return rc;
+  p->unpack_src = (const float4*)as.src;
+  p->unpack_frame = (float4*)as.frame;
+  p->unpack_table = c->d_unpack;
+  p->n_unpack = c->n_unpack;
+  p->unpack_slot_f4 = (long long)(as.slot_floats / 4);
+  return PT_OK;
+}
+
+// The wavefront pipeline's launch: its path buffers, the wide walk's arrays where the plan walks them,
+// the second stream on first use.
+static int launch_wf(pt_context* c, const LaunchPlan& plan, uint32_t n_batches, ptd::RenderParams* p) {
+  const long long tiles = p->n_tiles;
+  const long long items = p->items ? p->n_items : tiles * p->spl;
+  long long chunk_paths = 0;
+  const int rc = wf_reserve(c, items * (256 / p->spl), n_batches, &chunk_paths);
+  if (rc) return rc;
+  ptd::WfBuffers b = c->wf;
+  b.cap = chunk_paths;   // paths per chunk (the allocation may be larger)
+  if (plan.wide) {
+    const int rw = wide_params(c, p);
+    if (rw) return rw;
+    p->wide_handback = plan.wide_handback;
+    p->wf_fuse = plan.wf_fuse;
+    p->wf_tail = plan.wf_tail;
+  }
+  if (plan.two_streams && !c->wf_stream2) {
+    PT_HIP(hipStreamCreateWithFlags(&c->wf_stream2, hipStreamNonBlocking));
+    PT_HIP(hipEventCreateWithFlags(&c->wf_fork, hipEventDisableTiming));
+    PT_HIP(hipEventCreateWithFlags(&c->wf_join, hipEventDisableTiming));
+  }
+  PT_HIP(ptd::launch_wavefront(*p, b, plan.lds, c->stream, plan.cnt, plan.two_streams ? c->wf_stream2 : nullptr,
+                               c->wf_fork, c->wf_join));
+  return PT_OK;
+}
+
+// The path-recursive launch, the read-back of a measuring launch's costs (mix_feedback), and the
+// parameters pt_dist_run relaunches.
+static int launch_recursive(pt_context* c, const LaunchPlan& plan, const ptd::RenderParams& p, Launched* launched) {
+  PT_HIP(ptd::launch_render(p, c->stats_mode, plan.lds, c->stream, plan.cnt));
+  if (p.cost_out) {
+    PT_HIP(hipMemcpyAsync(c->h_cost, c->d_cost, (size_t)p.blocks_total * 4 * sizeof(unsigned), hipMemcpyDeviceToHost,
+                          c->stream));
+    PT_HIP(hipEventRecord(c->cost_ev, c->stream));
+    c->cost_pending = true;
+    c->cost_measure = false;
+  }
+  if (launched && p.pack_out && !c->stats_mode) {
+    launched->p = p;
+    launched->lds = plan.lds;
+    launched->cnt = plan.cnt;
+    launched->valid = true;
+  }
+  return PT_OK;
+}
+
+// pt_render_packed on the wavefront pipeline, whose kernels render into the
+// accumulation buffer: assemble the previous frame in a launch of its own,
+// render a fresh frame from batch 0 as pt_render would (p is that render's too:
+// a packed frame is fresh, and neither mixes lanes), then pack it.
+static int render_packed_wavefront(pt_context* c, const LaunchPlan& plan, ptd::RenderParams p, uint32_t n_batches,
+                                   float4* pack_out, const Assembly& as) {
+  // (the calls below rebuild c->key_scratch: keep this frame's key)
+  const std::vector<float> frame_k = c->key_scratch;
+  if (as.src) {
+    const int rc = pt_items_unpack_all(c, as.src, as.slot_floats, as.frame);
     if (rc) return rc;
-    c->last_mix = !mixed || !c->items_mixed ? 0 : plan.cost ? 2 : 1;
-    if (mixed && c->opt_mixed < 0 && c->cost_measure) {
-      // this launch measures its blocks' costs (mix_feedback)
-      PT_HIP(hipMemsetAsync(c->d_cost, 0, (size_t)p.blocks_total * 4 * sizeof(unsigned), c->stream));
-      p.cost_out = c->d_cost;
-      c->cost_lanes = c->block_lanes;
-    }
   }
+  if (n_batches > 0) c->moments_valid = false;   // the accumulator moves on without them
+  LaunchTimer timer;   // the pair opens after the assembly
+  { const int rc = timing_begin(c, &timer); if (rc) return rc; }
+  const Culled culled = culled_before(c, &p, false, n_batches);
+  { const int rc = order_shared(c); if (rc) return rc; }
+  { const int rc = launch_wf(c, plan, n_batches, &p); if (rc) return rc; }
+  { const int rc = mark_shared(c); if (rc) return rc; }
+  { const int rc = timing_end(c, timer); if (rc) return rc; }
+  culled_after(c, culled, false, true, 0, n_batches);
+  c->packed_key = frame_k;
+  const int rp = pt_items_pack(c, pack_out);
+  if (rp) return rp;
+  return mark_shared(c);   // the pack read the accumulation buffer
+}
+
+// pt_render / pt_render_packed (pack_out != null: fresh frame, live items
+// written to pack_out in the pt_items_pack layout).
+int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4* pack_out, const Assembly& as,
+                Launched* launched) {
+  { const int rc = render_ready(c); if (rc) return rc; }
+  const bool packed = pack_out != nullptr;
+  ptd::RenderParams p{};   // what is not set below is 0 or null: no wide walk, item list, packed output, assembly
+  frame_params(c, c->stats_mode, &p);
+  const LaunchPlan plan =
+      plan_launch(*c, ptd::part_count(part_of(c, c->rank), p.blocks_total), n_batches, packed);
+  if (plan.refuse_first) return fail(plan.refuse_code, plan.refuse);
+  Moments moments;
+  { const int rc = moments_open(c, first_batch, n_batches, packed, &moments); if (rc) return rc; }
+  p.moments = moments.fold ? c->d_moments : nullptr;
+  { const int rc = render_params(c, plan, first_batch, n_batches, packed, &p); if (rc) return rc; }
+  PT_HIP(hipSetDevice(c->device));
+  LaunchTimer timer;
+  { const int rc = timing_begin(c, &timer); if (rc) return rc; }
+  if (plan.refuse) return fail(plan.refuse_code, plan.refuse);
+  { const int rc = cull_and_items(c, plan, n_batches, &p); if (rc) return rc; }
   c->last = p;   // the item exchange (pt_items_*) follows the last rendered frame
-  // Culled items written once (culled_state): a launch whose culled items
-  // already hold (0,0,0,1) in this buffer under this item layout -- a fold of
-  // (0,0,0,1) samples into (0,0,0,1) is (0,0,0,1), whatever the batch --
-  // skips their fill workgroups (23 MB of writes per box 1080p frame).
-  const bool culled_launch = p.n_cull >= 0 && p.items && !pack_out && !c->stats_mode && n_batches > 0;
-  bool culled_skipped = false;
-  if (culled_launch && c->culled_state == 2 && c->culled_buf == c->d_accum && c->culled_key == c->items_key) {
-    p.n_culled_items = 0;
-    culled_skipped = true;
-  }
-  c->last_kernel = wf ? 3 : 1;
+  const Culled culled = culled_before(c, &p, packed, n_batches);
+  c->last_kernel = plan.wf ? 3 : 1;
   c->last_valid = true;
-  if (pack_out && as.frame == (void*)c->d_accum) c->culled_state = 0;   // the assembly writes this buffer
-  if (pack_out) {
+  if (packed && as.frame == (void*)c->d_accum) c->culled_state = 0;   // the assembly writes this buffer
+  if (packed) {
     frame_key(c, p, &c->key_scratch);
-    const std::vector<float>& key = c->key_scratch;
-    if (as.src && key != c->packed_key)
+    if (as.src && c->key_scratch != c->packed_key)
       return fail(PT_ERR_INVALID, "pt_render_packed: the frame to assemble has another item layout (size, partition, lanes, culling)");
-    if (wf) {
-      // these kernels render into the accumulation buffer: render, pack,
-      // then assemble the previous frame in a launch of its own (the calls
-      // below rebuild c->key_scratch: keep this frame's key)
-      const std::vector<float> frame_k = key;
-      if (as.src) {
-        const int rc = pt_items_unpack_all(c, as.src, as.slot_floats, as.frame);
-        if (rc) return rc;
-      }
-      const int fresh = c->opt_fresh;
-      c->opt_fresh = 1;
-      const int rc = render_impl(c, 0, n_batches, nullptr);
-      c->opt_fresh = fresh;
-      if (rc) return rc;
-      c->packed_key = frame_k;
-      const int rp = pt_items_pack(c, pack_out);
-      if (rp) return rp;
-      return mark_shared(c);   // the pack read the accumulation buffer
-    }
-    if (as.src) {
-      const int rc = unpack_table(c, p, key);
-      if (rc) return rc;
-      p.unpack_src = (const float4*)as.src;
-      p.unpack_frame = (float4*)as.frame;
-      p.unpack_table = c->d_unpack;
-      p.n_unpack = c->n_unpack;
-      p.unpack_slot_f4 = (long long)(as.slot_floats / 4);
-    }
+    if (plan.wf) return render_packed_wavefront(c, plan, p, n_batches, pack_out, as);
+    { const int rc = assembly_params(c, as, &p); if (rc) return rc; }
     if (!p.items) p.n_items = p.n_tiles * p.spl;
-    c->packed_key = key;
+    c->packed_key = c->key_scratch;
+    p.pack_out = pack_out;
   }
-  p.pack_out = pack_out;
   // every launch but the path-recursive render_packed writes the context's
   // accumulation buffer or wavefront buffers
-  const bool shared = !pack_out || wf || c->stats_mode;
+  const bool shared = !packed || plan.wf || c->stats_mode;
   if (shared) {
     const int ro = order_shared(c);
     if (ro) return ro;
   }
   // a launch from batch 0 starts every pixel's moments at +0; the kernels write the live pixels only
-  if (fold_moments && first_batch == 0)
+  if (moments.fold && first_batch == 0)
     PT_HIP(hipMemsetAsync(c->d_moments, 0, (size_t)c->width * c->height * sizeof(float2), c->stream));
-  if (wf) {
-    const long long tiles = p.n_tiles;
-    const long long items = p.items ? p.n_items : tiles * p.spl;
-    long long chunk_paths = 0;
-    const int rc = wf_reserve(c, items * (256 / p.spl), n_batches, &chunk_paths);
+  {
+    const int rc = plan.wf ? launch_wf(c, plan, n_batches, &p) : launch_recursive(c, plan, p, launched);
     if (rc) return rc;
-    ptd::WfBuffers b = c->wf;
-    b.cap = chunk_paths;   // paths per chunk (the allocation may be larger)
-    if (c->opt_wide && c->n_wide > 0 && !lds) {
-      const int rw = wide_params(c, &p);
-      if (rw) return rw;
-      p.wide_handback = c->opt_wide == 2 ? 1 : 0;
-      // fused shadow walks: hit records carry the rank in 29 bits
-      p.wf_fuse = c->opt_wf_fuse && c->n_tris <= ptd::kHitRankMask && c->n_lights > 0 ? 1 : 0;
-      // wf_tail_kernel (4-wide layouts).  Auto: once a list holds fewer than
-      // 400K rays (with the wave-wide flush, item 39; ab_bench device time):
-      // emulated 1/8 tile shares of configs 3 / 4 / 5 13.48 -> 11.31, 64.68 ->
-      // 64.26, 22.36 -> 21.91 ms; whole frames 44.28 -> 43.77, 384.41 ->
-      // 384.89, 117.72 -> 117.39 ms.  (2^20: 11.17 / 65.31 / 22.39; from the
-      // first list: +28-57 % on whole frames.)
-      const int tail_auto = 400000;
-      p.wf_tail = c->opt_wf_tail >= 0 ? c->opt_wf_tail : tail_auto;
-    }
-    if (c->opt_wf_streams == 2 && !c->wf_stream2) {
-      PT_HIP(hipStreamCreateWithFlags(&c->wf_stream2, hipStreamNonBlocking));
-      PT_HIP(hipEventCreateWithFlags(&c->wf_fork, hipEventDisableTiming));
-      PT_HIP(hipEventCreateWithFlags(&c->wf_join, hipEventDisableTiming));
-    }
-    const bool two = c->opt_wf_streams == 2;
-    PT_HIP(ptd::launch_wavefront(p, b, lds, c->stream, cnt, two ? c->wf_stream2 : nullptr, c->wf_fork, c->wf_join));
-  } else {
-    PT_HIP(ptd::launch_render(p, c->stats_mode, lds, c->stream, cnt));
-    if (p.cost_out) {
-      PT_HIP(hipMemcpyAsync(c->h_cost, c->d_cost, (size_t)p.blocks_total * 4 * sizeof(unsigned),
-                            hipMemcpyDeviceToHost, c->stream));
-      PT_HIP(hipEventRecord(c->cost_ev, c->stream));
-      c->cost_pending = true;
-      c->cost_measure = false;
-    }
-    if (launched && pack_out && !c->stats_mode) {
-      launched->p = p;
-      launched->lds = lds;
-      launched->cnt = cnt;
-      launched->valid = true;
-    }
   }
   if (shared) {
     const int rm = mark_shared(c);
@@ -892,29 +905,9 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
     const int ru = note_use(c);   // render_packed reads the scene and item tables
     if (ru) return ru;
   }
-  if (timed) {
-    PT_HIP(hipEventRecord(c->ring[slot][1], c->stream));
-    c->ring_launch[slot] = c->launch_n;
-    c->last_slot = slot;
-    c->ring_n++;
-    c->timed = true;
-  }
-  c->launch_n++;
-  if (fold_moments) {
-    c->moments_valid = moments_cont;
-    c->moments_n = moments_cont ? first_batch + n_batches : 0;
-  }
-  // the state of the culled items after this launch (culled_state)
-  if (culled_launch && !culled_skipped) {
-    const bool same = c->culled_state == 2 && c->culled_buf == c->d_accum && c->culled_key == c->items_key;
-    const bool exact = (c->opt_fresh && first_batch == 0) || same ||
-                       (first_batch == 0 && c->culled_state == 1 && c->culled_buf == c->d_accum);
-    c->culled_state = exact ? 2 : 0;
-    c->culled_key = c->items_key;
-    c->culled_buf = c->d_accum;
-  } else if (!culled_launch && !pack_out && n_batches > 0) {
-    c->culled_state = 0;   // every pixel rendered (no culling, stats mode): not tracked
-  }
+  { const int rc = timing_end(c, timer); if (rc) return rc; }
+  moments_close(c, moments, first_batch, n_batches);
+  culled_after(c, culled, packed, c->opt_fresh != 0, first_batch, n_batches);
   return PT_OK;
 }
 

@@ -1,9 +1,11 @@
 // pt_context.h — internal: the context behind the C ABI (include/pathtracer.h)
 // and the helpers the shim's translation units share.  pt_api.cpp is the core
-// (create/destroy, uploads, item lists, render_impl, options, exchange, stats,
-// timing); pt_post.cpp the post-processing chain (guide, filters, temporal
-// accumulation); pt_dist.cpp the RCCL step loop; pt_group.cpp the multi-device
-// context.  The fields of pt_context are grouped in that order.
+// (create/destroy, uploads, item lists, render_impl and its steps, options,
+// exchange, stats, timing); pt_plan.h the launch plan, every policy render_impl
+// carries out, as one pure function (plan_launch); pt_post.cpp the
+// post-processing chain (guide, filters, temporal accumulation); pt_dist.cpp
+// the RCCL step loop; pt_group.cpp the multi-device context.  The fields of
+// pt_context are grouped in that order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -172,7 +174,7 @@ struct pt_context {
   ptd::RenderParams last{};     // configuration of the last pt_render
   bool last_valid = false;
   int last_kernel = 0;        // kernel of the last render (1 recursive, 3 wavefront)
-  // What the accumulation buffer's culled items hold (render_impl): 0 not
+  // What the accumulation buffer's culled items hold (culled_before, culled_after): 0 not
   // known, 1 finite (+-0 after a clear), 2 (0,0,0,1) in every culled item of
   // the item layout culled_key in buffer culled_buf.  Only the library's own
   // calls are assumed to write the buffer (accum_overwritten).
@@ -357,7 +359,9 @@ inline int read_image(pt_context* c, const void* img, int w, int h, int per, flo
   return PT_OK;
 }
 
-// ---- what the core (pt_api.cpp) gives pt_post.cpp (a launch's camera block and wide-walk arrays) ...
+// ---- what the core (pt_api.cpp) gives pt_post.cpp (a launch's scene, frame and camera fields, the
+// camera block alone, and the wide-walk arrays) ...
+void frame_params(const pt_context* c, bool full_nodes, ptd::RenderParams* p);
 void camera_params(const float cam[16], ptd::RenderParams* p);
 int wide_params(pt_context* c, ptd::RenderParams* p);
 // ... and pt_dist.cpp: one frame of the step loop is render_impl with a packed output and an

@@ -10,6 +10,7 @@
 
 #include "pt_context.h"
 #include "pt_denoise.h"
+#include "pt_plan.h"
 
 // Frees what this file allocates in a context (pt_destroy).
 void post_release(pt_context* c) {
@@ -97,21 +98,13 @@ int pt_render_guide(pt_context* c) {
   PT_HIP(hipSetDevice(c->device));
   c->guide_valid = false;
   ptd::RenderParams p{};
-  p.nodes = c->d_nodes;
-  p.n_nodes = c->n_nodes;
-  p.tris = c->d_tris;
-  p.hit_tris = c->d_tris;
-  p.n_tris = c->n_tris;
-  p.width = c->width;
-  p.height = c->height;
-  camera_params(c->cam, &p);
-  p.blocks_x = (c->width + 15) / 16;
-  p.blocks_total = p.blocks_x * ((c->height + 15) / 16);
+  frame_params(c, false, &p);
   p.n_cull = -1;
+  // the wide walk first, then the LDS rule (pt_plan.h)
   const bool wide = c->opt_wide && c->n_wide > 0;
-  const bool fits = ptd::scene_lds_bytes(p) <= ptd::kMaxSceneLds;
-  if (!wide && c->opt_scene_lds == 2 && !fits) return fail(PT_ERR_UNSUPPORTED, "scene too large for the LDS variant");
-  const bool lds = !wide && (c->opt_scene_lds == 2 || (c->opt_scene_lds == 1 && fits));
+  const bool fits = lds_fits(*c, c->n_nodes);
+  if (!wide && lds_refused(*c, fits)) return fail(PT_ERR_UNSUPPORTED, kLdsTooLarge);
+  const bool lds = !wide && lds_staged(*c, fits);
   if (wide) {
     const int rw = wide_params(c, &p);
     if (rw) return rw;

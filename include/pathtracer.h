@@ -770,13 +770,13 @@ int pt_dist_finalize(pt_context* ctx);
  * tiles at one lane per pixel (all samples of a pixel in one lane: the least
  * work per sample, the longest workgroups) and tile parts at more lanes
  * (short workgroups that fill the launch's drain).  -1 (default) = measured:
- * until the frame's inputs have been measured, the first live tiles up to
- * half of the workgroups the device holds at once run whole and the rest at
- * PT_OPT_SAMPLE_LANES; render_kernel meanwhile times its blocks (two
- * launches once the inputs are unchanged for a render, copied back without
- * a host wait), and from then on every tile gets the fewest lanes that keep
- * its workgroups short enough, longest first, the lane cut chosen by a
- * simulation of the launch (pt_mixed_info reports the schedule).  A change of
+ * until the frame's inputs have been measured, every item runs at
+ * PT_OPT_SAMPLE_LANES (uniform lanes); render_kernel meanwhile times its
+ * blocks (two launches once the inputs are unchanged for a render, copied
+ * back without a host wait), and from then on every wholly live tile runs as
+ * two 16x8 halves at 2 lanes per pixel and the live parts of the other tiles
+ * at PT_OPT_SAMPLE_LANES, all items longest first by their measured cost
+ * (pt_mixed_info reports the schedule).  A change of
  * size, batches, camera, params, scene or lights starts over.  k = 1-1000:
  * the static schedule with whole tiles for k % of the resident workgroups,
  * never measured.  0 = off (every item at PT_OPT_SAMPLE_LANES).  Output is

@@ -2,7 +2,7 @@
 
 Each test renders the config's full frame on the kernel the library selects
 on its own (the wavefront pipeline for all three: >= 32768 triangles and
-enough paths, pt_api.cpp render_impl) and compares a subset of rows bitwise
+enough paths, pt_plan.h plan_launch) and compares a subset of rows bitwise
 with the CPU oracle, which restates raytrace_comp.comp:90-470 op for op.
 The oracle is exhaustive DFS on one CPU core per thread, so it checks every
 k-th row (row_stride / row_phase of oracle_render) instead of the whole frame.

@@ -1,0 +1,100 @@
+"""The launch plan on the CPU: every row of tests/plan_cases.py through
+tests/plan_check.cpp, a host program around plan_launch (csrc/pt_plan.h).
+
+The plan decides which kernel a frame runs on and with how many lanes; apart
+from this table those decisions show only on a GPU (tests/test_gpu_plan.py runs
+the table's cheap rows there)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+import plan_cases
+from plan_cases import ROWS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "discovering-path-tracer_amd", "csrc")
+BUILD = os.path.join(ROOT, "tests", "_build")
+
+
+def _harness():
+    src = os.path.join(ROOT, "tests", "plan_check.cpp")
+    exe = os.path.join(BUILD, "plan_check")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("pt_plan.h", "pt_context.h", "pt_device.h", "pt_group.h")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        os.makedirs(BUILD, exist_ok=True)
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", CSRC,
+                               "-o", exe, src])
+    return exe
+
+
+def line_of(r):
+    """The row as plan_check reads it."""
+    f = r["facts"]
+    boxes, leaves, hull = f["sweep"]
+    w = dict(n_tris=f["tris"], n_nodes=f["nodes"], n_nodes_full=f["nodes_full"], n_wide=f["n_wide"],
+             has_sweep=int(boxes > 0), sweep_boxes=boxes, sweep_leaves=leaves, sweep_hull=hull,
+             exit_normals=f["exit_normals"], stats_mode=r["stats"], nranks=r["ranks"], rank=0, width=r["size"][0],
+             height=r["size"][1], n_tiles=plan_cases.n_tiles(r), n_batches=r["batches"], packed=r["packed"])
+    for k, v in r["opts"].items():
+        w[plan_cases.OPT_FIELD[k]] = v
+    words = [f"{k}={v}" for k, v in w.items()]
+    if f["lights"]:
+        words.append("lights=" + ",".join(repr(float(x)) for x in f["lights"]))
+    return " ".join(words)
+
+
+@pytest.fixture(scope="module")
+def plans():
+    out = subprocess.run([_harness()], input="\n".join(line_of(r) for r in ROWS) + "\n", capture_output=True,
+                         text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(ROWS)
+    return {r["name"]: ln for r, ln in zip(ROWS, lines)}
+
+
+@pytest.mark.parametrize("r", ROWS, ids=[r["name"] for r in ROWS])
+def test_row(plans, r):
+    got, want = plans[r["name"]], r["expect"]
+    if isinstance(want, str):
+        first = int(want.startswith("PT_OPT_MOMENTS"))   # refused before the render touches anything
+        assert got == f"refuse_code={plan_cases.UNSUPPORTED} first={first} refuse={want}"
+        return
+    assert not got.startswith("refuse"), got
+    plan = {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", got)}
+    assert plan == want, {k: (plan.get(k), want[k]) for k in want if plan.get(k) != want[k]}
+
+
+def test_table_holds_both_sides_of_every_threshold():
+    """The rows the thresholds need are there (by the facts, not by name)."""
+    def has(pred):
+        return any(pred(r) for r in ROWS)
+
+    paths = lambda r: plan_cases.n_tiles(r) * 256 * r["batches"]
+    for t in (16383, 16384):
+        assert has(lambda r: r["facts"]["tris"] == t and r["facts"]["n_wide"] > 0 and paths(r) >= 1 << 20)
+    for t in (32767, 32768):
+        assert has(lambda r: r["facts"]["tris"] == t and r["facts"]["n_wide"] == 0 and paths(r) >= 1 << 23)
+    for p in ((1 << 20) - 256, 1 << 20):
+        assert has(lambda r: paths(r) == p and r["facts"]["n_wide"] > 0 and r["facts"]["tris"] >= 16384)
+        assert has(lambda r: paths(r) == p and r["facts"]["n_wide"] == 0 and r["facts"]["tris"] == 1 << 20)
+    for p in ((1 << 23) - 256, 1 << 23):
+        assert has(lambda r: paths(r) == p and r["facts"]["n_wide"] == 0 and 32768 <= r["facts"]["tris"] < 1 << 20)
+    for rec in (3072, 3073):
+        assert has(lambda r: 2 * r["facts"]["nodes"] + 3 * r["facts"]["tris"] == rec and not r["opts"])
+    for ranks in (1, 2, 7, 8):
+        assert has(lambda r: r["ranks"] == ranks and "SAMPLE_LANES" not in r["opts"])
+    for b in (1, 2, 4, 8):
+        assert has(lambda r: r["ranks"] == 8 and r["batches"] == b)
+    for boxes in (15, 16):
+        for o in (None, 0, 1):
+            assert has(lambda r: r["facts"]["sweep"][0] == boxes and r["opts"].get("SMALL_SWEEP") == o)
+    for g in (99, 100):
+        assert has(lambda r: r["opts"].get("WF_GRID") == g and "WF_REFILL" not in r["opts"])
+    for t in (0x1fffffff, 0x20000000):
+        assert has(lambda r: r["facts"]["tris"] == t)
+    texts = {r["expect"] for r in ROWS if isinstance(r["expect"], str)}
+    assert texts == {plan_cases.T_MOM_PACKED, plan_cases.T_MOM_RANKS, plan_cases.T_MOM_STATS, plan_cases.T_MOM_COUNT,
+                     plan_cases.T_LDS, plan_cases.T_STATS_WF}
