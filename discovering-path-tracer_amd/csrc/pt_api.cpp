@@ -669,6 +669,11 @@ static int render_params(pt_context* c, const LaunchPlan& plan, uint32_t first_b
     p->sweep_hull = plan.sweep_hull;
     p->sweep_boxes = c->sweep_boxes;
     p->sweep_leaves = c->sweep_leaves;
+    if (plan.sweep_cube) {   // the straight-line walk's table: the root box is root_lo / root_hi above
+      p->sweep_cube = 1;
+      memcpy(p->cube_under, c->cube_under, sizeof p->cube_under);
+      p->cube_all = c->cube_all;
+    }
   }
   p->item_order = plan.item_order;
   return PT_OK;
@@ -919,6 +924,7 @@ static void scene_release(pt_context* c) {
   dev_free(c->d_sweep);
   dev_free(c->d_sweep_plain);
   c->sweep_boxes = c->sweep_leaves = c->sweep_hull = 0;
+  c->sweep_cube = false;
   dev_free(c->d_wide);
   dev_free(c->d_wide_q);
   dev_free(c->d_wide_leafbox);
@@ -1192,6 +1198,11 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->sweep_boxes = has_sweep ? sweep.n_boxes : 0;
   c->sweep_leaves = has_sweep ? sweep.n_leaves : 0;
   c->sweep_hull = has_sweep ? sweep.n_hull : 0;
+  // the cube table's walk reads the root box from root_lo / root_hi: only where box 0 of the table is that, bitwise
+  c->sweep_cube = has_sweep && sweep.cube && memcmp(&sweep.boxes[0], lo, sizeof lo) == 0 &&
+                  memcmp(&sweep.boxes[4], hi, sizeof hi) == 0;
+  memcpy(c->cube_under, sweep.cube_under, sizeof c->cube_under);
+  c->cube_all = sweep.cube_all;
   memcpy(c->root_lo, lo, sizeof lo);
   memcpy(c->root_hi, hi, sizeof hi);
   c->exit_normals = exit_normals;
@@ -1520,6 +1531,7 @@ static const IntOption kIntOptions[] = {
     {PT_OPT_CULL_TIGHT, &pt_context::opt_cull_tight, 0, 1, "PT_OPT_CULL_TIGHT takes 0 or 1"},
     {PT_OPT_SWEEP_HULL, &pt_context::opt_sweep_hull, 0, 1, "PT_OPT_SWEEP_HULL takes 0 or 1"},
     {PT_OPT_EXIT_SKIP, &pt_context::opt_exit_skip, 0, 1, "PT_OPT_EXIT_SKIP takes 0 or 1"},
+    {PT_OPT_SWEEP_CUBE, &pt_context::opt_sweep_cube, 0, 1, "PT_OPT_SWEEP_CUBE takes 0 or 1"},
 };
 
 int pt_set_option(pt_context* c, int key, int value) {
@@ -1703,6 +1715,13 @@ int pt_sweep_info(pt_context* c, int* boxes, int* leaves) {
   const bool on = sweep_in_force(c);
   *boxes = on ? c->sweep_boxes : 0;
   *leaves = on ? c->sweep_leaves : 0;
+  return PT_OK;
+}
+
+int pt_sweep_walk(pt_context* c, int* walk) {
+  if (c && c->group) return ptg::sweep_walk(c->group, walk);
+  if (!c || !walk) return fail(PT_ERR_INVALID, "null argument");
+  *walk = sweep_in_force(c) ? sweep_walk_kind(*c) : 0;
   return PT_OK;
 }
 

@@ -75,6 +75,11 @@ struct pt_context {
   float4* d_sweep_plain = nullptr;  // ... and the same table without hull codes (PT_OPT_SWEEP_HULL 0)
   int sweep_boxes = 0, sweep_leaves = 0;
   int sweep_hull = 0;               // boxes of the table with a hull code
+  // the cube table (scene/small_sweep.h SmallSweep::cube, its box 0 bitwise root_lo / root_hi below): the
+  // faces' under words and the root's, as the SWEEP 3 kernels take them (PT_OPT_SWEEP_CUBE)
+  bool sweep_cube = false;
+  uint32_t cube_under[6] = {0, 0, 0, 0, 0, 0};
+  uint32_t cube_all = 0;
   // culled wide walk (wide_walk.h): nodes, triangle records by rank, rank ->
   // slot, per-lane stack overflow areas (grown on demand)
   float4* d_wide = nullptr;
@@ -116,6 +121,7 @@ struct pt_context {
   int opt_count = 0;          // PT_OPT_COUNT_TRACED
   int opt_small_sweep = -1;   // PT_OPT_SMALL_SWEEP: -1 auto (kSweepAutoBoxes), 0 off, 1 whenever the scene has a table
   int opt_sweep_hull = 1;     // PT_OPT_SWEEP_HULL
+  int opt_sweep_cube = 1;     // PT_OPT_SWEEP_CUBE
   int opt_exit_skip = 1;      // PT_OPT_EXIT_SKIP
   int opt_wide = 1;           // PT_OPT_WIDE
   int opt_wide_node = 64;     // PT_OPT_WIDE_NODE

@@ -184,6 +184,14 @@ struct RenderParams {
   // (profiles/temporal/resource_usage.md).  It sits in the struct's tail padding: the kernel argument
   // keeps its size
   uint32_t seed_base = 0;
+  // the cube table (PT_OPT_SWEEP_CUBE, sweep_walk.h sweep_cands_cube): the under words of the root box's six
+  // faces in the order x lo, x hi, y lo, y hi, z lo, z hi (0: the table has no such face) and the root's own;
+  // the root box itself is root_lo / root_hi above.  Read by the SWEEP 3 instantiations only, as one run of words
+  // from root_lo to cube_all (pt_device.hip sweep_cube_words: keep them adjacent); after every older member.
+  // sweep_cube: host only, picks those instantiations (launch_render)
+  uint32_t cube_under[6] = {};
+  uint32_t cube_all = 0;
+  int sweep_cube = 0;
 };
 constexpr int kMixShift = 24;
 constexpr int kMaxCullRects = 8;

@@ -292,26 +292,72 @@ __device__ __forceinline__ void walk_pair(const RenderParams& P, bool has_s, v3 
 // its leaf's (P.hit_tris is the same array).  A wave none of whose rays passes
 // the root box has no candidates.  One kernel for every table (up to 64
 // boxes, 32 leaves): the lanes hold a leaf mask only, no box mask.
-template <bool HULL>
+// SWEEP: 1 a table without hull faces, 2 with some, 3 the cube table, whose
+// walk reads the root box and the faces' under words from the parameters and
+// nothing through P.sweep (sweep_cands_cube).
+//
+// The cube table's 13 words -- root_lo, root_hi, cube_under[], cube_all, one run
+// of RenderParams -- are read from the kernel argument segment at each walk,
+// issued ahead of the three rcp_ and waited on once, past them.  Left to the
+// compiler they stay in 13 scalar registers for the whole kernel, which cost
+// more in spilled scalars than the loads do (53 against 34; profiles/cube: the
+// frame 0.128 against 0.120 ms), so the offset goes through an empty asm that
+// keeps the loads where they are written.  Only for a kernel whose first
+// argument is the RenderParams (render_kernel).
+struct CubeWords {
+  float lo[3], hi[3];
+  uint32_t under[6], all;
+};
+static_assert(offsetof(RenderParams, root_lo) % 4 == 0 &&
+                  offsetof(RenderParams, root_hi) == offsetof(RenderParams, root_lo) + 12 &&
+                  offsetof(RenderParams, cube_under) == offsetof(RenderParams, root_lo) + 28 &&
+                  offsetof(RenderParams, cube_all) == offsetof(RenderParams, root_lo) + 52,
+              "sweep_cube_words reads root_lo .. cube_all as one run of words");
+template <int SWEEP>
+__device__ __forceinline__ CubeWords sweep_cube_words() {
+  CubeWords w = {};
+  if constexpr (SWEEP == 3) {
+    typedef const __attribute__((address_space(4))) uint32_t* KernargWords;
+    uint32_t at = (uint32_t)(offsetof(RenderParams, root_lo) / 4);
+    __asm__ volatile("" : "+s"(at));
+    const KernargWords k = (KernargWords)__builtin_amdgcn_kernarg_segment_ptr() + at;
+    for (int i = 0; i < 3; ++i) w.lo[i] = u2f(k[i]), w.hi[i] = u2f(k[3 + i]);
+    for (int i = 0; i < 6; ++i) w.under[i] = k[7 + i];   // (k[6] is seed_base)
+    w.all = k[13];
+  }
+  return w;
+}
+
+template <int SWEEP>
+__device__ uint32_t sweep_trace_cands(const RenderParams& P, const CubeWords& w, v3 o, v3 inv, bool* none) {
+  if constexpr (SWEEP == 3) {
+    return sweep_cands_cube(o, inv, w.lo, w.hi, w.under, w.all, none);
+  } else {
+    const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
+    return sweep_cands<SWEEP == 2>(o, inv, tb, none);
+  }
+}
+
+template <int SWEEP>
 __device__ Hit sweep_trace_closest(const RenderParams& P, v3 o, v3 d) {
+  const CubeWords w = sweep_cube_words<SWEEP>();
   const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
-  const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
   Hit r;
   r.t = 1e30f;
   r.tri = -1;
   bool none;
-  const uint32_t lm = sweep_cands<HULL>(o, inv, tb, &none);
+  const uint32_t lm = sweep_trace_cands<SWEEP>(P, w, o, inv, &none);
   if (none) return r;
   sweep_closest(o, d, lm, P.tris, &r.t, &r.tri);
   return r;
 }
 
-template <bool HULL>
+template <int SWEEP>
 __device__ bool sweep_trace_occluded(const RenderParams& P, v3 o, v3 d, float limit) {
+  const CubeWords w = sweep_cube_words<SWEEP>();
   const v3 inv = mk(rcp_(d.x), rcp_(d.y), rcp_(d.z));
-  const SweepTable tb = {P.sweep, P.sweep_boxes, P.sweep_leaves};
   bool none;
-  const uint32_t lm = sweep_cands<HULL>(o, inv, tb, &none);
+  const uint32_t lm = sweep_trace_cands<SWEEP>(P, w, o, inv, &none);
   if (none) return false;
   return sweep_occluded(o, d, limit, lm, P.tris);
 }
@@ -452,20 +498,21 @@ __device__ __forceinline__ v3 unpark3(const float* pk, int i) {
 
 // pathTrace (:300-418)
 // SWEEP: the walks are the box sweep's (no candidate queue: the parked state
-// starts at cand); 2: of a table with hull faces (sweep_walk.h sweep_slab_hull).
+// starts at cand); 2: of a table with hull faces (sweep_walk.h sweep_slab_hull);
+// 3: of the cube table (sweep_cands_cube).
 template <bool STATS, bool PF, bool CNT = false, int SWEEP = 0>
 __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr& c, int* cand) {
   constexpr bool PARK = !STATS && !PF;
   float* pk = (float*)(cand + (SWEEP ? 0 : kCand) * 64);
   auto closest = [&](v3 o, v3 d, Ctr& cc) {
     if constexpr (SWEEP)
-      return sweep_trace_closest<SWEEP == 2>(P, o, d);
+      return sweep_trace_closest<SWEEP>(P, o, d);
     else
       return trace_closest<STATS, PF, false, CNT>(P, o, d, cc, cand);
   };
   auto shadowed = [&](v3 o, v3 d, float limit) {
     if constexpr (SWEEP)
-      return sweep_trace_occluded<SWEEP == 2>(P, o, d, limit);
+      return sweep_trace_occluded<SWEEP>(P, o, d, limit);
     else
       return occluded<STATS, PF, CNT>(P, o, d, limit, c);
   };
@@ -888,7 +935,9 @@ __device__ unsigned long long g_wg_trace[kWgTraceCap][4];
 // P.sweep; only the triangle records are staged, by leaf.  SWEEP 2: the table
 // has hull faces (P.sweep_hull) and the walk reuses the root's slab products
 // for them; a table without any runs SWEEP 1, the walk that keeps nothing
-// from the root's test.
+// from the root's test.  SWEEP 3: the cube table (P.sweep_cube: every box but
+// the root is a hull face), walked straight-line from P.root_lo / root_hi and
+// P.cube_under / cube_all with no read through P.sweep (PT_OPT_SWEEP_CUBE).
 // MOMENTS (PT_OPT_MOMENTS; never with STATS or CNT): the lane that folds a
 // pixel's red also folds the sample luminances L and L * L into P.moments, in
 // batch order with the colour's own step (fold_one).
@@ -2920,11 +2969,15 @@ hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipS
   void (*kern)(RenderParams);
   const bool ex = p.exit_skip != 0 && !stats;   // the exit skip: device-memory scenes take the EXIT instantiations
   if (p.moments)   // PT_OPT_MOMENTS: the same choice among the MOMENTS instantiations
-    kern = sweep ? (p.sweep_hull ? render_kernel<false, true, false, 2, true> : render_kernel<false, true, false, 1, true>)
+    kern = sweep ? (p.sweep_cube   ? render_kernel<false, true, false, 3, true>
+                    : p.sweep_hull ? render_kernel<false, true, false, 2, true>
+                                   : render_kernel<false, true, false, 1, true>)
                  : (lds_scene ? render_kernel<false, true, false, 0, true>
                               : (ex ? render_kernel<false, false, false, 0, true, true> : render_kernel<false, false, false, 0, true>));
   else if (sweep)
-    kern = p.sweep_hull ? render_kernel<false, true, false, 2> : render_kernel<false, true, false, 1>;
+    kern = p.sweep_cube   ? render_kernel<false, true, false, 3>
+           : p.sweep_hull ? render_kernel<false, true, false, 2>
+                          : render_kernel<false, true, false, 1>;
   else if (cnt)
     kern = lds_scene ? render_kernel<false, true, true>
                      : (ex ? render_kernel<false, false, true, 0, false, true> : render_kernel<false, false, true>);

@@ -52,6 +52,7 @@ int reset_stats(pt_group* g);
 int get_traced(pt_group* g, pt_traced* out);
 int wide_info(pt_group* g, int info[2]);
 int sweep_info(pt_group* g, int* boxes, int* leaves);
+int sweep_walk(pt_group* g, int* walk);
 int last_launch_ms(pt_group* g, float* ms);
 int launch_times_ms(pt_group* g, float* out, size_t max_n, size_t* n_out);
 int launch_span_ms(pt_group* g, float* ms, size_t* n_out);

@@ -38,6 +38,15 @@ inline bool sweep_in_force(const pt_context* c) {
   return wanted && c->opt_scene_lds != 0 && c->opt_kernel != 3 && !c->stats_mode && c->opt_count == 0;
 }
 
+// Which sweep walk those launches run (pt_sweep_walk): 1 the walk that keeps nothing from the root's
+// test, 2 the one that tests hull faces with the root's products (PT_OPT_SWEEP_HULL, a table that has
+// some), 3 the straight-line walk of a cube table (PT_OPT_SWEEP_CUBE): a hull table with no other box.
+// A hull table that also has a general or an uncoded box stays on 2.
+inline int sweep_walk_kind(const pt_context& c) {
+  if (!c.opt_sweep_hull || c.sweep_hull <= 0) return 1;
+  return c.opt_sweep_cube && c.sweep_cube ? 3 : 2;
+}
+
 // The LDS rule (PT_OPT_SCENE_IN_LDS) of a scene of n_nodes threaded nodes: 2 asks for the LDS
 // variant and is refused when the scene cannot fit, 1 stages a scene that fits, 0 none.
 constexpr const char* kLdsTooLarge = "scene too large for the LDS variant";
@@ -68,6 +77,7 @@ struct LaunchPlan {
   bool cnt = false;             // traced-work counters (PT_OPT_COUNT_TRACED)
   bool sweep = false;           // the sweep walk ...
   bool sweep_hull = false;      // ... reading the table with hull codes, and finding some
+  bool sweep_cube = false;      // ... all of whose boxes but the root are hull faces: the straight-line walk
   bool wide = false;            // the wavefront pipeline's culled wide walk
   bool mixed_eligible = false;  // mixed lanes, if the frame has cull rectangles
   int item_order = 0, exit_skip = 0;
@@ -151,7 +161,9 @@ inline LaunchPlan plan_launch(const pt_context& c, long long n_tiles, uint32_t n
   pl.cnt = c.opt_count != 0 && !c.stats_mode;
   // the sweep walk (PT_OPT_SMALL_SWEEP): the plain LDS kernel of a scene with a table
   pl.sweep = pl.lds && !pl.wf && !pl.cnt && sweep_in_force(&c);
-  pl.sweep_hull = pl.sweep && c.opt_sweep_hull && c.sweep_hull > 0;
+  const int walk = pl.sweep ? sweep_walk_kind(c) : 0;
+  pl.sweep_hull = walk >= 2;
+  pl.sweep_cube = walk == 3;
   // PT_OPT_ITEM_ORDER auto: scan order for a whole frame on the path-recursive
   // kernel (box 1080p8 at 4 lanes, one context: 0.2403 against 0.2463 ms
   // heaviest first, profiles/r06b), heaviest first on a share of the frame

@@ -107,6 +107,25 @@ bool build_small_sweep(const float* collapsed, size_t n_kept, SmallSweep* out, i
     for (int b = 0; b < s.n_boxes; ++b)
       if (s.need[(size_t)l] >> b & 1u) s.under[(size_t)b] |= 1u << l;
   for (int b = 0; b < s.n_boxes; ++b) memcpy(&s.boxes[8 * (size_t)b + 3], &s.under[(size_t)b], 4);
+  // the cube table: every box past the root has a hull code (so none is general), one box per (axis, code)
+  s.cube = true;
+  s.cube_all = s.under[0];
+  bool taken[6] = {false, false, false, false, false, false};
+  for (int b = 1; b < s.n_boxes && s.cube; ++b) {
+    const float* r = &s.boxes[8 * (size_t)b];
+    uint32_t code;
+    memcpy(&code, r + 7, 4);
+    int flat = -1;
+    for (int a = 2; a >= 0; --a)
+      if (memcmp(r + a, r + 4 + a, 4) == 0) flat = a;   // the first flat axis: the one the code is about
+    if (flat < 0 || (code != 1u && code != 2u) || taken[2 * flat + (int)code - 1]) {
+      s.cube = false;
+      break;
+    }
+    taken[2 * flat + (int)code - 1] = true;
+    s.cube_under[2 * flat + (int)code - 1] = s.under[(size_t)b];
+  }
+  if (!s.cube) s.cube_all = 0u, memset(s.cube_under, 0, sizeof s.cube_under);
   *out = s;
   return true;
 }

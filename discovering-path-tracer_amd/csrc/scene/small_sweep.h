@@ -31,6 +31,13 @@ struct SmallSweep {
   std::vector<int32_t> slot;     // per leaf: its triangle slot
   int n_boxes = 0, n_leaves = 0;
   int n_hull = 0;                // boxes with a hull code
+  // The cube table: no general box, every flat box has a hull code, at most one box per (axis, code) -- every box
+  // other than the root is a face of it (the box, a cuboid, a cuboid without some face).  sweep_walk.h
+  // sweep_cands_cube then needs no record: cube_under[] are the faces' under words in the fixed order x lo, x hi,
+  // y lo, y hi, z lo, z hi (0: no such face), cube_all the root's
+  bool cube = false;
+  uint32_t cube_under[6] = {0, 0, 0, 0, 0, 0};
+  uint32_t cube_all = 0;
   // The device table (sweep_walk.h SweepTable): boxes, need[] (32-bit words
   // for up to 32 boxes, else 64-bit) padded to whole float4s, slot[].
   // hull_codes false: the same table with every hull code 0.

@@ -35,6 +35,12 @@
 //     operands, same operations, same bits, NaNs included.  The branch on the
 //     code is scalar.  A table without hull faces is walked by
 //     sweep_cands<false>, which keeps nothing from the root's test.
+//   * A table all of whose boxes but the root are hull faces (the cube table:
+//     the box, a cuboid, a cuboid without some face) needs no record at all:
+//     sweep_cands_cube takes the root box and the faces' under words from its
+//     caller and tests the six faces straight-line, their axis and code fixed
+//     at compile time -- the booleans sweep_cands<true> forms, ORed in another
+//     order.
 //   * sweep_mask / sweep_leaves state the same predicate from need[] in two
 //     passes (box bits, then (sb & need[l]) == need[l] per leaf).  The device
 //     does not call them: they are the restatement the tests hold sweep_cands
@@ -294,6 +300,40 @@ PT_FN uint32_t sweep_cands(v3 o, v3 inv, const SweepTable& t, bool* none) {
   if (*none) return 0u;
   if constexpr (HULL) sweep_root_detach(&R);
   return sweep_fold_vals<HULL>(o, inv, t, R, root);
+}
+
+// The sweep of a cube table (scene/small_sweep.h SmallSweep::cube): every box
+// other than the root [lo, hi] is a hull face of it, at most one per (axis,
+// code).  A hull face's test reads nothing but the root's six products and its
+// code (sweep_slab_hull), and the answer ORs the under words of the failing
+// boxes, which does not depend on their order or on where their words come
+// from.  So the walk needs no record: the six faces in the fixed order x lo,
+// x hi, y lo, y hi, z lo, z hi with their axis and code known at compile time,
+// under[f] the face's under word or 0 where the table has no such face (its
+// boolean then ORs nothing), `all` the root's.  The same booleans from the same
+// operands as sweep_cands<true>: the same leaf mask and *none bit for bit, NaNs
+// of 0 * inf included.  No loop, no branch on the table, no load but the
+// caller's lo, hi, under and all; the products are not detached from the root's
+// test (sweep_root_detach): the compiler may keep the per-axis min/max.
+PT_FN uint32_t sweep_cands_cube(v3 o, v3 inv, const float* lo, const float* hi, const uint32_t* under, uint32_t all,
+                                bool* none) {
+  const SweepBox r0 = {lo[0], lo[1], lo[2], 0.0f, hi[0], hi[1], hi[2], 0.0f};
+  const SweepRootVals R = sweep_root_vals(o, inv, r0);
+  const bool root = sweep_root_pass(R);
+#if defined(__HIP_DEVICE_COMPILE__)
+  *none = __builtin_amdgcn_ballot_w64(root) == 0;
+#else
+  *none = !root;
+#endif
+  if (*none) return 0u;
+  uint32_t fail = root ? 0u : all;
+  fail |= sweep_slab_hull<0>(R, 1u) ? 0u : under[0];
+  fail |= sweep_slab_hull<0>(R, 2u) ? 0u : under[1];
+  fail |= sweep_slab_hull<1>(R, 1u) ? 0u : under[2];
+  fail |= sweep_slab_hull<1>(R, 2u) ? 0u : under[3];
+  fail |= sweep_slab_hull<2>(R, 1u) ? 0u : under[4];
+  fail |= sweep_slab_hull<2>(R, 2u) ? 0u : under[5];
+  return all & ~fail;
 }
 
 // Closest hit over the leaf mask: leaves in visit order, triangle records by

@@ -46,6 +46,7 @@ PT_OPT_SWEEP_HULL = 26
 PT_OPT_MOMENTS = 27
 PT_OPT_EXIT_SKIP = 28
 PT_OPT_SEED_BASE = 29
+PT_OPT_SWEEP_CUBE = 30
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -63,7 +64,7 @@ EXPORTS = [
     "pt_set_partition_slots", "pt_get_traced", "pt_wide_info", "pt_partition_items",
     "pt_dist_unique_id", "pt_dist_init", "pt_dist_run", "pt_dist_slot_floats", "pt_dist_finalize",
     "pt_dist_set_streams", "pt_dist_wait", "pt_dist_abort", "pt_create_multi", "pt_group_info",
-    "pt_group_check", "pt_dist_info", "pt_mixed_info", "pt_sweep_info",
+    "pt_group_check", "pt_dist_info", "pt_mixed_info", "pt_sweep_info", "pt_sweep_walk",
     "pt_denoise_default_params", "pt_guide_ray", "pt_render_guide", "pt_guide_device_ptr", "pt_read_guide",
     "pt_denoise", "pt_read_denoised", "pt_denoise_host",
     "pt_moments_device_ptr", "pt_read_moments", "pt_denoise_var_default_params", "pt_denoise_var",
@@ -156,6 +157,7 @@ def lib():
             "pt_wide_info": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
             "pt_mixed_info": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
             "pt_sweep_info": ([vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], i32),
+            "pt_sweep_walk": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
             "pt_partition_items": ([i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, psz, vp, psz, vp], i32),
             "pt_dist_unique_id": ([vp, sz], i32), "pt_dist_init": ([vp, vp, i32, i32], i32),
             "pt_dist_run": ([vp, u32, i32, i32, vp, i32], i32), "pt_dist_slot_floats": ([vp, psz], i32),
@@ -937,6 +939,15 @@ class Renderer:
         b, n = ctypes.c_int(0), ctypes.c_int(0)
         _check(lib().pt_sweep_info(self._c, ctypes.byref(b), ctypes.byref(n)), "pt_sweep_info")
         return b.value, n.value
+
+    def sweep_walk(self):
+        """Which walk the launches run as the options stand: 0 the threaded
+        walk, 1 the sweep that keeps nothing from the root's test, 2 the sweep
+        with hull faces (PT_OPT_SWEEP_HULL), 3 the straight-line sweep of a
+        cube table (PT_OPT_SWEEP_CUBE)."""
+        w = ctypes.c_int(0)
+        _check(lib().pt_sweep_walk(self._c, ctypes.byref(w)), "pt_sweep_walk")
+        return w.value
 
     def mixed_info(self):
         """(schedule, live workgroups, measured launches) of the last launch:

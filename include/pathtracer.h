@@ -53,7 +53,8 @@ extern "C" {
  * pt_temporal_device_ptr, pt_read_temporal, pt_temporal_denoise,
  * pt_denoise_var_plane_host); the spatial variance estimate of short histories
  * (pt_spatial_var_params, pt_spatial_var_default_params,
- * pt_spatial_variance_host, pt_spatial_variance, pt_temporal_denoise_spatial). */
+ * pt_spatial_variance_host, pt_spatial_variance, pt_temporal_denoise_spatial);
+ * the straight-line sweep of a cube table (PT_OPT_SWEEP_CUBE, pt_sweep_walk). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -849,6 +850,17 @@ int pt_dist_finalize(pt_context* ctx);
  * Every render path (multi-device contexts forward it).  0: the frames of
  * before. */
 #define PT_OPT_SEED_BASE 29
+/* PT_OPT_SWEEP_CUBE: a sweep table in which every box other than the root is
+ * a hull face of it (PT_OPT_SWEEP_HULL; no general box, no uncoded flat box:
+ * box.obj, a cuboid, a cuboid without some face) is walked by a straight-line
+ * kernel: the root's six slab products, its test, the one ballot, then the six
+ * faces with their axis and side fixed at compile time, their leaf masks and
+ * the root box taken from the kernel's parameters -- no loop over the table
+ * and no record load.  The same booleans from the same operands as the hull
+ * walk, so the same bits.  1 (default) = on; 0 = the
+ * hull walk.  A table with any other box runs the hull walk either way;
+ * pt_sweep_walk tells which walk is in force.  Output is identical. */
+#define PT_OPT_SWEEP_CUBE 30
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
@@ -897,6 +909,11 @@ int pt_wide_info(pt_context* ctx, int info[2]);
  * mode nor PT_OPT_COUNT_TRACED is on (the same predicate pt_render uses) --
  * else zeros. */
 int pt_sweep_info(pt_context* ctx, int* boxes, int* leaves);
+/* Which walk those launches run, by the same predicate: *walk = 0 the
+ * threaded walk, 1 the sweep that keeps nothing from the root's test, 2 the
+ * sweep with hull faces (PT_OPT_SWEEP_HULL), 3 the straight-line sweep of a
+ * cube table (PT_OPT_SWEEP_CUBE). */
+int pt_sweep_walk(pt_context* ctx, int* walk);
 /* Mixed sample lanes of the last path-recursive launch (PT_OPT_MIXED_LANES):
  * info[0] = 0 uniform lanes, 1 the static mixed schedule, 2 the measured one;
  * info[1] = live workgroups it launched; info[2] = measuring launches folded
