@@ -1,6 +1,6 @@
 // pt_cull.h — the radius bounds of primary-ray culling, shared by the host
 // derivation (pt_cull.cpp cull_rects), the render kernel's per-sample test
-// (pt_device.hip) and tests/cull_radius_check.cpp.
+// (kernels/render.h) and tests/cull_radius_check.cpp.
 #pragma once
 #include "pt_math.h"
 

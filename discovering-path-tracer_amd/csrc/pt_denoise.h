@@ -1,6 +1,6 @@
 // pt_denoise.h — the first-hit guide ray and the edge-avoiding a-trous filter
 // (Dammertz et al., HPG 2010), stated once for the device kernels
-// (guide_kernel in pt_device.hip, atrous_kernel in pt_denoise.hip) and the host
+// (guide_kernel in kernels/guide.h, atrous_kernel in pt_denoise.hip) and the host
 // (pt_guide_ray, pt_denoise_host in pt_post.cpp), the way wide_walk.h is
 // shared with tests/wide_check.cpp: both run the same statements, compiled
 // with -ffp-contract=off, so the device image equals the host's bit for bit.

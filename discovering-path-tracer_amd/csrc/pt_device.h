@@ -187,7 +187,7 @@ struct RenderParams {
   // the cube table (PT_OPT_SWEEP_CUBE, sweep_walk.h sweep_cands_cube): the under words of the root box's six
   // faces in the order x lo, x hi, y lo, y hi, z lo, z hi (0: the table has no such face) and the root's own;
   // the root box itself is root_lo / root_hi above.  Read by the SWEEP 3 instantiations only, as one run of words
-  // from root_lo to cube_all (pt_device.hip sweep_cube_words: keep them adjacent); after every older member.
+  // from root_lo to cube_all (kernels/walks.h sweep_cube_words: keep them adjacent); after every older member.
   // sweep_cube: host only, picks those instantiations (launch_render)
   uint32_t cube_under[6] = {};
   uint32_t cube_all = 0;
@@ -293,5 +293,214 @@ long long render_slots(size_t lds_bytes, bool sweep = false);   // sweep: of its
 hipError_t launch_gather_tris(const float4* tris, const int* tri_of, int n, float4* dst, hipStream_t stream);
 hipError_t launch_math(int fn, const float* x, float* y, size_t n, hipStream_t stream);
 hipError_t launch_exhaustive(int fn, unsigned long long* bad, uint32_t* first_bad, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
+// Kernel selection.  What launch_render and launch_wavefront refuse, the grid
+// and dynamic LDS they launch with and the instantiation they run are pure
+// functions of the parameters: they call no HIP function and launch nothing,
+// so a host program table-tests them (tests/plan_check.cpp, tests/test_plan.py)
+// -- most instantiations give bit-identical frames, and no GPU test would
+// notice the wrong one.  Each kernel family's instantiations are listed once,
+// here; pt_device.hip builds its table of kernels from the same list, and a
+// variant that is not listed is hipErrorInvalidValue.
+// ---------------------------------------------------------------------------
+#pragma GCC visibility push(hidden)
+struct RenderVariant {     // render_kernel<STATS, LDS, CNT, SWEEP, MOMENTS, EXIT>
+  bool stats, lds, cnt;
+  int sweep;
+  bool moments, exit;
+};
+struct WfTraceVariant {    // wf_trace_kernel<LDS, G, CNT>
+  bool lds;
+  int group;
+  bool cnt;
+};
+struct WfWideVariant { bool qn, cnt; };          // wf_trace_wide_kernel<CNT, LAYOUT = qn>
+struct WfShadeVariant { bool exit; };            // wf_shade_kernel<EXIT>
+struct WfTailVariant { bool cnt, qn, exit; };    // wf_tail_kernel<CNT, QN, EXIT>
+constexpr bool operator==(const RenderVariant& a, const RenderVariant& b) {
+  return a.stats == b.stats && a.lds == b.lds && a.cnt == b.cnt && a.sweep == b.sweep && a.moments == b.moments &&
+         a.exit == b.exit;
+}
+constexpr bool operator==(const WfTraceVariant& a, const WfTraceVariant& b) {
+  return a.lds == b.lds && a.group == b.group && a.cnt == b.cnt;
+}
+constexpr bool operator==(const WfWideVariant& a, const WfWideVariant& b) { return a.qn == b.qn && a.cnt == b.cnt; }
+constexpr bool operator==(const WfShadeVariant& a, const WfShadeVariant& b) { return a.exit == b.exit; }
+constexpr bool operator==(const WfTailVariant& a, const WfTailVariant& b) {
+  return a.cnt == b.cnt && a.qn == b.qn && a.exit == b.exit;
+}
+
+// The instantiations that exist, X(template arguments in the struct's order).  The kernels lie in the code
+// object in the order they are listed in: keep it when the object is to be compared with an earlier one.
+#define PT_RENDER_VARIANTS(X)                                                                                  \
+  X(false, true, false, 2, true, false) X(false, true, false, 1, true, false)     /* moments: the sweep walks, */ \
+  X(false, true, false, 3, true, false) X(false, false, false, 0, true, true)     /* device memory, LDS */        \
+  X(false, false, false, 0, true, false) X(false, true, false, 0, true, false)                                    \
+  X(false, true, false, 2, false, false) X(false, true, false, 1, false, false)   /* the sweep walks */           \
+  X(false, true, false, 3, false, false)                                                                          \
+  X(false, false, true, 0, false, true) X(false, false, true, 0, false, false)    /* counting */                  \
+  X(false, true, true, 0, false, false)                                                                           \
+  X(true, true, false, 0, false, false) X(false, true, false, 0, false, false)    /* stats and plain */           \
+  X(false, false, false, 0, false, true) X(false, false, false, 0, false, false)                                  \
+  X(true, false, false, 0, false, false)
+#define PT_WF_WIDE_VARIANTS(X) X(true, false) X(true, true) X(false, false) X(false, true)
+#define PT_WF_TRACE_VARIANTS(X)                                                                \
+  X(true, 2, true) X(true, 4, true) X(false, 2, true) X(false, 4, true) X(true, 2, false)      \
+  X(true, 4, false) X(false, 2, false) X(false, 4, false)
+#define PT_WF_SHADE_VARIANTS(X) X(true) X(false)
+#define PT_WF_TAIL_VARIANTS(X)                                                              \
+  X(true, true, true) X(false, true, true) X(true, false, true) X(false, false, true)       \
+  X(true, true, false) X(false, true, false) X(true, false, false) X(false, false, false)
+#define PT_VARIANT_ROW(...) {__VA_ARGS__},
+constexpr RenderVariant kRenderVariants[] = {PT_RENDER_VARIANTS(PT_VARIANT_ROW)};
+constexpr WfTraceVariant kWfTraceVariants[] = {PT_WF_TRACE_VARIANTS(PT_VARIANT_ROW)};
+constexpr WfWideVariant kWfWideVariants[] = {PT_WF_WIDE_VARIANTS(PT_VARIANT_ROW)};
+constexpr WfShadeVariant kWfShadeVariants[] = {PT_WF_SHADE_VARIANTS(PT_VARIANT_ROW)};
+constexpr WfTailVariant kWfTailVariants[] = {PT_WF_TAIL_VARIANTS(PT_VARIANT_ROW)};
+#undef PT_VARIANT_ROW
+template <class V, size_t N>
+constexpr int variant_index(const V (&list)[N], const V& v) {   // -1: no such instantiation
+  for (size_t i = 0; i < N; ++i)
+    if (list[i] == v) return (int)i;
+  return -1;
+}
+
+// The flags' share of launch_render's decision.  sweep_table: 0 no sweep table, 1 a general one, 2 one with
+// hull faces, 3 the cube table; the sweep walk is the plain LDS kernel's only.  exit_skip: device-memory
+// scenes take the EXIT instantiations, the LDS-staged kernels branch on P.exit_skip instead.
+struct RenderPick {
+  bool ok;   // false: refused
+  RenderVariant v;
+};
+constexpr RenderPick pick_render(bool stats, bool lds_scene, bool cnt, int sweep_table, bool moments, bool exit_skip,
+                                 bool pack_out) {
+  if ((cnt && stats) || (pack_out && stats) || (moments && (stats || cnt || pack_out))) return {false, {}};
+  const int sweep = lds_scene && !stats && !cnt ? sweep_table : 0;
+  return {true, {stats, lds_scene, cnt, sweep, moments, exit_skip && !stats && !lds_scene}};
+}
+
+constexpr bool spl_valid(int spl) { return spl == 1 || spl == 2 || spl == 4 || spl == 8; }
+enum class Launch { Refused, Nothing, Run };   // Refused: hipErrorInvalidValue; Nothing: success, no work
+struct RenderLaunch {
+  Launch what = Launch::Refused;
+  long long grid = 0;   // workgroups (0 with Run: a compact launch that lists no item; nothing is launched)
+  size_t lds = 0;       // dynamic LDS bytes
+  RenderVariant v = {};
+};
+// pix_per_fill: the render kernel's kPixPerFill (pixels per thread of its trailing workgroups).
+inline RenderLaunch plan_render(const RenderParams& p, bool stats, bool lds_scene, bool cnt, int pix_per_fill) {
+  RenderLaunch l;
+  if ((cnt && stats) || !spl_valid(p.spl)) return l;
+  // owned tiles (part_tile); the recursive kernel splits each into spl workgroups
+  l.grid = (long long)p.n_tiles * p.spl;
+  if (l.grid <= 0 || p.n_batches == 0) {
+    l.what = Launch::Nothing;
+    return l;
+  }
+  // live items (p.n_items), then the trailing workgroups: with pack_out those that assemble the previous
+  // frame, with a compact list (p.items) those that fill the culled items
+  const long long trailing_px = (long long)(p.pack_out ? p.n_unpack : p.n_culled_items) * (256 / p.spl);
+  if (p.pack_out || p.items) l.grid = p.n_items + (trailing_px + 256 * pix_per_fill - 1) / (256 * pix_per_fill);
+  if (l.grid > 0x7fffffffll) return l;
+  const int table = !p.sweep ? 0 : p.sweep_cube ? 3 : p.sweep_hull ? 2 : 1;
+  const RenderPick pick = pick_render(stats, lds_scene, cnt, table, p.moments != nullptr, p.exit_skip != 0,
+                                      p.pack_out != nullptr);
+  if (!pick.ok) return l;
+  if (pick.v.sweep && (p.sweep_boxes < 1 || p.sweep_boxes > 64 || p.sweep_leaves < 1 || p.sweep_leaves > 32)) return l;
+  l.lds = pick.v.sweep ? sweep_lds_bytes(p) : lds_scene ? scene_lds_bytes(p) : 0;
+  if (l.lds > kMaxSceneLds) return l;
+  l.v = pick.v;
+  l.what = Launch::Run;
+  return l;
+}
+
+// ... and of launch_wavefront's.  wide: the culled wide walk is set up (p.wide); it traces device-memory
+// scenes only.  tail_wanted: p.wf_tail > 0 (wf_tail_kernel takes the short lists: the wide walk's layouts
+// only -- the trace and shading kernels would skip its lists).  group2: fewer than kWfGroup4Tris triangles.
+struct WfPick {
+  bool ok, wide, tail;
+  WfTraceVariant trace;   // !wide
+  WfWideVariant wide_trace;   // wide
+  WfShadeVariant shade;
+  WfTailVariant tail_v;   // tail
+};
+constexpr WfPick pick_wavefront(bool lds_scene, bool wide, bool wide_qn, bool cnt, bool exit_skip, bool moments,
+                                bool tail_wanted, bool group2) {
+  const bool w = wide && !lds_scene;
+  if ((moments && cnt) || (tail_wanted && !w)) return {false, false, false, {}, {}, {}, {}};
+  return {true, w, w && tail_wanted, {lds_scene, group2 ? 2 : 4, cnt}, {wide_qn, cnt}, {exit_skip},
+          {cnt, wide_qn, exit_skip}};
+}
+// Where launch_wavefront stops.  The culled items' fill is launched before the checks that need a live item,
+// so a launch they refuse has run it (FillRefused), as has one without a live item (FillOnly).
+enum class WfStop { Refused, Nothing, FillOnly, FillRefused, Run };
+struct WfLaunch {
+  WfStop stop = WfStop::Refused;
+  long long fill_grid = 0;   // fill_culled_kernel's workgroups (0: not launched)
+  long long px = 0;          // pixels of the live items
+  size_t lds_trace = 0;      // the trace kernel's dynamic LDS bytes
+  WfPick k = {};
+};
+// cap: WfBuffers::cap.  pix_per_fill as above; group4_tris: the trace kernel's kWfGroup4Tris.
+inline WfLaunch plan_wavefront(const RenderParams& p, long long cap, bool lds_scene, bool cnt, int pix_per_fill,
+                               int group4_tris) {
+  WfLaunch l;
+  if ((p.moments && cnt) || !spl_valid(p.spl)) return l;
+  if (p.n_batches == 0) {
+    l.stop = WfStop::Nothing;
+    return l;
+  }
+  const int per = 256 / p.spl;
+  const long long items = p.items ? p.n_items : (long long)p.n_tiles * p.spl;
+  if (p.items && p.n_culled_items > 0)
+    l.fill_grid = ((long long)p.n_culled_items * per + 256 * pix_per_fill - 1) / (256 * pix_per_fill);
+  if (items <= 0) {
+    l.stop = WfStop::FillOnly;
+    return l;
+  }
+  l.stop = WfStop::FillRefused;
+  l.px = items * per;
+  if (l.px > cap || cap > 0x7fffffffll) return l;
+  const size_t lds = lds_scene ? scene_lds_bytes(p) : 0;
+  if (lds > kMaxSceneLds) return l;
+  const WfPick k = pick_wavefront(lds_scene, p.wide != nullptr, p.wide_qn != 0, cnt, p.exit_skip != 0,
+                                  p.moments != nullptr, p.wf_tail > 0, p.n_tris < group4_tris);
+  if (!k.ok) return l;
+  if (k.wide && p.wide_ovf_lanes < 256) return l;   // every lane needs its overflow stack area
+  l.lds_trace = k.wide ? 0 : lds;
+  l.k = k;
+  l.stop = WfStop::Run;
+  return l;
+}
+
+// Every listed instantiation is one the picks above can return, and they return no other.
+template <class V, size_t N>
+constexpr bool all_met(const V (&)[N], unsigned met) { return met == (1u << N) - 1u; }
+constexpr bool variant_lists_exact() {
+  unsigned r = 0, t = 0, w = 0, s = 0, x = 0;   // the listed variants met, as bit sets
+  bool ok = true;
+  auto mark = [&ok](unsigned& met, int i) {
+    ok = ok && i >= 0;
+    met |= i >= 0 ? 1u << i : 0u;
+  };
+  for (int f = 0; f < 256; ++f) {
+    const auto bit = [f](int i) { return ((f >> i) & 1) != 0; };
+    const RenderPick a = pick_render(bit(0), bit(1), bit(2), (f >> 6) & 3, bit(3), bit(4), bit(5));
+    if (a.ok) mark(r, variant_index(kRenderVariants, a.v));
+    const WfPick b = pick_wavefront(bit(0), bit(1), bit(2), bit(3), bit(4), bit(5), bit(6), bit(7));
+    if (!b.ok) continue;
+    if (b.wide)
+      mark(w, variant_index(kWfWideVariants, b.wide_trace));
+    else
+      mark(t, variant_index(kWfTraceVariants, b.trace));
+    mark(s, variant_index(kWfShadeVariants, b.shade));
+    if (b.tail) mark(x, variant_index(kWfTailVariants, b.tail_v));
+  }
+  return ok && all_met(kRenderVariants, r) && all_met(kWfTraceVariants, t) && all_met(kWfWideVariants, w) &&
+         all_met(kWfShadeVariants, s) && all_met(kWfTailVariants, x);
+}
+static_assert(variant_lists_exact(), "the variant lists and the picks disagree");
+#pragma GCC visibility pop
 
 }  // namespace ptd

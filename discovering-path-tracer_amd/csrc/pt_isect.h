@@ -1,5 +1,5 @@
 // pt_isect.h — the reference's two intersection tests, shared by the device
-// kernels (pt_device.hip) and host-side checks of the culled wide walk
+// kernels (kernels/*.h, pt_device.hip) and host-side checks of the culled wide walk
 // (wide_walk.h, tests/wide_check.cpp).  Same float ops, same order as the
 // shader; compiled with -ffp-contract=off like everything in pt_math.h.
 #pragma once

@@ -1,5 +1,5 @@
 // sweep_walk.h — the exact walk of a tiny scene as a wave-uniform box sweep
-// (scene/small_sweep.h builds the table; pt_device.hip's LDS render kernel and
+// (scene/small_sweep.h builds the table; the LDS render kernel, through kernels/walks.h, and
 // tests/sweep_check.cpp, tests/sweep_fold_check.cpp run these functions).
 //
 // Why it returns the threaded walk's hits bit for bit:

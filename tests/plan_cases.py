@@ -219,3 +219,192 @@ row("moments_stats_count", BOX, T_MOM_STATS, opts=dict(MOM, COUNT_TRACED=1), sta
 row("moments_stats_kernel3", BOX, T_MOM_STATS, opts=dict(MOM, KERNEL=3), stats=1)
 row("moments_count_lds", FITS_NOT, T_MOM_COUNT, opts=dict(MOM, COUNT_TRACED=1, SCENE_IN_LDS=2))
 row("lds_stats_kernel3", FITS_NOT, T_LDS, opts={"SCENE_IN_LDS": 2, "KERNEL": 3}, stats=1)
+
+
+# ==== kernel selection (csrc/pt_device.h plan_render, plan_wavefront) ==========================================
+# What launch_render and launch_wavefront launch.  Most instantiations give bit-identical frames, so only these
+# rows notice the wrong one.  The expectations are restatements of the two launchers' conditional ladders as they
+# stood before the selection became a pure function over a table: they do not call the code under test.
+
+K_MAX_SCENE_LDS = 48 * 1024     # pt_device.h kMaxSceneLds
+PIX_PER_FILL = 8                # kernels/render.h kPixPerFill
+GROUP4_TRIS = 500000            # kernels/wf_trace.h kWfGroup4Tris
+
+# The 17 render_kernel instantiations the ladder of launch_render could reach, as
+# (STATS, LDS, CNT, SWEEP, MOMENTS, EXIT): counted from its four arms --
+# moments 6 (three sweep walks, LDS, device memory with and without the exit skip), the sweep walks 3,
+# counting 3 (LDS, device memory with and without the exit skip), the rest 5 (stats and plain on LDS, stats,
+# plain and plain with the exit skip on device memory).
+RENDER_VARIANTS = {
+    (0, 1, 0, 1, 1, 0), (0, 1, 0, 2, 1, 0), (0, 1, 0, 3, 1, 0), (0, 1, 0, 0, 1, 0), (0, 0, 0, 0, 1, 0), (0, 0, 0, 0, 1, 1),
+    (0, 1, 0, 1, 0, 0), (0, 1, 0, 2, 0, 0), (0, 1, 0, 3, 0, 0),
+    (0, 1, 1, 0, 0, 0), (0, 0, 1, 0, 0, 0), (0, 0, 1, 0, 0, 1),
+    (1, 1, 0, 0, 0, 0), (0, 1, 0, 0, 0, 0), (1, 0, 0, 0, 0, 0), (0, 0, 0, 0, 0, 0), (0, 0, 0, 0, 0, 1),
+}
+# ... and launch_wavefront's: wf_trace_kernel<LDS, G, CNT> 8, wf_trace_wide_kernel by (qn, cnt) 4,
+# wf_shade_kernel<EXIT> 2, wf_tail_kernel<CNT, QN, EXIT> 8
+WF_TRACE_VARIANTS = {(l, g, c) for l in (0, 1) for g in (2, 4) for c in (0, 1)}
+WF_WIDE_VARIANTS = {(q, c) for q in (0, 1) for c in (0, 1)}
+WF_SHADE_VARIANTS = {(0,), (1,)}
+WF_TAIL_VARIANTS = {(c, q, e) for c in (0, 1) for q in (0, 1) for e in (0, 1)}
+
+# a launch's words: the launcher's flags and the RenderParams members the selection reads
+RENDER_BASE = dict(stats=0, lds=0, cnt=0, sweep=0, moments=0, exit_skip=0, pack_out=0, items=0, spl=4, n_tiles=4,
+                   n_batches=8, n_items=3, n_culled=5, n_unpack=4000, sweep_boxes=7, sweep_leaves=12, n_nodes=7,
+                   n_tris=12)
+WF_BASE = dict(lds=0, wide=0, wide_qn=0, cnt=0, exit_skip=0, moments=0, wf_tail=0, n_tris=12, spl=4, n_tiles=4,
+               n_batches=8, items=0, n_items=3, n_culled=5, cap=1 << 20, n_nodes=7, wide_ovf_lanes=256)
+
+
+def parent_launch_render(r):
+    """launch_render's ladder: "refused" (hipErrorInvalidValue), "nothing" (success before any decision), or
+    ("run", grid, dynamic LDS bytes, the instantiation)."""
+    stats, lds_scene, cnt, spl = r["stats"], r["lds"], r["cnt"], r["spl"]
+    if cnt and stats:
+        return "refused"
+    if spl not in (1, 2, 4, 8):
+        return "refused"
+    grid = r["n_tiles"] * spl
+    if grid <= 0 or r["n_batches"] == 0:
+        return "nothing"
+    if r["pack_out"] and stats:
+        return "refused"
+    if r["pack_out"]:
+        px = r["n_unpack"] * (256 // spl)
+        grid = r["n_items"] + (px + 256 * PIX_PER_FILL - 1) // (256 * PIX_PER_FILL)
+    elif r["items"]:
+        px = r["n_culled"] * (256 // spl)
+        grid = r["n_items"] + (px + 256 * PIX_PER_FILL - 1) // (256 * PIX_PER_FILL)
+    if grid > 0x7fffffff:
+        return "refused"
+    sweep = bool(r["sweep"]) and lds_scene and not stats and not cnt
+    if sweep and (r["sweep_boxes"] < 1 or r["sweep_boxes"] > 64 or r["sweep_leaves"] < 1 or r["sweep_leaves"] > 32):
+        return "refused"
+    lds = 3 * r["sweep_leaves"] * 16 if sweep else (2 * r["n_nodes"] + 3 * r["n_tris"]) * 16 if lds_scene else 0
+    if lds > K_MAX_SCENE_LDS:
+        return "refused"
+    if r["moments"] and (stats or cnt or r["pack_out"]):
+        return "refused"
+    cube, hull = r["sweep"] == 3, r["sweep"] >= 2   # p.sweep_cube, p.sweep_hull
+    ex = r["exit_skip"] and not stats
+    if r["moments"]:
+        if sweep:
+            k = (0, 1, 0, 3, 1, 0) if cube else (0, 1, 0, 2, 1, 0) if hull else (0, 1, 0, 1, 1, 0)
+        elif lds_scene:
+            k = (0, 1, 0, 0, 1, 0)
+        else:
+            k = (0, 0, 0, 0, 1, 1) if ex else (0, 0, 0, 0, 1, 0)
+    elif sweep:
+        k = (0, 1, 0, 3, 0, 0) if cube else (0, 1, 0, 2, 0, 0) if hull else (0, 1, 0, 1, 0, 0)
+    elif cnt:
+        if lds_scene:
+            k = (0, 1, 1, 0, 0, 0)
+        else:
+            k = (0, 0, 1, 0, 0, 1) if ex else (0, 0, 1, 0, 0, 0)
+    elif lds_scene:
+        k = (1, 1, 0, 0, 0, 0) if stats else (0, 1, 0, 0, 0, 0)
+    elif stats:
+        k = (1, 0, 0, 0, 0, 0)
+    else:
+        k = (0, 0, 0, 0, 0, 1) if ex else (0, 0, 0, 0, 0, 0)
+    return ("run", grid, lds, k)
+
+
+def parent_launch_wavefront(r):
+    """launch_wavefront's decisions in its order: "refused", "nothing", ("fill_only", fill grid) for a launch
+    without a live item, ("fill_refused", fill grid) for one refused after the culled items' fill was launched, or
+    ("run", fill grid, pixels, the trace kernel's LDS bytes, ("trace" | "wide", variant), shade variant, tail
+    variant or None)."""
+    lds_scene, cnt, spl = r["lds"], r["cnt"], r["spl"]
+    if r["moments"] and cnt:
+        return "refused"
+    if spl not in (1, 2, 4, 8):
+        return "refused"
+    if r["n_batches"] == 0:
+        return "nothing"
+    per = 256 // spl
+    items = r["n_items"] if r["items"] else r["n_tiles"] * spl
+    fill = 0
+    if r["items"] and r["n_culled"] > 0:
+        fill = (r["n_culled"] * per + 256 * PIX_PER_FILL - 1) // (256 * PIX_PER_FILL)
+    if items <= 0:
+        return ("fill_only", fill)
+    px = items * per
+    if px > r["cap"] or r["cap"] > 0x7fffffff:
+        return ("fill_refused", fill)
+    lds = (2 * r["n_nodes"] + 3 * r["n_tris"]) * 16 if lds_scene else 0
+    if lds > K_MAX_SCENE_LDS:
+        return ("fill_refused", fill)
+    g = 2 if r["n_tris"] < GROUP4_TRIS else 4
+    trace = ("trace", (1 if lds_scene else 0, g, 1 if cnt else 0))
+    wide = bool(r["wide"]) and not lds_scene
+    if wide:
+        trace = ("wide", (1 if r["wide_qn"] else 0, 1 if cnt else 0))
+    ex = 1 if r["exit_skip"] else 0
+    tail = wide and r["wf_tail"] > 0
+    if r["wf_tail"] > 0 and not tail:
+        return ("fill_refused", fill)
+    if wide and r["wide_ovf_lanes"] < 256:
+        return ("fill_refused", fill)
+    tail_v = (1 if cnt else 0, 1 if r["wide_qn"] else 0, ex) if tail else None
+    return ("run", fill, px, 0 if wide else lds, trace, (ex,), tail_v)
+
+
+def _cross(base, **axes):
+    rows = [dict(base)]
+    for k, values in axes.items():
+        rows = [dict(r, **{k: v}) for r in rows for v in values]
+    return rows
+
+
+B = (0, 1)
+# every flag the ladder reads, sweep as 0 off / 1 a general table / 2 a hull table / 3 the cube table: 512 rows
+RENDER_CROSS = _cross(RENDER_BASE, stats=B, lds=B, cnt=B, sweep=(0, 1, 2, 3), moments=B, exit_skip=B, pack_out=B,
+                      items=B)
+SWEEP_ON = dict(RENDER_BASE, lds=1, sweep=2)
+LDS_ON = dict(RENDER_BASE, lds=1)
+RENDER_EDGES = (
+    # the sweep table's sizes, both sides of both ends; they bind only where the sweep walk runs
+    [dict(SWEEP_ON, sweep_boxes=n) for n in (0, 1, 64, 65)] + [dict(SWEEP_ON, sweep_leaves=n) for n in (0, 1, 32, 33)] +
+    [dict(SWEEP_ON, cnt=1, sweep_boxes=65), dict(SWEEP_ON, stats=1, sweep_leaves=0), dict(SWEEP_ON, lds=0, sweep_boxes=0)] +
+    # sample lanes; no batch, no tile
+    [dict(RENDER_BASE, spl=s) for s in (0, 1, 2, 3, 4, 5, 8, 16)] +
+    [dict(RENDER_BASE, n_batches=n) for n in (0, 1)] + [dict(RENDER_BASE, n_tiles=n) for n in (0, 1)] +
+    # ... where only the refusals checked before "nothing to render" still refuse
+    [dict(RENDER_BASE, n_batches=0, cnt=1, stats=1), dict(RENDER_BASE, n_batches=0, moments=1, stats=1),
+     dict(RENDER_BASE, n_batches=0, spl=3), dict(RENDER_BASE, n_batches=0, lds=1, n_tris=2000)] +
+    # 48 KB of LDS: 3072 records of 16 B fit, 3073 do not (and a sweep table's 32 leaves always fit)
+    [dict(LDS_ON, n_nodes=36, n_tris=1000), dict(LDS_ON, n_nodes=35, n_tris=1001),
+     dict(RENDER_BASE, n_nodes=35, n_tris=1001), dict(SWEEP_ON, n_nodes=35, n_tris=1001)] +
+    # a grid of 2^31 - 1 workgroups and one more: whole tiles, a compact list, a packed launch
+    [dict(RENDER_BASE, spl=1, n_tiles=0x7fffffff), dict(RENDER_BASE, spl=2, n_tiles=1 << 30),
+     dict(RENDER_BASE, items=1, n_items=0x7fffffff, n_culled=0), dict(RENDER_BASE, items=1, n_items=0x7fffffff, n_culled=1),
+     dict(RENDER_BASE, pack_out=1, n_items=0x7fffffff, n_unpack=0), dict(RENDER_BASE, pack_out=1, n_items=0x7fffffff, n_unpack=1)] +
+    # a compact launch that lists nothing launches nothing; the trailing workgroups round up
+    [dict(RENDER_BASE, items=1, n_items=0, n_culled=0), dict(RENDER_BASE, items=1, n_items=0, n_culled=32),
+     dict(RENDER_BASE, items=1, n_items=0, n_culled=33), dict(RENDER_BASE, pack_out=1, n_items=2, n_unpack=33, spl=1)]
+)
+RENDER_ROWS = RENDER_CROSS + RENDER_EDGES
+
+# every flag the ladder reads, on both sides of kWfGroup4Tris (scenes of that size never fit in LDS: those rows are
+# refused for it) and for a scene that fits
+WF_CROSS = _cross(WF_BASE, lds=B, wide=B, wide_qn=B, cnt=B, exit_skip=B, moments=B, wf_tail=(0, 1000),
+                  n_tris=(12, GROUP4_TRIS - 1, GROUP4_TRIS))
+WF_WIDE = dict(WF_BASE, wide=1, wide_qn=1, wf_tail=1000)
+WF_EDGES = (
+    [dict(WF_BASE, spl=s) for s in (0, 1, 2, 3, 4, 8, 16)] + [dict(WF_BASE, n_batches=0), dict(WF_BASE, n_batches=0, spl=3),
+     dict(WF_BASE, n_batches=0, moments=1, cnt=1), dict(WF_BASE, n_batches=0, wf_tail=5)] +
+    # no live item: the fill alone, whatever the later checks would say
+    [dict(WF_BASE, n_tiles=0), dict(WF_BASE, items=1, n_items=0), dict(WF_BASE, items=1, n_items=0, n_culled=0),
+     dict(WF_BASE, items=1, n_items=0, wf_tail=5), dict(WF_BASE, items=1, n_items=0, n_culled=33, spl=1)] +
+    # the buffers hold the launch's pixels, and at most 2^31 - 1 paths
+    [dict(WF_BASE, cap=16 * 64), dict(WF_BASE, cap=16 * 64 - 1), dict(WF_BASE, items=1, cap=3 * 64 - 1),
+     dict(WF_BASE, cap=0x7fffffff), dict(WF_BASE, cap=1 << 31)] +
+    [dict(WF_BASE, lds=1, n_nodes=36, n_tris=1000), dict(WF_BASE, lds=1, n_nodes=35, n_tris=1001),
+     dict(WF_BASE, n_nodes=35, n_tris=1001), dict(WF_WIDE, lds=1, wf_tail=0, n_nodes=35, n_tris=1001)] +
+    # the tail kernel needs the wide walk; the wide walk needs an overflow area per lane of a workgroup
+    [dict(WF_BASE, wf_tail=1), dict(WF_WIDE, wf_tail=1), dict(WF_WIDE, lds=1), dict(WF_WIDE, wide_ovf_lanes=255),
+     dict(WF_WIDE, wide_ovf_lanes=256), dict(WF_BASE, wide_ovf_lanes=0), dict(WF_WIDE, lds=1, wf_tail=0, wide_ovf_lanes=0)] +
+    [dict(WF_WIDE, items=1), dict(WF_WIDE, items=1, n_culled=0)]
+)
+WF_ROWS = WF_CROSS + WF_EDGES

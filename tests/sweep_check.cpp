@@ -59,7 +59,7 @@ std::string build(const float* V, const uint32_t* I, size_t nt, const float* N, 
   return "";
 }
 
-// The threaded walk of pt_device.hip (trace_closest / occluded) for one ray:
+// The threaded walk of csrc/kernels/walks.h (trace_closest / occluded) for one ray:
 // the slots of the leaves whose triangles it tests, in visit order.
 void threaded_leaves(const Built& b, v3 o, v3 inv, std::vector<int>* leaves) {
   const float4* nodes = (const float4*)b.collapsed.data();

@@ -1,5 +1,7 @@
 """The launch plan on the CPU: every row of tests/plan_cases.py through
-tests/plan_check.cpp, a host program around plan_launch (csrc/pt_plan.h).
+tests/plan_check.cpp, a host program around plan_launch (csrc/pt_plan.h) and
+around the kernel selection of launch_render and launch_wavefront
+(csrc/pt_device.h plan_render, plan_wavefront).
 
 The plan decides which kernel a frame runs on and with how many lanes; apart
 from this table those decisions show only on a GPU (tests/test_gpu_plan.py runs
@@ -98,3 +100,88 @@ def test_table_holds_both_sides_of_every_threshold():
     texts = {r["expect"] for r in ROWS if isinstance(r["expect"], str)}
     assert texts == {plan_cases.T_MOM_PACKED, plan_cases.T_MOM_RANKS, plan_cases.T_MOM_STATS, plan_cases.T_MOM_COUNT,
                      plan_cases.T_LDS, plan_cases.T_STATS_WF}
+
+
+# ---- kernel selection: what launch_render and launch_wavefront launch ---------------------------------------
+
+def _words(kind, r, **more):
+    return kind + " " + " ".join(f"{k}={v}" for k, v in dict(r, **more).items())
+
+
+def _variant(text):
+    return tuple(int(x) for x in text.split(","))
+
+
+@pytest.fixture(scope="module")
+def selection():
+    """plan_check's answers to every selection row, and the lists of instantiations it was built with."""
+    lines = (["lists"] + [_words("render", r, pix_per_fill=plan_cases.PIX_PER_FILL) for r in plan_cases.RENDER_ROWS] +
+             [_words("wavefront", r, pix_per_fill=plan_cases.PIX_PER_FILL, group4_tris=plan_cases.GROUP4_TRIS)
+              for r in plan_cases.WF_ROWS])
+    out = subprocess.run([_harness()], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = out.stdout.splitlines()
+    assert len(got) == len(lines)
+    n = len(plan_cases.RENDER_ROWS)
+    return dict(lists=got[0], render=got[1:1 + n], wavefront=got[1 + n:])
+
+
+def test_render_selection(selection):
+    """plan_render against launch_render's ladder, row by row; every launch runs a listed instantiation."""
+    assert len(plan_cases.RENDER_CROSS) == 512
+    reached = set()
+    for r, got in zip(plan_cases.RENDER_ROWS, selection["render"]):
+        want = plan_cases.parent_launch_render(r)
+        if isinstance(want, str):
+            assert got == want, (r, got)
+            continue
+        _, grid, lds, k = want
+        assert k in plan_cases.RENDER_VARIANTS, (r, k)
+        assert got == f"run grid={grid} lds={lds} v={','.join(map(str, k))} listed", (r, got)
+        reached.add(k)
+    assert len(plan_cases.RENDER_VARIANTS) == 17 and reached == plan_cases.RENDER_VARIANTS
+
+
+def test_wavefront_selection(selection):
+    """plan_wavefront against launch_wavefront's ladder, row by row."""
+    reached = dict(trace=set(), wide=set(), shade=set(), tail=set())
+    for r, got in zip(plan_cases.WF_ROWS, selection["wavefront"]):
+        want = plan_cases.parent_launch_wavefront(r)
+        if isinstance(want, str):
+            assert got == want, (r, got)
+            continue
+        if want[0] != "run":
+            assert got == f"{want[0]} fill={want[1]}", (r, got)
+            continue
+        _, fill, px, lds, (family, trace), shade, tail = want
+        text = f"run fill={fill} px={px} lds={lds} {family}={','.join(map(str, trace))} listed shade={shade[0]} listed"
+        if tail is not None:
+            text += f" tail={','.join(map(str, tail))} listed"
+            reached["tail"].add(tail)
+        assert got == text, (r, got)
+        reached[family].add(trace)
+        reached["shade"].add(shade)
+    # (a scene of kWfGroup4Tris triangles never fits in LDS: the ladder named wf_trace_kernel<true, 4, *>, and the
+    # lists keep them, but no launch reaches them)
+    assert reached["trace"] == {v for v in plan_cases.WF_TRACE_VARIANTS if v[:2] != (1, 4)}
+    assert reached["wide"] == plan_cases.WF_WIDE_VARIANTS
+    assert reached["shade"] == plan_cases.WF_SHADE_VARIANTS
+    assert reached["tail"] == plan_cases.WF_TAIL_VARIANTS
+
+
+def test_variant_lists_are_the_ladders(selection):
+    """The lists pt_device.hip builds its kernel tables from hold exactly the instantiations the ladders named
+    (that they hold exactly what the picks can return is pt_device.h's static_assert)."""
+    words = selection["lists"].split()
+    lists, name = {}, None
+    for w in words:
+        if "," in w or w.isdigit():
+            lists[name].append(_variant(w))
+        else:
+            name = w
+            lists[name] = []
+    want = dict(render=plan_cases.RENDER_VARIANTS, trace=plan_cases.WF_TRACE_VARIANTS, wide=plan_cases.WF_WIDE_VARIANTS,
+                shade=plan_cases.WF_SHADE_VARIANTS, tail=plan_cases.WF_TAIL_VARIANTS)
+    assert set(lists) == set(want)
+    for name, variants in want.items():
+        assert len(lists[name]) == len(variants) and set(lists[name]) == variants, name

@@ -54,7 +54,7 @@ std::string build(const float* V, size_t nvf, const uint32_t* I, size_t nt, cons
 // QUEUE: leaf hits queued (stride 64, like one lane of the kernel's LDS
 // queue) and flushed when the queue cannot take another node's four leaves
 // or the walk has no node left (PT_WIDE_FLUSH_T 1).
-// The wave-wide flush of the trace kernel (pt_device.hip wide_flush_wave),
+// The wave-wide flush of the trace kernel (csrc/kernels/wf_wide.h wide_flush_wave),
 // restated for one lane: every queued candidate is tested (here in reverse
 // queue order, as another lane of the wave could), the accepted ones reduce
 // to the lexicographic least (t, rank) -- the kernel's LDS atomic min of

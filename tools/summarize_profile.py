@@ -24,8 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOX_KERNEL = "render_kernel<false, true, false"   # ..., false>: the threaded walk; ..., true>: the sweep walk
 KERNEL_SOURCES = ("pt_device.hip", "pt_device.h", "pt_isect.h", "wide_walk.h", "pt_math.h", "scene/wide_bvh.cpp",
                   "../Makefile")   # the Makefile: the device build flags   # == bench.py
-# (bench.py's list predates csrc/sweep_walk.h, which holds the box kernel's walk: after an edit
-# to that header alone the SHA-1 still matches, so retake the box profile by hand)
+# (bench.py's list predates csrc/sweep_walk.h, which holds the box kernel's walk, and csrc/kernels/*.h, which
+# hold the kernels: after an edit to those headers alone the SHA-1 still matches, so retake the box profile by hand)
 WF_KERNELS = ("wf_gen_kernel", "wf_trace_kernel", "wf_trace_wide_kernel", "wf_trace_pairs_kernel", "wf_tail_kernel", "wf_shade_kernel",
               "wf_fold_kernel", "fill_culled_kernel")
 
