@@ -1,6 +1,6 @@
 """Regenerates tests/golden/ref_tinyobj.json: the array sizes and SHA-256
 digests of what the reference's own OBJ loader (oracle/_ref/libref_tinyobj.so,
-`make -C oracle ref`) returns for every file tests/test_ref_tinyobj.py uses.
+`make -C oracle ref`) returns for every file of tests/obj_cases.py.
 Needs that library, so it runs only where the reference tree exists; the
 tests check the recorded digests against the library whenever it is there."""
 import json
@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 for p in (os.path.join(ROOT, "discovering-path-tracer_amd"), os.path.dirname(HERE)):
     sys.path.insert(0, p)
-import test_ref_tinyobj as T  # noqa: E402
+import obj_cases as T  # noqa: E402
 
 if T.ref_lib() is None:
     raise SystemExit("the reference loader's library is absent and cannot be built here")

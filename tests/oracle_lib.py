@@ -16,6 +16,8 @@ _LIB = None
 F32P = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 U32P = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 U64P = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
+I32P = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+F64P = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 
 
 def lib():
@@ -37,7 +39,7 @@ def lib():
         L.oracle_render_ex.argtypes = L.oracle_render.argtypes + [ctypes.c_uint32]
         L.oracle_render_pixels.argtypes = [F32P, U32P, F32P, sz, F32P, F32P, sz, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
-                                           np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), sz,
+                                           I32P, sz,
                                            F32P, U64P, ctypes.c_int, ctypes.c_uint32]
         L.oracle_math.argtypes = [ctypes.c_int, F32P, F32P, sz]
         L.oracle_rng.argtypes = [ctypes.c_uint32, F32P, sz]

@@ -87,6 +87,47 @@ def flat_quad():
     return v.reshape(-1), np.array([0, 1, 2, 0, 2, 3], np.uint32)
 
 
+# three different extents, translated off the origin: no two of its six plane values coincide
+CUBOID_LO = np.float32([0.375, -1.25, 2.0])
+CUBOID_HI = np.float32([1.125, -0.75, 3.5])
+
+
+def cuboid(lo=CUBOID_LO, hi=CUBOID_HI, outward=True):
+    """(vertices, indices) of the cuboid [lo, hi]: 8 vertices, 12 triangles, their geometric normals
+    pointing out of it (or, for a view from inside, into it)."""
+    v = np.float32([[hi[0] if i & 1 else lo[0], hi[1] if i & 2 else lo[1], hi[2] if i & 4 else lo[2]] for i in range(8)])
+    quads = [(0, 2, 6, 4), (1, 5, 7, 3), (0, 4, 5, 1), (2, 3, 7, 6), (0, 1, 3, 2), (4, 6, 7, 5)]
+    idx = np.uint32([t for q in quads for t in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))])
+    if outward:
+        idx = idx[:, [0, 2, 1]]
+    return v.reshape(-1), idx.reshape(-1)
+
+
+def cuboid_inward():
+    return cuboid(outward=False)
+
+
+def open_cuboid(outward=True):
+    """The cuboid without its y hi face (triangles 6 and 7): 10 triangles, the root box still [CUBOID_LO, CUBOID_HI]."""
+    v, i = cuboid(outward=outward)
+    return v, np.delete(i.reshape(-1, 3), [6, 7], axis=0).reshape(-1)
+
+
+def cuboid_with_inner_triangle():
+    """The cuboid and one tilted triangle inside it: the triangle's box is a general one."""
+    v, i = cuboid()
+    c, e = (CUBOID_LO + CUBOID_HI) * np.float32(0.5), CUBOID_HI - CUBOID_LO
+    tri = np.float32([c + e * [-0.25, -0.125, 0.125], c + e * [0.25, -0.25, -0.125], c + e * [0.0, 0.25, 0.25]])
+    return np.concatenate([v, tri.reshape(-1)]), np.concatenate([i, np.uint32([8, 9, 10])])
+
+
+def stacked_cuboids():
+    """Two cuboids, the second on top of the first (y): no face of either spans the root box of both."""
+    v, i = cuboid()
+    up = v.reshape(-1, 3) + np.float32([0.0, CUBOID_HI[1] - CUBOID_LO[1], 0.0])
+    return np.concatenate([v, up.reshape(-1)]).astype(np.float32), np.concatenate([i, i + np.uint32(8)])
+
+
 def random_triangles(n, seed=42, spread=1.0, size=0.01):
     """SURVEY.md §8d config 5 generator: centroids ~U[-1,1]^3, vertex offsets
     ~U[-size,size]^3, unshared vertices."""
@@ -144,3 +185,20 @@ def displaced_sphere(subdiv=5, seed=3):
     r = 1.0 + 0.08 * rng.standard_normal(len(V))
     V = (V * r[:, None]).astype(np.float32)
     return V.reshape(-1), np.array(F, np.uint32).reshape(-1)
+
+
+# Scenes away from the [-1, 1]^3 most cases live in, for the wide walk.  The
+# cull bound's terms grow with |o - v0|, with the edge lengths and with the
+# largest coefficients below a node (wide_bvh.cpp: wide_tri_coeffs,
+# node_cull_consts), and the 64-byte nodes' 8-bit grid is rounded outward from
+# each node's own origin and scale.
+WIDE_HOSTILE = {
+    "cloud_far": lambda: (transformed(random_triangles(20000, seed=7)[0], 1.0, (1000, -500, 2000)),
+                          random_triangles(20000, seed=7)[1]),
+    "sphere_at_300": lambda: (transformed(displaced_sphere(3)[0], 1.0, (300, 300, -300)), displaced_sphere(3)[1]),
+    "sphere_x50": lambda: (transformed(displaced_sphere(3)[0], 50.0, (0, 0, 0)), displaced_sphere(3)[1]),
+    "sphere_x0.05": lambda: (transformed(displaced_sphere(3)[0], 0.05, (0, 0, 0)), displaced_sphere(3)[1]),
+    "floor_and_cloud": floor_and_cloud,
+    "coincident_x6": lambda: coincident_copies(*displaced_sphere(2), 6),
+    "degenerates": lambda: with_degenerates(*random_triangles(3000, seed=8, spread=0.5, size=0.02)),
+}

@@ -22,28 +22,20 @@ import subprocess
 import numpy as np
 import pytest
 
+import native
 import oracle_lib
 import ptamd
 import scenes
-import test_cull
-from test_cull import CASES
+from cull_support import CASE_IDS, CASES, culled_mask, light_hit, margin_mask, rays, rng_draws, skip_counts, slab_hit
+from support import box_mesh, oracle_built
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "discovering-path-tracer_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "_build")
 R_TIGHT = 4.25
 U0_BITS = 0x38FAD897   # kCullTightU0 = 0x1.f5b12ep-14f
 
 
 def _harness():
-    src = os.path.join(ROOT, "tests", "cull_radius_check.cpp")
-    exe = os.path.join(BUILD, "cull_radius_check")
-    deps = [src, os.path.join(CSRC, "pt_cull.h"), os.path.join(CSRC, "pt_math.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        os.makedirs(BUILD, exist_ok=True)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", CSRC, "-o", exe, src, "-lpthread"])
-    return exe
+    return native.build("cull_radius_check", [os.path.join(native.TESTS, "cull_radius_check.cpp")],
+                        ["-O2"] + native.COMMON + ["-I", native.CSRC], libs=["-lpthread"])
 
 
 def test_radius_guarantee_over_every_float():
@@ -74,7 +66,7 @@ def _sets(cam, W, H, lights):
     return loose, tight, zero, np.float32(u0)
 
 
-@pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=[c[0] for c in CASES])
+@pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=CASE_IDS)
 def test_tight_rectangles_nest(name, cam, W, H, lights):
     """Per object: the R = 0 rectangle inside the tight one inside the loose
     one; the default bound of the new entry point is the loose derivation's."""
@@ -91,25 +83,6 @@ def test_tight_rectangles_nest(name, cam, W, H, lights):
         ptamd.primary_cull_rects_r(cam, W, H, lo, hi, lights, 13.5)
 
 
-def _margin(loose, tight, W, H):
-    """Pixels inside a loose rectangle but outside every tight one."""
-    return ~test_cull._culled_mask(loose, W, H) & test_cull._culled_mask(tight, W, H)
-
-
-def rng_draws(seeds, n):
-    """The shader's RNG (raytrace_comp.comp:207-216) in numpy: the first n
-    draws of every seed, (len(seeds), n) float32."""
-    s = np.asarray(seeds, np.uint64) & np.uint64(0xFFFFFFFF)
-    m32 = np.uint64(0xFFFFFFFF)
-    out = np.empty((s.size, n), np.float32)
-    for k in range(n):
-        s = (s * np.uint64(747796405) + np.uint64(2891336453)) & m32
-        r = (((s >> ((s >> np.uint64(28)) + np.uint64(4))) ^ s) * np.uint64(277803737)) & m32
-        r = (r >> np.uint64(22)) ^ r
-        out[:, k] = r.astype(np.uint32).astype(np.float32) / np.float32(4294967296.0)
-    return out
-
-
 def test_rng_restatement_equals_the_oracle():
     rnd = np.random.default_rng(5)
     seeds = np.concatenate([np.arange(0, 64), 2 ** 32 - 1 - np.arange(0, 64), 2 ** 31 + np.arange(-32, 32),
@@ -118,30 +91,6 @@ def test_rng_restatement_equals_the_oracle():
     want = np.stack([oracle_lib.rng(int(s), 4) for s in seeds])
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert len(np.unique(got)) > 0.99 * got.size
-
-
-def skip_counts(cam, W, H, lights, first_batch, n_batches, lo=(-1, -1, -1), hi=(1, 1, 1)):
-    """What include/pathtracer.h defines for PT_OPT_CULL_TIGHT, counted on the
-    host: (live pixels, margin samples the kernel must skip, margin samples it
-    must trace) over the batches.  A margin pixel lies inside a loose
-    rectangle and outside every tight one; its sample of a batch is skipped
-    when draws 0 and 2 of seed (batch * H + y) * W + x, after fmax(1e-38, .),
-    are both at least u0."""
-    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
-    loose = ptamd.primary_cull_rects(cam, W, H, lo, hi, lights)
-    tight, u0 = ptamd.primary_cull_rects_r(cam, W, H, lo, hi, lights)
-    assert loose is not None and tight is not None and len(loose) == len(tight)
-    u0 = np.float32(u0)
-    live = ~test_cull._culled_mask(loose, W, H)
-    ys, xs = np.nonzero(_margin(loose, tight, W, H))
-    skipped = traced = 0
-    for batch in range(first_batch, first_batch + n_batches):
-        seeds = (np.uint64(batch) * np.uint64(H) + ys.astype(np.uint64)) * np.uint64(W) + xs.astype(np.uint64)
-        u = np.maximum(np.float32(1e-38), rng_draws(seeds, 3))
-        skip = (u[:, 0] >= u0) & (u[:, 2] >= u0)
-        skipped += int(skip.sum())
-        traced += int((~skip).sum())
-    return int(live.sum()), skipped, traced
 
 
 def test_skip_counts_of_the_gpu_test_frame():
@@ -154,14 +103,14 @@ def test_skip_counts_of_the_gpu_test_frame():
     assert skipped + traced == 5369 * 600 and traced == 767
 
 
-@pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=[c[0] for c in CASES])
+@pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=CASE_IDS)
 def test_margin_pixels_reach_nothing_with_radii_at_the_bound(name, cam, W, H, lights):
     """Aperture and jitter radii both at the bound, both angles scanned (the
     worst angle of each lies within half a step of a scanned one; the margin
     the rectangles keep, a pixel and more, is far above what half a step of
     1/32 turn moves a ray), plus random radii below the bound."""
     loose, tight, _, _ = _sets(cam, W, H, lights)
-    margin = _margin(loose, tight, W, H)
+    margin = margin_mask(loose, tight, W, H)
     assert margin.any(), "pixels between the two sets"
     lo, hi = np.full(3, -1.0), np.full(3, 1.0)
     L = np.asarray(lights, np.float32).reshape(-1, 16)
@@ -175,21 +124,19 @@ def test_margin_pixels_reach_nothing_with_radii_at_the_bound(name, cam, W, H, li
         probes += [(rnd.uniform(0, R_TIGHT), rnd.uniform(0, 2 * np.pi), rnd.uniform(0, R_TIGHT), rnd.uniform(0, 2 * np.pi))
                    for _ in range(32)]
         for ra, ta, rj, tj in probes:
-            o, d = test_cull._rays(cam, W, H, px, py, 0.02 * ra * np.cos(ta), 0.02 * ra * np.sin(ta), rj * np.cos(tj),
+            o, d = rays(cam, W, H, px, py, 0.02 * ra * np.cos(ta), 0.02 * ra * np.sin(ta), rj * np.cos(tj),
                                    rj * np.sin(tj))
-            assert not test_cull._slab_hit(o, d, lo, hi), (name, px, py, ra, ta, rj, tj)
+            assert not slab_hit(o, d, lo, hi), (name, px, py, ra, ta, rj, tj)
             for li in L:
-                assert not test_cull._light_hit(o, d, li), (name, px, py, ra, ta, rj, tj)
+                assert not light_hit(o, d, li), (name, px, py, ra, ta, rj, tj)
 
 
 @pytest.fixture(scope="module")
 def box():
-    v, i, _ = oracle_lib.obj_parse(open(scenes.BOX_OBJ, "rb").read())
-    ri, nodes = oracle_lib.bvh_build(v, i)
-    return v, ri, nodes
+    return oracle_built(*box_mesh())
 
 
-@pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=[c[0] for c in CASES])
+@pytest.mark.parametrize("name,cam,W,H,lights", CASES, ids=CASE_IDS)
 def test_oracle_samples_the_kernel_skips_are_black(box, name, cam, W, H, lights):
     """The samples render_kernel skips -- margin pixels, real seeds whose two
     radius draws are at least kCullTightU0 -- rendered one batch at a time by
@@ -201,7 +148,7 @@ def test_oracle_samples_the_kernel_skips_are_black(box, name, cam, W, H, lights)
     loose = ptamd.primary_cull_rects(cam, W, H, lo, hi, lights)
     tight, u0 = ptamd.primary_cull_rects_r(cam, W, H, lo, hi, lights)
     u0 = np.float32(u0)
-    margin = _margin(loose, tight, W, H)
+    margin = margin_mask(loose, tight, W, H)
     ys, xs = np.nonzero(margin)
     assert len(xs) > 0
     skipped = 0
@@ -228,8 +175,8 @@ def test_blocks_in_the_margin(W, H, n_live, n_margin):
     lo, hi = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
     loose = ptamd.primary_cull_rects(scenes.DEFAULT_CAMERA, W, H, lo, hi, scenes.REFERENCE_LIGHT)
     tight, _ = ptamd.primary_cull_rects_r(scenes.DEFAULT_CAMERA, W, H, lo, hi, scenes.REFERENCE_LIGHT)
-    live = ~test_cull._culled_mask(loose, W, H)
-    inner = ~test_cull._culled_mask(tight, W, H)
+    live = ~culled_mask(loose, W, H)
+    inner = ~culled_mask(tight, W, H)
     by = -(-H // 4)
     pad = np.zeros((by * 4, W), bool)
     blocks = lambda m: np.where(np.arange(by * 4)[:, None] < H, np.vstack([m, pad[H:]]), False).reshape(by, 4, W // 16, 16)

@@ -10,12 +10,9 @@ import pytest
 import denoise_ref as R
 import ptamd
 import scenes
+from support import bits, same
 
 PT_ERR_INVALID = -1
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("cam", [scenes.DEFAULT_CAMERA, scenes.camera((3, 2, 4))], ids=["default", "from_3_2_4"])
@@ -26,10 +23,9 @@ def test_guide_ray_matches_restatement(cam):
     for y in range(H):
         for x in range(W):
             o, d = ptamd.guide_ray(cam, W, H, x, y)
-            assert np.array_equal(_bits(o), _bits(o_ref))
+            assert np.array_equal(bits(o), bits(o_ref))
             got[y, x] = d
-    bad = np.argwhere(_bits(got) != _bits(d_ref))
-    assert bad.size == 0, f"{len(bad)} direction components differ, first at (y, x, c) = {bad[0]}"
+    same(got, d_ref, "against the restatement")
     if cam is scenes.DEFAULT_CAMERA:   # the column the wide walk hands to the exact walk
         assert np.all(got[:, W // 2, 0] == 0.0)
 
@@ -50,11 +46,10 @@ def test_host_filter_matches_restatement(W, H, iterations):
     got = ptamd.denoise_host(rgba, guide, W, H, params)
     ref = R.atrous(rgba, guide, W, H, params)
     assert np.all(np.isfinite(got))
-    bad = np.argwhere(_bits(got) != _bits(ref))
-    assert bad.size == 0, f"{len(bad)} of {got.size} floats differ, first at (y, x, c) = {bad[0]}"
-    assert np.array_equal(_bits(got[..., 3]), _bits(rgba[..., 3]))   # alpha passes through
+    same(got, ref, "against the restatement")
+    assert np.array_equal(bits(got[..., 3]), bits(rgba[..., 3]))   # alpha passes through
     if (W, H) == (1, 1):
-        assert np.array_equal(_bits(got), _bits(rgba))               # the centre tap alone
+        assert np.array_equal(bits(got), bits(rgba))               # the centre tap alone
 
 
 def test_host_filter_default_params():
@@ -62,8 +57,8 @@ def test_host_filter_default_params():
     assert (p.iterations, p.sigma_color, p.sigma_normal, p.sigma_depth) == tuple(
         [R.DEFAULTS[0]] + [float(np.float32(v)) for v in R.DEFAULTS[1:]])
     rgba, guide = R.make_images(20, 12, seed=7)
-    assert np.array_equal(_bits(ptamd.denoise_host(rgba, guide, 20, 12)),
-                          _bits(ptamd.denoise_host(rgba, guide, 20, 12, R.DEFAULTS)))
+    assert np.array_equal(bits(ptamd.denoise_host(rgba, guide, 20, 12)),
+                          bits(ptamd.denoise_host(rgba, guide, 20, 12, R.DEFAULTS)))
 
 
 def test_host_filter_edges_do_not_mix():

@@ -3,18 +3,17 @@
 independent numpy-float32 restatement of tests/denoise_var_ref.py, bit for
 bit, the argument checks, and the zero-variance limit."""
 import ctypes
+import subprocess
 
 import numpy as np
 import pytest
 
 import denoise_var_ref as R
+import native
 import ptamd
+from support import bits, same
 
 PT_OK, PT_ERR_INVALID = 0, -1
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_symbols_and_defaults():
@@ -44,21 +43,20 @@ def test_host_filter_matches_restatement(W, H, iterations):
     got = ptamd.denoise_var_host(rgba, moments, n, guide, W, H, params)
     ref = R.atrous_var(rgba, moments, n, guide, W, H, params)
     assert np.all(np.isfinite(got))
-    bad = np.argwhere(_bits(got) != _bits(ref))
-    assert bad.size == 0, f"{len(bad)} of {got.size} floats differ, first at (y, x, c) = {bad[0]}"
-    assert np.array_equal(_bits(got[..., 3]), _bits(rgba[..., 3]))           # alpha passes through
-    assert not np.array_equal(_bits(got[..., :3]), _bits(rgba[..., :3]))     # ... and the filter filters
+    same(got, ref, "against the restatement")
+    assert np.array_equal(bits(got[..., 3]), bits(rgba[..., 3]))           # alpha passes through
+    assert not np.array_equal(bits(got[..., :3]), bits(rgba[..., :3]))     # ... and the filter filters
 
 
 def test_host_filter_default_params_and_sample_count():
     W, H = 37, 23
     rgba, moments, guide = R.make_images(W, H, seed=7)
     got = ptamd.denoise_var_host(rgba, moments, 8, guide, W, H, None)
-    assert np.array_equal(_bits(got), _bits(R.atrous_var(rgba, moments, 8, guide, W, H, R.DEFAULTS)))
+    assert np.array_equal(bits(got), bits(R.atrous_var(rgba, moments, 8, guide, W, H, R.DEFAULTS)))
     # the sample count scales the variance of the mean: another n, another image
     other = ptamd.denoise_var_host(rgba, moments, 32, guide, W, H, None)
-    assert np.array_equal(_bits(other), _bits(R.atrous_var(rgba, moments, 32, guide, W, H, R.DEFAULTS)))
-    assert not np.array_equal(_bits(other), _bits(got))
+    assert np.array_equal(bits(other), bits(R.atrous_var(rgba, moments, 32, guide, W, H, R.DEFAULTS)))
+    assert not np.array_equal(bits(other), bits(got))
 
 
 def test_host_filter_rejects_bad_arguments():
@@ -115,8 +113,8 @@ def test_zero_variance_frame_comes_back_unchanged(iterations):
     want = rgba.copy()
     for _ in range(iterations):
         want[..., :3] = (h * want[..., :3]) / h
-    assert np.array_equal(_bits(got), _bits(want))
-    ulps = np.abs(_bits(got[..., :3]).astype(np.int64) - _bits(rgba[..., :3]).astype(np.int64))
+    assert np.array_equal(bits(got), bits(want))
+    ulps = np.abs(bits(got[..., :3]).astype(np.int64) - bits(rgba[..., :3]).astype(np.int64))
     assert int(ulps.max()) <= iterations and np.count_nonzero(ulps) < 0.2 * ulps.size
     # ... and a flat zero-variance frame (every neighbour alike) stays finite too
     flat_rgba = np.full((H, W, 4), 0.5, np.float32)
@@ -129,15 +127,7 @@ def test_zero_variance_frame_comes_back_unchanged(iterations):
 def test_stand_alone_check_program(tmp_path):
     """tests/denoise_var_check.cpp (the program sanitizer runs use), built
     plainly against the library and run."""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.dirname(os.path.abspath(ptamd.__file__))
-    exe = str(tmp_path / "denoise_var_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(root, "include"), "-I", os.path.join(pkg, "csrc"),
-                           os.path.join(root, "tests", "denoise_var_check.cpp"), "-L", pkg, "-lptamd",
-                           "-Wl,-rpath," + pkg, "-o", exe])
+    exe = native.against_library("denoise_var_check", tmp_path)
     res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert res.stdout.startswith("ok:")

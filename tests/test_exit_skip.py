@@ -20,28 +20,18 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "discovering-path-tracer_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "exit_skip_check.cpp")
-BUILD = os.path.join(ROOT, "tests", "_build")
-EXE = os.path.join(BUILD, "exit_skip_check")
-FLAGS = ["-std=c++17", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-I", CSRC]
+import native
+
 _OUT = None
-
-
-def _stale(out, deps):
-    return not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
 def output():
     """The program's three lines as {name: {key: value}}, run once."""
     global _OUT
     if _OUT is None:
-        deps = [SRC, os.path.join(CSRC, "pt_isect.h"), os.path.join(CSRC, "pt_math.h")]
-        if _stale(EXE, deps):
-            os.makedirs(BUILD, exist_ok=True)
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2"] + FLAGS + ["-o", EXE, SRC])
-        run = subprocess.run([EXE], capture_output=True, text=True, timeout=900)
+        exe = native.build("exit_skip_check", [os.path.join(native.TESTS, "exit_skip_check.cpp")],
+                           ["-O2"] + native.COMMON + ["-pthread", "-I", native.CSRC])
+        run = subprocess.run([exe], capture_output=True, text=True, timeout=900)
         lines = {}
         for line in run.stdout.strip().splitlines():
             name, *kv = line.split()

@@ -6,7 +6,7 @@ samples the kernel must trace are black in the oracle too).
 
 The frame is the box at 320x180, 4 spp: 98 of its 326 live 16x4 pixel blocks
 lie wholly between the loose and the tight rectangles
-(test_cull_tight.test_blocks_in_the_margin), so whole waves take the skip,
+(test_cull_tight.py, test_blocks_in_the_margin), so whole waves take the skip,
 others take it lane by lane.
 """
 import functools
@@ -14,11 +14,10 @@ import functools
 import numpy as np
 import pytest
 
-import oracle_lib as O
 import ptamd
 import scenes
-from test_cull_tight import skip_counts
-from test_gpu_sweep import _same
+from cull_support import skip_counts
+from support import oracle_frame, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,32 +25,15 @@ W, H, DEPTH, SSS = 320, 180, 4, 3
 
 
 @functools.lru_cache(maxsize=None)
-def _box():
-    v, i, n, _, _ = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh().arrays()
-    return v, i, n
-
-
-@functools.lru_cache(maxsize=None)
 def _oracle(first, nb, nranks=1, rank=0):
-    v, i, n = _box()
-    ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, first_batch=0,
-                      n_batches=first + nb, max_depth=DEPTH, sss_bounces=SSS, nranks=nranks, rank=rank)
-    ref.setflags(write=False)
-    return ref
+    return oracle_frame(scene("box"), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, 0, first + nb, DEPTH, SSS,
+                        nranks=nranks, rank=rank)
 
 
 def _renderer(tight, lanes=1, cam=scenes.DEFAULT_CAMERA, count=False):
-    v, i, n = _box()
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_CULL_TIGHT, tight)
-    r.set_option(ptamd.PT_OPT_SAMPLE_LANES, lanes)
-    if count:
-        r.set_option(ptamd.PT_OPT_COUNT_TRACED, 1)
-    r.upload_scene(v, i, n)
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(cam)
-    r.set_params(DEPTH, SSS)
-    return r
+    return renderer(scene("box"), cam, depth=DEPTH, sss=SSS,
+                    options=[(ptamd.PT_OPT_CULL_TIGHT, tight), (ptamd.PT_OPT_SAMPLE_LANES, lanes)] +
+                    ([(ptamd.PT_OPT_COUNT_TRACED, 1)] if count else []))
 
 
 @pytest.mark.parametrize("lanes", [1, 2, 4])
@@ -73,10 +55,10 @@ def test_skip_on_and_off_equal_the_oracle(lanes):
         r.close()
         frames[tight] = (a, b, c)
     for k, what in enumerate(("batches 0-3", "batches 4-7 on top", "batches 0-3 over a stale frame")):
-        _same(frames[0][k], frames[1][k], f"lanes={lanes} {what}: PT_OPT_CULL_TIGHT 0 against 1")
-    _same(frames[1][0], _oracle(0, 4), f"lanes={lanes} batches 0-3 against the oracle")
-    _same(frames[1][1], _oracle(4, 4), f"lanes={lanes} batches 0-7 against the oracle")
-    _same(frames[1][2], _oracle(0, 4), f"lanes={lanes} fresh restart against the oracle")
+        same(frames[0][k], frames[1][k], f"lanes={lanes} {what}: PT_OPT_CULL_TIGHT 0 against 1")
+    same(frames[1][0], _oracle(0, 4), f"lanes={lanes} batches 0-3 against the oracle")
+    same(frames[1][1], _oracle(4, 4), f"lanes={lanes} batches 0-7 against the oracle")
+    same(frames[1][2], _oracle(0, 4), f"lanes={lanes} fresh restart against the oracle")
 
 
 @pytest.mark.parametrize("rank", [0, 1])
@@ -89,11 +71,11 @@ def test_two_rank_share(rank):
         r.render(0, 4)
         frames[tight] = r.read_accum()
         r.close()
-    _same(frames[0], frames[1], f"rank {rank} of 2: PT_OPT_CULL_TIGHT 0 against 1")
+    same(frames[0], frames[1], f"rank {rank} of 2: PT_OPT_CULL_TIGHT 0 against 1")
     ref = _oracle(0, 4, 2, rank).reshape(-1, 4)
     own = ref[:, 3] != 0   # the oracle leaves the other rank's pixels untouched (0)
     assert own.any() and not own.all()
-    _same(frames[1].reshape(-1, 4)[own], ref[own], f"rank {rank} of 2 against the oracle")
+    same(frames[1].reshape(-1, 4)[own], ref[own], f"rank {rank} of 2 against the oracle")
 
 
 @pytest.mark.parametrize("kernel", [ptamd.KERNEL_RECURSIVE, ptamd.KERNEL_WAVEFRONT])
@@ -109,8 +91,8 @@ def test_counting_mode_shows_skipped_primaries(kernel):
         counts[tight] = r.traced()
         assert r.last_kernel() == kernel
         r.close()
-    _same(frames[0], frames[1], "counting mode: PT_OPT_CULL_TIGHT 0 against 1")
-    _same(frames[1], _oracle(0, 4), "counting mode against the oracle")
+    same(frames[0], frames[1], "counting mode: PT_OPT_CULL_TIGHT 0 against 1")
+    same(frames[1], _oracle(0, 4), "counting mode against the oracle")
     print(f"kernel {kernel}: primaries on {counts[1]['primaries']}, off {counts[0]['primaries']}")
     assert 0 < counts[1]["primaries"] < counts[0]["primaries"] <= W * H * 4
     assert counts[1]["closest_walks"] < counts[0]["closest_walks"]
@@ -125,7 +107,7 @@ def test_skip_counts_are_exact(kernel, lanes):
     skipped every margin sample would render the same frame.  The counters
     can: with the option off every sample of a live pixel generates its
     primary ray, with it on exactly the margin samples whose two radius draws
-    are at least u0 do not (test_cull_tight.skip_counts, from the header's
+    are at least u0 do not (cull_support.skip_counts, from the header's
     definition).  At 4 lanes the samples of one pixel sit in neighbouring
     lanes."""
     nb = 8
@@ -144,8 +126,8 @@ def test_skip_counts_are_exact(kernel, lanes):
         r.close()
     print(f"kernel {kernel} lanes {lanes}: primaries on {counts[1]['primaries']}, off {counts[0]['primaries']}; "
           f"expected off {live * nb}, skipped {skipped}, margin samples traced {traced}")
-    _same(frames[0], frames[1], "counting mode: PT_OPT_CULL_TIGHT 0 against 1")
-    _same(frames[1], _oracle(4, 4), "counting mode against the oracle")
+    same(frames[0], frames[1], "counting mode: PT_OPT_CULL_TIGHT 0 against 1")
+    same(frames[1], _oracle(4, 4), "counting mode against the oracle")
     assert counts[0]["primaries"] == live * nb
     assert counts[0]["primaries"] - counts[1]["primaries"] == skipped
     assert 0 < counts[1]["primaries"] < counts[0]["primaries"] <= W * H * nb
@@ -168,7 +150,7 @@ def test_no_guarantee_no_skip():
         frames[tight] = r.read_accum()
         assert r.traced()["primaries"] == W * H * 2
         r.close()
-    _same(frames[0], frames[1], "camera inside the box: PT_OPT_CULL_TIGHT 0 against 1")
+    same(frames[0], frames[1], "camera inside the box: PT_OPT_CULL_TIGHT 0 against 1")
 
 
 def test_option_range():

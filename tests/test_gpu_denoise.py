@@ -16,29 +16,22 @@ import denoise_ref as R
 import oracle_lib as O
 import ptamd
 import scenes
+from support import PKG, bits, built, mse, read_pfm, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
-PKG = os.path.dirname(os.path.abspath(ptamd.__file__))
 PT_ERR_INVALID, PT_ERR_UNSUPPORTED = -1, -5
 MISS = np.array([0.0, 0.0, 0.0, 1e30], np.float32)
 CAM_324 = scenes.camera((3, 2, 4))
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
 def box():
-    v, i, n, _, _ = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh().arrays()
-    return v, i, n
+    return scene("box")
 
 
 def _sphere(subdiv):
-    v, i = scenes.displaced_sphere(subdiv=subdiv)
-    v, i, n, _, _ = ptamd.Scene.from_arrays(v, i).build_bvh().arrays()
-    return v, i, n
+    return built(*scenes.displaced_sphere(subdiv=subdiv))
 
 
 @pytest.fixture(scope="module")
@@ -46,19 +39,13 @@ def sphere3():
     return _sphere(3)
 
 
-def _renderer(scene, cam, W, H):
-    r = ptamd.Renderer(0)
-    r.upload_scene(*scene)
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(cam)
-    r.set_params(4, 3)
-    r.resize_and_clear(W, H)
-    return r
+def _renderer(mesh, cam, W, H):
+    return renderer(mesh, cam, size=(W, H))
 
 
-def _oracle_guide(scene, cam, W, H):
+def _oracle_guide(mesh, cam, W, H):
     """The guide the header defines, from oracle_lib.trace of pt_guide_ray."""
-    v, i, n = scene
+    v, i, n = mesh
     out = np.zeros((H, W, 4), np.float32)
     for y in range(H):
         for x in range(W):
@@ -78,11 +65,6 @@ def sphere_guide(sphere3):
     return _oracle_guide(sphere3, CAM_324, 67, 45)
 
 
-def _assert_same(got, want, what):
-    bad = np.argwhere(_bits(got) != _bits(want))
-    assert bad.size == 0, f"{what}: {len(bad)} of {got.size} floats differ, first at (y, x, c) = {bad[0]}"
-
-
 def test_guide_box_matches_oracle(box, box_guide):
     W, H = 64, 48
     r = _renderer(box, scenes.DEFAULT_CAMERA, W, H)
@@ -92,7 +74,7 @@ def test_guide_box_matches_oracle(box, box_guide):
     assert ptamd.guide_ray(scenes.DEFAULT_CAMERA, W, H, W // 2, 7)[1][0] == 0.0
     hits = int(np.count_nonzero(got[..., 3] < 1e30))
     assert 0 < hits < W * H and np.any(got[:, W // 2, 3] < 1e30)
-    _assert_same(got, box_guide, "box guide")
+    same(got, box_guide, "box guide")
 
 
 def test_guide_sphere_matches_oracle(sphere3, sphere_guide):
@@ -102,7 +84,7 @@ def test_guide_sphere_matches_oracle(sphere3, sphere_guide):
     got = r.read_guide()
     hits = int(np.count_nonzero(got[..., 3] < 1e30))
     assert 0 < hits < W * H
-    _assert_same(got, sphere_guide, "sphere guide")
+    same(got, sphere_guide, "sphere guide")
 
 
 def test_guide_walk_parity_wide_tree(sphere3, sphere_guide):
@@ -112,7 +94,7 @@ def test_guide_walk_parity_wide_tree(sphere3, sphere_guide):
     for key, value in [(ptamd.PT_OPT_WIDE, 1), (ptamd.PT_OPT_WIDE_NODE, 128), (ptamd.PT_OPT_WIDE, 0)]:
         r.set_option(key, value)
         r.render_guide()
-        _assert_same(r.read_guide(), sphere_guide, f"option {key} = {value}")
+        same(r.read_guide(), sphere_guide, f"option {key} = {value}")
 
 
 def test_guide_walk_parity_box(box, box_guide):
@@ -124,7 +106,7 @@ def test_guide_walk_parity_box(box, box_guide):
         for key, value in opts.items():
             r.set_option(key, value)
         r.render_guide()
-        _assert_same(r.read_guide(), box_guide, f"options {opts}")
+        same(r.read_guide(), box_guide, f"options {opts}")
 
 
 @pytest.mark.parametrize("W,H", [(67, 45), (20, 12)])
@@ -137,11 +119,11 @@ def test_device_filter_matches_host_and_restatement(box, W, H):
     for iterations in (1, 5, 6):
         params = (iterations, 0.6, 0.35, 0.25)
         ref = R.atrous(accum, guide, W, H, params)
-        _assert_same(ptamd.denoise_host(accum, guide, W, H, params), ref, f"host, {iterations} passes")
+        same(ptamd.denoise_host(accum, guide, W, H, params), ref, f"host, {iterations} passes")
         for staged in (0, 1):
             r.set_option(ptamd.PT_OPT_DENOISE_LDS, staged)
-            _assert_same(r.denoise(params), ref, f"device, {iterations} passes, staged {staged}")
-    _assert_same(r.read_accum().reshape(H, W, 4), accum, "the accumulation image after the filter")
+            same(r.denoise(params), ref, f"device, {iterations} passes, staged {staged}")
+    same(r.read_accum().reshape(H, W, 4), accum, "the accumulation image after the filter")
 
 
 def test_device_filter_caller_images(box):
@@ -157,9 +139,9 @@ def test_device_filter_caller_images(box):
     assert r.denoise(params, src.data_ptr(), dst.data_ptr()) is None
     r.synchronize()
     guide = r.read_guide()                         # pt_denoise rendered it
-    _assert_same(dst.cpu().numpy(), R.atrous(rgba, guide, W, H, params), "caller-owned destination")
-    _assert_same(src.cpu().numpy(), rgba, "caller-owned source")
-    _assert_same(r.read_accum().reshape(H, W, 4), accum, "the accumulation image")
+    same(dst.cpu().numpy(), R.atrous(rgba, guide, W, H, params), "caller-owned destination")
+    same(src.cpu().numpy(), rgba, "caller-owned source")
+    same(r.read_accum().reshape(H, W, 4), accum, "the accumulation image")
     L = ptamd.lib()
     assert L.pt_denoise(r._c, None, src.data_ptr(), src.data_ptr()) == PT_ERR_INVALID      # in place
     assert L.pt_denoise(r._c, None, src.data_ptr() + 4, dst.data_ptr()) == PT_ERR_INVALID  # misaligned
@@ -183,9 +165,9 @@ def test_guide_staleness(box, sphere3):
     fresh = _renderer(box, CAM_324, W, H)          # the new camera's guide from a context of its own
     fresh.render_guide()
     new_guide = fresh.read_guide()
-    assert not np.array_equal(_bits(new_guide), _bits(old_guide))
-    _assert_same(second, R.atrous(r.read_accum(), new_guide, W, H, params), "after the camera moved")
-    assert not np.array_equal(_bits(first), _bits(second))
+    assert not np.array_equal(bits(new_guide), bits(old_guide))
+    same(second, R.atrous(r.read_accum(), new_guide, W, H, params), "after the camera moved")
+    assert not np.array_equal(bits(first), bits(second))
     # the other inputs the guide depends on
     assert r.guide_ptr()
     assert r.progressive_camera(scenes.DEFAULT_CAMERA) and not r.guide_ptr()
@@ -217,25 +199,20 @@ def test_calls_without_inputs_are_invalid(box):
     assert r.denoise().shape == (4, 4, 4)
 
 
-def _mse(a, b):
-    d = a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)
-    return float(np.mean(d * d))
-
-
 @pytest.mark.parametrize("name", ["box", "sphere"])
 def test_it_denoises(box, name):
     """8 spp filtered with the default parameters is closer to 256 spp than
     8 spp is.  The printed errors are the ones include/pathtracer.h quotes."""
     W = H = 256
-    scene, cam = (box, scenes.DEFAULT_CAMERA) if name == "box" else (_sphere(4), CAM_324)
-    r = _renderer(scene, cam, W, H)
+    mesh, cam = (box, scenes.DEFAULT_CAMERA) if name == "box" else (_sphere(4), CAM_324)
+    r = _renderer(mesh, cam, W, H)
     r.render(0, 8)
     raw = r.read_accum().reshape(H, W, 4)
     den = r.denoise()
     r.clear()
     r.render(0, 256)
     ref = r.read_accum().reshape(H, W, 4)
-    e_raw, e_den = _mse(raw, ref), _mse(den, ref)
+    e_raw, e_den = mse(raw, ref), mse(den, ref)
     print(f"denoise {name} 256x256: mse(8 spp) = {e_raw:.4e}, mse(8 spp denoised) = {e_den:.4e}")
     assert np.all(np.isfinite(den))
     assert e_den < e_raw
@@ -252,14 +229,6 @@ def test_multi_device_context_is_unsupported():
     assert not L.pt_guide_device_ptr(g._c)
 
 
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = map(int, f.readline().split())
-        assert float(f.readline()) < 0   # little-endian
-        return np.fromfile(f, "<f4").reshape(h, w, 3)
-
-
 def test_pt_render_denoise_and_guide_flags(box, box_guide, tmp_path):
     W, H, spp = 64, 48, 2
     exe = os.path.join(PKG, "pt_render")
@@ -269,5 +238,5 @@ def test_pt_render_denoise_and_guide_flags(box, box_guide, tmp_path):
     assert res.returncode == 0, res.stderr[-3000:]
     r = _renderer(box, scenes.DEFAULT_CAMERA, W, H)
     r.render(0, spp)
-    _assert_same(_read_pfm(out), r.denoise()[..., :3], "pt_render -denoise")
-    _assert_same(_read_pfm(gpath), box_guide[..., :3], "pt_render -guide")
+    same(read_pfm(out), r.denoise()[..., :3], "pt_render -denoise")
+    same(read_pfm(gpath), box_guide[..., :3], "pt_render -guide")

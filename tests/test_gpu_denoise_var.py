@@ -15,45 +15,18 @@ import torch
 import denoise_var_ref as R
 import ptamd
 import scenes
+from support import PKG, bits, mse, read_pfm, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
-PKG = os.path.dirname(os.path.abspath(ptamd.__file__))
 PT_OK, PT_ERR_INVALID = 0, -1
 CAM_324 = scenes.camera((3, 2, 4))
 FRAMES = {"box": (scenes.DEFAULT_CAMERA, 64, 48), "sphere": (CAM_324, 67, 45)}   # edge tiles in both directions
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = np.argwhere(_bits(got) != _bits(want))
-    assert bad.size == 0, f"{what}: {len(bad)} of {np.size(got)} floats differ, first at (y, x, c) = {bad[0]}"
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        s = ptamd.Scene.from_arrays(*scenes.displaced_sphere(subdiv=3)).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
-
-
 def _renderer(name, W=None, H=None, moments=1):
     cam, w, h = FRAMES[name]
-    W, H = W or w, H or h
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_MOMENTS, moments)
-    r.upload_scene(*_scene(name))
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(cam)
-    r.set_params(4, 3)
-    r.resize_and_clear(W, H)
-    return r
+    return renderer(scene(name), cam, size=(W or w, H or h), options=[(ptamd.PT_OPT_MOMENTS, moments)])
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -70,13 +43,13 @@ def test_device_filter_matches_host_and_restatement(name):
     for params in (None, (1, 1.5, 0.35, 0.25), (3, 0.75, 0.5, 0.25), (6, 4.0, 0.35, 0.5)):
         ref = R.atrous_var(accum, moments, n, guide, W, H, R.DEFAULTS if params is None else params)
         assert np.all(np.isfinite(ref))
-        _same(ptamd.denoise_var_host(accum, moments, n, guide, W, H, params), ref, f"{name}: host, {params}")
+        same(ptamd.denoise_var_host(accum, moments, n, guide, W, H, params), ref, f"{name}: host, {params}")
         for staged in (0, 1):
             r.set_option(ptamd.PT_OPT_DENOISE_LDS, staged)
-            _same(r.denoise_var(params), ref, f"{name}: device, {params}, staged {staged}")
-    _same(r.read_accum().reshape(H, W, 4), accum, "the accumulation image after the filter")
-    _same(r.read_moments()[0], moments, "the moments after the filter")
-    assert not np.array_equal(_bits(ref[..., :3]), _bits(accum[..., :3]))
+            same(r.denoise_var(params), ref, f"{name}: device, {params}, staged {staged}")
+    same(r.read_accum().reshape(H, W, 4), accum, "the accumulation image after the filter")
+    same(r.read_moments()[0], moments, "the moments after the filter")
+    assert not np.array_equal(bits(ref[..., :3]), bits(accum[..., :3]))
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -89,7 +62,7 @@ def test_caller_owned_destination(name):
     torch.cuda.synchronize()
     assert r.denoise_var(None, dst.data_ptr()) is None
     r.synchronize()
-    _same(dst.cpu().numpy(), want, f"{name}: caller-owned destination")
+    same(dst.cpu().numpy(), want, f"{name}: caller-owned destination")
     L = ptamd.lib()
     assert L.pt_denoise_var(r._c, None, dst.data_ptr() + 4) == PT_ERR_INVALID      # misaligned
     assert L.pt_denoise_var(r._c, None, r.accum_ptr()) == PT_ERR_INVALID           # accum onto itself
@@ -103,7 +76,7 @@ def test_calls_without_inputs_are_invalid():
     r = ptamd.Renderer(0)
     r.set_option(ptamd.PT_OPT_MOMENTS, 1)
     assert L.pt_denoise_var(r._c, None, None) == PT_ERR_INVALID     # no scene
-    r.upload_scene(*_scene("box"))
+    r.upload_scene(*scene("box"))
     assert L.pt_denoise_var(r._c, None, None) == PT_ERR_INVALID     # no camera
     r.set_camera(scenes.DEFAULT_CAMERA)
     assert L.pt_denoise_var(r._c, None, None) == PT_ERR_INVALID     # no frame
@@ -112,14 +85,6 @@ def test_calls_without_inputs_are_invalid():
     assert L.pt_denoise_var(r._c, None, None) == PT_ERR_INVALID     # no moments yet
     r.render(0, 2)
     assert r.denoise_var().shape == (12, 20, 4)
-
-
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = map(int, f.readline().split())
-        assert float(f.readline()) < 0   # little-endian
-        return np.fromfile(f, "<f4").reshape(h, w, 3)
 
 
 def test_pt_render_denoise_var_flag(tmp_path):
@@ -131,12 +96,7 @@ def test_pt_render_denoise_var_flag(tmp_path):
     assert res.returncode == 0, res.stderr[-3000:]
     r = _renderer("box")
     r.render(0, spp)
-    _same(_read_pfm(out), r.denoise_var()[..., :3], "pt_render -denoise-var")
-
-
-def _mse(a, b):
-    d = a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)
-    return float(np.mean(d * d))
+    same(read_pfm(out), r.denoise_var()[..., :3], "pt_render -denoise-var")
 
 
 @functools.lru_cache(maxsize=None)
@@ -160,7 +120,7 @@ def test_it_denoises_at_every_sample_count(name, spp):
     raw = r.read_accum().reshape(H, W, 4)
     var = r.denoise_var()
     fixed = r.denoise()
-    e_raw, e_var, e_fixed = _mse(raw, ref), _mse(var, ref), _mse(fixed, ref)
+    e_raw, e_var, e_fixed = mse(raw, ref), mse(var, ref), mse(fixed, ref)
     print(f"denoise_var {name} 96x96 {spp} spp: mse raw = {e_raw:.4e}, pt_denoise_var = {e_var:.4e} "
           f"({e_var / e_raw:.3f} of raw), pt_denoise = {e_fixed:.4e} ({e_fixed / e_raw:.3f} of raw)")
     assert np.all(np.isfinite(var))

@@ -24,7 +24,7 @@ import pytest
 import oracle_lib as O
 import ptamd
 import scenes
-from test_gpu_sweep import _same
+from support import lit_pixels, oracle_frame, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -33,14 +33,8 @@ ALL_TAIL, NO_TAIL = 1 << 30, 1
 EXIT = ptamd.PT_OPT_EXIT_SKIP
 
 
-def _built(v, i):
-    v, i, n, _, _ = ptamd.Scene.from_arrays(v, i).build_bvh().arrays()
-    return v, i, n
-
-
 def _box_arrays():
-    v, i, _, _, _ = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh().arrays()
-    return v, i
+    return scene("box")[:2]
 
 
 def _rotated_cube():
@@ -69,20 +63,17 @@ SCENES = {   # name: (vertices and indices, camera, fits in LDS)
 }
 
 
-@functools.lru_cache(maxsize=None)
+MAKERS = {name: make for name, (make, _, _) in SCENES.items()}
+
+
 def _scene(name):
-    make, cam, small = SCENES[name]
-    v, i, n = _built(*make())
-    return v, i, n, cam, small
+    return scene(name, MAKERS) + SCENES[name][1:]
 
 
 @functools.lru_cache(maxsize=None)
 def _oracle(name, depth=4, sss=3):
-    v, i, n, cam, _ = _scene(name)
-    ref, _ = O.render(v, i, n.reshape(-1), cam, scenes.REFERENCE_LIGHT, W, H, first_batch=0, n_batches=NB,
-                      max_depth=depth, sss_bounces=sss, nthreads=8)
-    ref.setflags(write=False)
-    lit = int(np.count_nonzero(np.any(ref.reshape(-1, 4)[:, :3] != 0, axis=1)))
+    ref = oracle_frame(scene(name, MAKERS), SCENES[name][1], scenes.REFERENCE_LIGHT, W, H, 0, NB, depth, sss, nthreads=8)
+    lit = lit_pixels(ref)
     assert lit >= 100, f"{name}: the oracle's frame shows {lit} lit pixels"
     return ref
 
@@ -107,16 +98,8 @@ CASES = [(s, k) for s in SCENES for k in VARIANTS if SCENES[s][2] or not VARIANT
 def _renderer(name, variant, exit_skip, depth=4, sss=3, lights=scenes.REFERENCE_LIGHT, count=False):
     v, i, n, cam, _ = _scene(name)
     opts, _, _ = VARIANTS[variant]
-    r = ptamd.Renderer(0)
-    for key, value in opts.items():
-        r.set_option(key, value)
-    r.set_option(EXIT, exit_skip)
-    if count:
-        r.set_option(ptamd.PT_OPT_COUNT_TRACED, 1)
-    r.upload_scene(v, i, n)
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(depth, sss)
+    r = renderer((v, i, n), cam, lights, depth, sss,
+                 options=list(opts.items()) + [(EXIT, exit_skip)] + ([(ptamd.PT_OPT_COUNT_TRACED, 1)] if count else []))
     if variant.startswith("sweep") and not count:
         assert r.sweep_info()[1] == i.size // 3, r.sweep_info()
     if opts.get(WIDE) == 1:
@@ -132,7 +115,7 @@ def test_frames_equal_the_oracle(name, variant):
         r.resize_and_clear(W, H)
         r.render(0, 1)
         r.render(1, NB - 1)
-        _same(r.read_accum(), ref, f"{name} {variant}, PT_OPT_EXIT_SKIP {exit_skip}")
+        same(r.read_accum(), ref, f"{name} {variant}, PT_OPT_EXIT_SKIP {exit_skip}")
         assert r.last_kernel() == VARIANTS[variant][2]
         r.close()
 
@@ -148,7 +131,7 @@ def _counts(name, variant, exit_skip, depth, sss, ref, lights=scenes.REFERENCE_L
         nan_g, nan_r = np.isnan(gpu), np.isnan(ref)
         assert np.array_equal(nan_g, nan_r)
         gpu, ref = np.where(nan_g, 0, gpu).astype(np.float32), np.where(nan_r, 0, ref).astype(np.float32)
-    _same(gpu, ref, f"counting: {name} {variant}, PT_OPT_EXIT_SKIP {exit_skip}")
+    same(gpu, ref, f"counting: {name} {variant}, PT_OPT_EXIT_SKIP {exit_skip}")
     t = r.traced()
     r.close()
     return t

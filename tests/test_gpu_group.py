@@ -6,20 +6,18 @@ member still owns its own context, stream and tile share, and the group's
 exchange runs exactly as across devices (peer stores into the frame on the
 first device, or packed tiles copied with hipMemcpyPeerAsync).  Every frame
 must be bitwise the single-GPU frame and the oracle's."""
-import numpy as np
 import pytest
 
 import oracle_lib as O
 import ptamd
 import scenes
+from support import same, scene
 
 pytestmark = pytest.mark.gpu
 
 
 def _box():
-    s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
+    return scene("box")
 
 
 def _setup(r, v, i, n, cam=scenes.DEFAULT_CAMERA, depth=4, int_bits=False):
@@ -30,12 +28,6 @@ def _setup(r, v, i, n, cam=scenes.DEFAULT_CAMERA, depth=4, int_bits=False):
     return r
 
 
-def _same(a, b, what):
-    if not np.array_equal(a.view(np.uint32), b.view(np.uint32)):
-        bad = np.flatnonzero(a.view(np.uint32) != b.view(np.uint32))
-        raise AssertionError(f"{what}: {bad.size} floats differ, first at pixel {bad[0] // 4}: {a[bad[0]]} vs {b[bad[0]]}")
-
-
 def test_group_of_one_is_a_plain_context():
     v, i, n = _box()
     g = _setup(ptamd.Renderer(devices=[0]), v, i, n)
@@ -43,7 +35,7 @@ def test_group_of_one_is_a_plain_context():
     g.resize_and_clear(96, 64)
     g.render(0, 3)
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, 96, 64, n_batches=3)
-    _same(g.read_accum(), ref, "group of one vs oracle")
+    same(g.read_accum(), ref, "group of one vs oracle")
 
 
 @pytest.mark.parametrize("exchange", [0, 1])
@@ -63,16 +55,16 @@ def test_group_frame_equals_single_gpu(members, exchange):
         r.render(0, 2)
         r.dispatch(2)
         r.dispatch(3)
-    _same(g.read_accum(), one.read_accum(), f"{members} members, exchange {exchange}: batches 0-3")
+    same(g.read_accum(), one.read_accum(), f"{members} members, exchange {exchange}: batches 0-3")
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, n_batches=4)
-    _same(g.read_accum(), ref, "group vs oracle")
+    same(g.read_accum(), ref, "group vs oracle")
     # a fresh frame from batch 0 over the old image, as the progressive loop
     # does after a camera change
     cam2 = scenes.camera((0.4, 0.3, 4.0))
     for r in (g, one):
         r.set_camera(cam2)
         r.render(0, 2)
-    _same(g.read_accum(), one.read_accum(), "camera change, fresh batch 0")
+    same(g.read_accum(), one.read_accum(), "camera change, fresh batch 0")
 
 
 def test_group_progressive_loop_and_readback():
@@ -85,9 +77,9 @@ def test_group_progressive_loop_and_readback():
     assert g.progressive_advance(2) == (3, 2)
     snap = g.readback_end(t)
     ref3, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, 64, 48, n_batches=3)
-    _same(snap, ref3, "readback snapshot after 3 batches")
+    same(snap, ref3, "readback snapshot after 3 batches")
     ref5, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, 64, 48, n_batches=5)
-    _same(g.read_accum(), ref5, "5 batches")
+    same(g.read_accum(), ref5, "5 batches")
     assert not g.progressive_camera(scenes.DEFAULT_CAMERA)
     assert g.progressive_advance(100, limit=7) == (5, 2)
 
@@ -102,7 +94,7 @@ def test_group_stats_sum_to_the_single_gpu_counts():
         r.reset_stats()
         r.render(0, 2)
     assert g.stats() == one.stats()
-    _same(g.read_accum(), one.read_accum(), "stats mode")
+    same(g.read_accum(), one.read_accum(), "stats mode")
 
 
 def test_group_wavefront_scene_matches_single_gpu():
@@ -119,7 +111,7 @@ def test_group_wavefront_scene_matches_single_gpu():
         r.resize_and_clear(128, 96)
         r.render(0, 2)
     assert g.last_kernel() == ptamd.KERNEL_WAVEFRONT
-    _same(g.read_accum(), one.read_accum(), "wavefront, 3 members")
+    same(g.read_accum(), one.read_accum(), "wavefront, 3 members")
 
 
 def test_group_rejects_share_calls():
@@ -150,7 +142,7 @@ def test_group_check_matches_on_one_device():
     assert state == 0 and ms_peer > 0 and ms_staged > 0
     assert g.group_info()[1] is True
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, 96, 64, n_batches=3)
-    _same(g.read_accum(), ref, "after the check")
+    same(g.read_accum(), ref, "after the check")
 
 
 def test_group_check_mismatch_falls_back_to_staged_copies():
@@ -171,7 +163,7 @@ def test_group_check_mismatch_falls_back_to_staged_copies():
     assert g.group_info()[1] is False
     g.dispatch(3)
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, n_batches=4)
-    _same(g.read_accum(), ref, "batches 0-1 by peer stores, 2-3 by staged copies")
+    same(g.read_accum(), ref, "batches 0-1 by peer stores, 2-3 by staged copies")
 
 
 def test_group_exchange_switch_keeps_the_accumulation():
@@ -189,7 +181,7 @@ def test_group_exchange_switch_keeps_the_accumulation():
     g.set_option(ptamd.PT_OPT_GROUP_EXCHANGE, 0)
     assert g.progressive_advance(1) == (4, 1)
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, n_batches=5)
-    _same(g.read_accum(), ref, "exchange 0 -> 1 -> 0 across advances")
+    same(g.read_accum(), ref, "exchange 0 -> 1 -> 0 across advances")
 
 
 def _devices():
@@ -219,9 +211,9 @@ def test_group_on_distinct_devices(exchange):
     if exchange == 0:
         assert g.group_check()[0] in (0, 1)   # the probe ran; 1 would mean staged copies took over
     ref3, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, n_batches=3)
-    _same(snap, ref3, f"{nd} devices, exchange {exchange}: snapshot after 3 batches")
+    same(snap, ref3, f"{nd} devices, exchange {exchange}: snapshot after 3 batches")
     ref5, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, n_batches=5)
-    _same(g.read_accum(), ref5, f"{nd} devices, exchange {exchange}: 5 batches")
+    same(g.read_accum(), ref5, f"{nd} devices, exchange {exchange}: 5 batches")
 
 
 def test_group_check_probe_frames_are_not_counted():
@@ -264,4 +256,4 @@ def test_group_check_rearmed_after_a_failed_render():
     g.render(0, 2)
     assert g.group_check()[0] == 0
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, 48, 32, n_batches=2)
-    _same(g.read_accum(), ref, "after a failed first render")
+    same(g.read_accum(), ref, "after a failed first render")

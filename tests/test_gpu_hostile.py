@@ -25,10 +25,9 @@ import pytest
 import oracle_lib as O
 import ptamd
 import scenes
-import test_sweep
-import test_wide
-from test_cull import ring_lights
-from test_gpu_sweep import _same
+from cull_support import ring_lights
+from support import built, lit_pixels, oracle_frame, renderer, same, scene
+from sweep_support import HOSTILE as TINY_HOSTILE, HOSTILE_TABLES
 
 pytestmark = pytest.mark.gpu
 
@@ -38,20 +37,8 @@ SPHERE_CAM = scenes.camera((0.0, 0.5, 3.0))
 MISS = np.array([0.0, 0.0, 0.0, 1e30], np.float32)
 
 
-def _built(v, i, int_bits=False):
-    v, i, n, _, _ = ptamd.Scene.from_arrays(v, i).build_bvh(int_bits=int_bits).arrays()
-    return v, i, n
-
-
-def _lit(frame):
-    return int(np.count_nonzero(np.any(frame.reshape(-1, 4)[:, :3] != 0, axis=1)))
-
-
 def _oracle_frame(v, i, n, cam, lights, int_bits=False):
-    ref, _ = O.render(v, i, n.reshape(-1), cam, lights, W, H, first_batch=0, n_batches=3, max_depth=4, sss_bounces=3,
-                      nthreads=8, int_bits=int_bits)
-    ref.setflags(write=False)
-    return ref
+    return oracle_frame((v, i, n), cam, lights, W, H, nb=3, nthreads=8, int_bits=int_bits)
 
 
 def _moved(cam, scale, offset):
@@ -61,11 +48,11 @@ def _moved(cam, scale, offset):
 # ---- device-memory scenes ---------------------------------------------------
 
 def _big_inputs(name):
-    """(vertices, indices, camera, lights, int_bits) of a scene of test_wide.HOSTILE."""
+    """(vertices, indices, camera, lights, int_bits) of a scene of scenes.WIDE_HOSTILE."""
     if name == "degenerates":   # larger triangles than the CPU case's: more of the frame lit
         v, i = scenes.with_degenerates(*scenes.random_triangles(3000, seed=8, spread=0.5, size=0.05))
         return v, i, scenes.camera((0.3, 0.2, 2.2)), scenes.REFERENCE_LIGHT, False
-    v, i = test_wide.HOSTILE[name]()
+    v, i = scenes.WIDE_HOSTILE[name]()
     if name == "cloud_far":     # int-encoded links, as the >= 2^24-node trees travel
         return (v, i) + _moved(scenes.camera((0.3, 0.2, 2.2)), 1.0, (1000, -500, 2000)) + (True,)
     if name == "sphere_at_300":
@@ -83,9 +70,9 @@ def _big_inputs(name):
 @functools.lru_cache(maxsize=None)
 def _big(name):
     v, i, cam, lights, int_bits = _big_inputs(name)
-    v, i, n = _built(v, i, int_bits)
+    v, i, n = built(v, i, int_bits)
     ref = _oracle_frame(v, i, n, cam, lights, int_bits)
-    assert _lit(ref) >= MIN_LIT, f"{name}: the oracle's frame shows {_lit(ref)} lit pixels"
+    assert lit_pixels(ref) >= MIN_LIT, f"{name}: the oracle's frame shows {lit_pixels(ref)} lit pixels"
     return v, i, n, cam, lights, int_bits, ref
 
 
@@ -111,28 +98,20 @@ def _render_two_launches(r, ref, what):
     r.resize_and_clear(W, H)
     r.render(0, 1)
     r.render(1, 2)
-    _same(r.read_accum(), ref, what)
+    same(r.read_accum(), ref, what)
 
 
 def _wide_renderer(v, i, n, cam, lights, int_bits, kernel, opts):
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_SCENE_IN_LDS, 0)
-    r.set_option(ptamd.PT_OPT_KERNEL, kernel)
-    if kernel == ptamd.KERNEL_WAVEFRONT:
-        r.set_option(ptamd.PT_OPT_WF_TAIL, ALL_TAIL)
-    for key, value in opts.items():
-        r.set_option(key, value)
-    r.upload_scene(v, i, n, int_bits=int_bits)   # PT_OPT_WIDE_BUILD is read here
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(4, 3)
+    tail = [(ptamd.PT_OPT_WF_TAIL, ALL_TAIL)] if kernel == ptamd.KERNEL_WAVEFRONT else []
+    r = renderer((v, i, n), cam, lights, int_bits=int_bits,   # PT_OPT_WIDE_BUILD is read at the scene's upload
+                 options=[(ptamd.PT_OPT_SCENE_IN_LDS, 0), (ptamd.PT_OPT_KERNEL, kernel)] + tail + list(opts.items()))
     info = r.wide_info()
     assert info[0] > 0 and info[1] > 0, f"no wide tree: {info}"   # a refused tree would pass on the exact walk
     return r
 
 
 @pytest.mark.parametrize("variant", list(BIG_VARIANTS))
-@pytest.mark.parametrize("name", sorted(test_wide.HOSTILE))
+@pytest.mark.parametrize("name", sorted(scenes.WIDE_HOSTILE))
 def test_device_memory_scene(name, variant):
     v, i, n, cam, lights, int_bits, ref = _big(name)
     kernel, opts = BIG_VARIANTS[variant]
@@ -148,7 +127,7 @@ def test_coincident_copies_tie_break_decides_the_image():
     is the visit order's.  The oracle's frame of it differs from its frame of
     the single sphere nearly everywhere the sphere is lit."""
     v, i, n, cam, lights, _, ref = _big("coincident_x6")
-    sv, si, sn = _built(*scenes.displaced_sphere(2))
+    sv, si, sn = built(*scenes.displaced_sphere(2))
     single = _oracle_frame(sv, si, sn, cam, lights)
     a, b = ref.reshape(-1, 4)[:, :3], single.reshape(-1, 4)[:, :3]
     lit = np.any(a != 0, axis=1) | np.any(b != 0, axis=1)
@@ -189,7 +168,7 @@ def _facing_light(v, i):
 
 @functools.lru_cache(maxsize=None)
 def _tiny(name):
-    v, i, n = _built(*test_sweep.HOSTILE[name]())
+    v, i, n = built(*TINY_HOSTILE[name]())
     if name == "box@300":
         cam, lights = _moved(scenes.DEFAULT_CAMERA, 1.0, (300, 300, -300))
     elif name == "box*50":
@@ -201,7 +180,7 @@ def _tiny(name):
     else:
         cam, lights = scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT
     ref = _oracle_frame(v, i, n, cam, lights)
-    assert _lit(ref) >= MIN_LIT, f"{name}: the oracle's frame shows {_lit(ref)} lit pixels"
+    assert lit_pixels(ref) >= MIN_LIT, f"{name}: the oracle's frame shows {lit_pixels(ref)} lit pixels"
     return v, i, n, cam, lights, ref
 
 
@@ -223,22 +202,16 @@ TINY_VARIANTS = {
 
 
 @pytest.mark.parametrize("variant", list(TINY_VARIANTS))
-@pytest.mark.parametrize("name", sorted(test_sweep.HOSTILE))
+@pytest.mark.parametrize("name", sorted(TINY_HOSTILE))
 def test_tiny_scene(name, variant):
     v, i, n, cam, lights, ref = _tiny(name)
     opts, walk, kernel = TINY_VARIANTS[variant]
-    r = ptamd.Renderer(0)
-    for key, value in opts.items():
-        r.set_option(key, value)
-    r.upload_scene(v, i, n)
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(4, 3)
+    r = renderer((v, i, n), cam, lights, options=opts)
     boxes, leaves = r.sweep_info()
     if walk == SWEEP:
         assert leaves == i.size // 3 and 1 <= boxes <= 2 * leaves - 1
-        if name in test_sweep.HOSTILE_TABLES:
-            assert (boxes, leaves) == test_sweep.HOSTILE_TABLES[name]
+        if name in HOSTILE_TABLES:
+            assert (boxes, leaves) == HOSTILE_TABLES[name]
     else:
         assert (boxes, leaves) == (0, 0)
     if variant == "wavefront_wide":
@@ -262,17 +235,12 @@ def _check_guide(v, i, n, cam, lights, int_bits, what, GW=32, GH=24):
             want[y, x] = np.concatenate([nrm, [np.float32(t)]]) if hit else MISS
     hits = int(np.count_nonzero(want[..., 3] < 1e30))
     assert 50 <= hits < GW * GH, hits
-    r = ptamd.Renderer(0)
-    r.upload_scene(v, i, n, int_bits=int_bits)
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(4, 3)
-    r.resize_and_clear(GW, GH)
+    r = renderer((v, i, n), cam, lights, size=(GW, GH), int_bits=int_bits)
     assert r.wide_info()[0] > 0, r.wide_info()
     for key, value in [(ptamd.PT_OPT_WIDE, 1), (ptamd.PT_OPT_WIDE_NODE, 128), (ptamd.PT_OPT_WIDE, 0)]:
         r.set_option(key, value)
         r.render_guide()
-        _same(r.read_guide(), want, f"guide {what}, option {key} = {value}")
+        same(r.read_guide(), want, f"guide {what}, option {key} = {value}")
     r.close()
 
 
@@ -289,7 +257,7 @@ def test_guide_image_from_far_away():
     from 1,100 away through a field of view of 0.027 degrees -- S = |o - v0|,
     which the cull bound's error terms multiply, is 2,000 times the scene's
     size on every ray (test_wide.test_wide_walk_far_origins on the device)."""
-    v, i, n = _built(*scenes.random_triangles(30000, seed=9, spread=0.2, size=0.004))
+    v, i, n = built(*scenes.random_triangles(30000, seed=9, spread=0.2, size=0.004))
     cam = scenes.camera((300.0, 200.0, 1000.0), fov=0.027)
     _check_guide(v, i, n, cam, scenes.REFERENCE_LIGHT, False, "far camera")
 
@@ -297,16 +265,14 @@ def test_guide_image_from_far_away():
 # ---- many lights ----------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)
-def _many(scene, n_lights):
-    if scene == "box":
-        v, i, n, _, _ = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh().arrays()
-        cam = scenes.DEFAULT_CAMERA
+def _many(which, n_lights):
+    if which == "box":
+        (v, i, n), cam = scene("box"), scenes.DEFAULT_CAMERA
     else:
-        v, i, n = _built(*scenes.displaced_sphere(3))
-        cam = SPHERE_CAM
+        (v, i, n), cam = scene("sphere"), SPHERE_CAM
     lights = ring_lights(n_lights)
     ref = _oracle_frame(v, i, n, cam, lights)
-    assert _lit(ref) >= MIN_LIT, f"{scene}, {n_lights} lights: the oracle's frame shows {_lit(ref)} lit pixels"
+    assert lit_pixels(ref) >= MIN_LIT, f"{which}, {n_lights} lights: the oracle's frame shows {lit_pixels(ref)} lit pixels"
     return v, i, n, cam, lights, ref
 
 
@@ -317,13 +283,7 @@ def test_many_lights_box(kernel, sweep, n_lights):
     """7 lights fill the cull-rectangle table (kMaxCullRects = 8), 8 and 9
     switch primary culling off; the per-light loops run 7 to 9 turns."""
     v, i, n, cam, lights, ref = _many("box", n_lights)
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_KERNEL, kernel)
-    r.set_option(ptamd.PT_OPT_SMALL_SWEEP, sweep)
-    r.upload_scene(v, i, n)
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(4, 3)
+    r = renderer((v, i, n), cam, lights, options=[(ptamd.PT_OPT_KERNEL, kernel), (ptamd.PT_OPT_SMALL_SWEEP, sweep)])
     if kernel == 1 and sweep:
         assert r.sweep_info() == (7, 12)
     else:
@@ -353,17 +313,11 @@ def test_many_lights_primaries(kernel):
     primaries = {}
     for n_lights in (7, 8, 9):
         v, i, n, cam, lights, ref = _many("box", n_lights)
-        r = ptamd.Renderer(0)
-        r.set_option(ptamd.PT_OPT_KERNEL, kernel)
-        r.set_option(ptamd.PT_OPT_COUNT_TRACED, 1)
-        r.upload_scene(v, i, n)
-        r.upload_lights(lights)
-        r.set_camera(cam)
-        r.set_params(4, 3)
-        r.resize_and_clear(W, H)
+        r = renderer((v, i, n), cam, lights, size=(W, H),
+                     options=[(ptamd.PT_OPT_KERNEL, kernel), (ptamd.PT_OPT_COUNT_TRACED, 1)])
         r.reset_stats()
         r.render(0, nb)
-        _same(r.read_accum(), ref, f"counting mode, {n_lights} lights, kernel {kernel}")
+        same(r.read_accum(), ref, f"counting mode, {n_lights} lights, kernel {kernel}")
         assert r.last_kernel() == kernel
         primaries[n_lights] = r.traced()["primaries"]
         r.close()

@@ -14,9 +14,9 @@ import pytest
 import torch
 
 import denoise_var_ref as R
-import oracle_lib as O
 import ptamd
 import scenes
+from support import bits, oracle_frame, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -27,50 +27,15 @@ FRAMES = {"box": (scenes.DEFAULT_CAMERA, 64, 48), "sphere": (CAM_324, 67, 45)}  
 TINY = np.float32(np.finfo(np.float32).tiny)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got, np.float32).reshape(-1), np.asarray(want, np.float32).reshape(-1)
-    assert got.shape == want.shape, what
-    bad = np.flatnonzero(_bits(got) != _bits(want))
-    assert bad.size == 0, f"{what}: {bad.size} of {got.size} floats differ, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        s = ptamd.Scene.from_arrays(*scenes.displaced_sphere(subdiv=3)).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
-
-
-@functools.lru_cache(maxsize=None)
 def _oracle(name, first, nb, cam_key="own"):
     cam, W, H = FRAMES[name]
-    if cam_key == "far":
-        cam = CAM_FAR
-    v, i, n = _scene(name)
-    ref, _ = O.render(v, i, n.reshape(-1), cam, scenes.REFERENCE_LIGHT, W, H, first_batch=first, n_batches=nb)
-    ref.setflags(write=False)
-    return ref
+    return oracle_frame(scene(name), CAM_FAR if cam_key == "far" else cam, scenes.REFERENCE_LIGHT, W, H, first, nb)
 
 
 def _renderer(name, opts=(), moments=1, cam=None):
     own_cam, W, H = FRAMES[name]
-    r = ptamd.Renderer(0)
-    for key, value in opts:
-        r.set_option(key, value)
-    r.set_option(ptamd.PT_OPT_MOMENTS, moments)
-    r.upload_scene(*_scene(name))
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(own_cam if cam is None else cam)
-    r.set_params(4, 3)
-    r.resize_and_clear(W, H)
-    return r
+    return renderer(scene(name), own_cam if cam is None else cam, size=(W, H),
+                    options=list(opts) + [(ptamd.PT_OPT_MOMENTS, moments)])
 
 
 def _sample_colours(name, b, cam_key="own"):
@@ -90,7 +55,7 @@ def test_lone_batch_moments_match_the_definition(name):
         assert (b + 1) & b == 0
         r.clear()
         r.dispatch(b)
-        _same(r.read_accum(), _oracle(name, b, 1), f"{name}: accumulator of the lone batch {b}")
+        same(r.read_accum(), _oracle(name, b, 1), f"{name}: accumulator of the lone batch {b}")
         got, n = r.read_moments()
         assert n == (1 if b == 0 else 0)          # only batch 0 alone is "batches 0..n-1"
         c, exact = _sample_colours(name, b)
@@ -98,8 +63,8 @@ def test_lone_batch_moments_match_the_definition(name):
         assert np.count_nonzero(live) >= 100
         assert np.count_nonzero(live & ~exact) < 0.01 * np.count_nonzero(live)
         want = R.fold_moments(np.zeros((H, W, 2), np.float32), c, b)
-        _same(got[exact], want[exact], f"{name}: moments of the lone batch {b}")
-        assert np.all(_bits(got[~live]) == 0)     # L = +0 wherever nothing was seen
+        same(got[exact], want[exact], f"{name}: moments of the lone batch {b}")
+        assert np.all(bits(got[~live]) == 0)     # L = +0 wherever nothing was seen
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -107,7 +72,7 @@ def test_two_batches_match_the_two_step_fold(name):
     _, W, H = FRAMES[name]
     r = _renderer(name)
     r.render(0, 2)
-    _same(r.read_accum(), _oracle(name, 0, 2), f"{name}: accumulator")
+    same(r.read_accum(), _oracle(name, 0, 2), f"{name}: accumulator")
     got, n = r.read_moments()
     assert n == 2 and r.moments_ptr()
     c0, e0 = _sample_colours(name, 0)
@@ -115,14 +80,14 @@ def test_two_batches_match_the_two_step_fold(name):
     want = R.fold_moments(R.fold_moments(np.zeros((H, W, 2), np.float32), c0, 0), c1, 1)
     ok = e0 & e1
     assert np.count_nonzero(~ok) < 0.01 * np.count_nonzero(np.any(c0 != 0, axis=-1))
-    _same(got[ok], want[ok], f"{name}: moments of batches 0 and 1")
+    same(got[ok], want[ok], f"{name}: moments of batches 0 and 1")
     assert np.any(got[..., 1] > got[..., 0] * got[..., 0])   # some pixel has a variance
 
 
 def _baseline(name, nb):
     r = _renderer(name)
     r.render(0, nb)
-    _same(r.read_accum(), _oracle(name, 0, nb), f"{name}: accumulator, {nb} batches")
+    same(r.read_accum(), _oracle(name, 0, nb), f"{name}: accumulator, {nb} batches")
     m, n = r.read_moments()
     assert n == nb
     return m
@@ -136,10 +101,10 @@ def _base(name, nb):
 
 
 def _check_run(name, r, nb, what):
-    _same(r.read_accum(), _oracle(name, 0, nb), f"{name}, {what}: accumulator")
+    same(r.read_accum(), _oracle(name, 0, nb), f"{name}, {what}: accumulator")
     m, n = r.read_moments()
     assert n == nb, what
-    _same(m, _base(name, nb), f"{name}, {what}: moments")
+    same(m, _base(name, nb), f"{name}, {what}: moments")
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -230,15 +195,15 @@ def test_camera_change_leaves_zero_moments_on_culled_pixels():
         old, _ = r.read_moments()
         r.set_camera(CAM_FAR)
         r.render(0, 2)
-        _same(r.read_accum(), _oracle(name, 0, 2, "far"), f"fresh {fresh}: accumulator under the new camera")
+        same(r.read_accum(), _oracle(name, 0, 2, "far"), f"fresh {fresh}: accumulator under the new camera")
         new, n = r.read_moments()
         assert n == 2
         c0, e0 = _sample_colours(name, 0, "far")
         c1, e1 = _sample_colours(name, 1, "far")
         want = R.fold_moments(R.fold_moments(np.zeros((H, W, 2), np.float32), c0, 0), c1, 1)
         assert np.all(e0 & e1)
-        _same(new, want, f"fresh {fresh}: moments under the new camera")
-        gone = np.any(old != 0, axis=-1) & np.all(_bits(new) == 0, axis=-1)
+        same(new, want, f"fresh {fresh}: moments under the new camera")
+        gone = np.any(old != 0, axis=-1) & np.all(bits(new) == 0, axis=-1)
         assert np.count_nonzero(gone) >= 100, "part of the old image is culled now"
 
 
@@ -277,18 +242,18 @@ def test_bookkeeping_off_gap_and_clear():
         clear()
         assert not r.moments_ptr()
         m, n = r.read_moments()
-        assert n == 0 and np.all(_bits(m) == 0)
+        assert n == 0 and np.all(bits(m) == 0)
         r.render(0, 2)
         assert r.moments_ptr()
     frame = torch.zeros(H, W, 4, dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
     r.bind_accum(frame.data_ptr(), W, H)
     m, n = r.read_moments()
-    assert n == 0 and np.all(_bits(m) == 0) and not r.moments_ptr()
+    assert n == 0 and np.all(bits(m) == 0) and not r.moments_ptr()
     r.render(0, 8)
     r.synchronize()
-    _same(frame.cpu().numpy(), _oracle(name, 0, 8), "bound accumulator")
-    _same(r.read_moments()[0], _base(name, 8), "moments beside a bound accumulator")
+    same(frame.cpu().numpy(), _oracle(name, 0, 8), "bound accumulator")
+    same(r.read_moments()[0], _base(name, 8), "moments beside a bound accumulator")
     assert L.pt_set_option(r._c, ptamd.PT_OPT_MOMENTS, 2) == PT_ERR_INVALID
     small = np.zeros(8, np.float32)
     assert L.pt_read_moments(r._c, small.ctypes.data, small.size, None) == PT_ERR_INVALID
@@ -326,15 +291,15 @@ def test_unsupported_combinations_are_refused():
 def test_moments_off_changes_nothing(name):
     r = _renderer(name, moments=0)
     r.render(0, 8)
-    _same(r.read_accum(), _oracle(name, 0, 8), f"{name}: option never set to 1")
+    same(r.read_accum(), _oracle(name, 0, 8), f"{name}: option never set to 1")
     r.set_option(ptamd.PT_OPT_MOMENTS, 1)
     r.render(0, 2)
     r.set_option(ptamd.PT_OPT_MOMENTS, 0)
     r.clear()
     r.render(0, 3)
     r.render(3, 5)
-    _same(r.read_accum(), _oracle(name, 0, 8), f"{name}: option back at 0")
+    same(r.read_accum(), _oracle(name, 0, 8), f"{name}: option back at 0")
     for b in (1, 7):
         r.clear()
         r.dispatch(b)
-        _same(r.read_accum(), _oracle(name, b, 1), f"{name}: lone batch {b}, option at 0")
+        same(r.read_accum(), _oracle(name, b, 1), f"{name}: lone batch {b}, option at 0")

@@ -10,6 +10,8 @@ import pytest
 import oracle_lib as O
 import ptamd
 import scenes
+import support
+from support import renderer, same
 
 pytestmark = pytest.mark.gpu
 
@@ -18,34 +20,17 @@ TOL = 1e-4   # north_star per-channel tolerance; every assertion below is strict
 
 def _setup(v, i, n, cam=scenes.DEFAULT_CAMERA, lights=scenes.REFERENCE_LIGHT, depth=4, sss=3, int_bits=False,
            lds=1):
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_SCENE_IN_LDS, lds)
-    r.upload_scene(v, i, n, int_bits=int_bits)
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(depth, sss)
-    return r
+    return renderer((v, i, n), cam, lights, depth, sss, options=[(ptamd.PT_OPT_SCENE_IN_LDS, lds)], int_bits=int_bits)
 
 
 def _box():
-    s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
+    return support.scene("box")
 
 
 def _oracle(v, i, n, W, H, first=0, nb=1, depth=4, sss=3, cam=scenes.DEFAULT_CAMERA,
             lights=scenes.REFERENCE_LIGHT, **kw):
     return O.render(v, i, n.reshape(-1), cam, lights, W, H, first_batch=first, n_batches=nb,
                     max_depth=depth, sss_bounces=sss, **kw)
-
-
-def _assert_same(gpu, ref, what=""):
-    assert gpu.shape == ref.shape
-    if not np.array_equal(gpu.view(np.uint32), ref.view(np.uint32)):
-        bad = np.flatnonzero(gpu.view(np.uint32) != ref.view(np.uint32))
-        diff = np.nanmax(np.abs(gpu[bad] - ref[bad])) if bad.size else 0.0
-        raise AssertionError(f"{what}: {bad.size} of {gpu.size} floats differ (max |diff| {diff}); "
-                             f"first at pixel {bad[0] // 4} gpu={gpu[bad[0]]} ref={ref[bad[0]]}")
 
 
 @pytest.mark.parametrize("lds", [0, 2])
@@ -57,7 +42,7 @@ def test_box_matches_oracle(W, H, depth, nb, lds):
     r.render(0, nb)
     gpu = r.read_accum()
     ref, _ = _oracle(v, i, n, W, H, nb=nb, depth=depth)
-    _assert_same(gpu, ref, f"box {W}x{H} d{depth} spp{nb}")
+    same(gpu, ref, f"box {W}x{H} d{depth} spp{nb}")
     assert np.all(np.abs(gpu - ref) <= TOL)
 
 
@@ -72,15 +57,14 @@ def test_sample_lanes(spl, nb):
     r.resize_and_clear(40, 27)
     r.render(2, nb)
     ref, _ = _oracle(v, i, n, 40, 27, first=2, nb=nb)
-    _assert_same(r.read_accum(), ref, f"spl={spl} nb={nb}")
+    same(r.read_accum(), ref, f"spl={spl} nb={nb}")
 
 
 def _scene_cases():
     gv, gi = scenes.grid_mesh(6)
     sv, si = scenes.displaced_sphere(2)
     tv, ti = scenes.random_triangles(1000, seed=1000)
-    two = np.concatenate([scenes.REFERENCE_LIGHT,
-                          ptamd.pack_light([0.5, 0.5, 1.5], [0, 0, -1], [2, 4, 8], [0.5, 1.0])])
+    two = support.TWO_LIGHTS
     return [("grid2lights", gv, gi, scenes.camera((0.0, 0.0, 3.0)), two, 3, 2),
             ("sphere", sv, si, scenes.camera((0.0, 0.5, 3.0)), scenes.REFERENCE_LIGHT, 4, 3),
             ("random", tv, ti, scenes.camera((0.3, 0.2, 2.2)), scenes.REFERENCE_LIGHT, 4, 3),
@@ -111,11 +95,11 @@ def test_dispatch_sequence_equals_fused_render():
     r.clear()
     r.render(0, 5)
     fused = r.read_accum()
-    _assert_same(fused, seq, "dispatch x5 vs render(0,5)")
+    same(fused, seq, "dispatch x5 vs render(0,5)")
     r.clear()
     r.render(0, 2)
     r.render(2, 3)
-    _assert_same(r.read_accum(), seq, "render(0,2)+render(2,3)")
+    same(r.read_accum(), seq, "render(0,2)+render(2,3)")
 
 
 @pytest.mark.parametrize("lds", [0, 2])
@@ -133,8 +117,8 @@ def test_stats_mode_counts_and_output(lds):
     counted = r.read_accum()
     st = r.stats()
     ref, ost = _oracle(v, i, n, W, H, nb=nb)
-    _assert_same(counted, plain, "stats-mode image vs fast image")
-    _assert_same(counted, ref, "stats-mode image vs oracle")
+    same(counted, plain, "stats-mode image vs fast image")
+    same(counted, ref, "stats-mode image vs oracle")
     assert (st["rays"], st["nodes"], st["leaf_tests"]) == tuple(int(x) for x in ost)
     assert st["samples"] == W * H * nb
 
@@ -148,7 +132,7 @@ def test_box_1080p_8spp_full_frame(lds):
     r.render(0, 8)
     gpu = r.read_accum()
     ref, _ = _oracle(v, i, n, 1920, 1080, nb=8)
-    _assert_same(gpu, ref, "box 1080p 8spp")
+    same(gpu, ref, "box 1080p 8spp")
 
 
 def test_box_1080p_8spp_bench_options_two_contexts():
@@ -177,7 +161,7 @@ def test_box_1080p_8spp_bench_options_two_contexts():
         r.synchronize()
     ref, _ = _oracle(v, i, n, 1920, 1080, nb=8)
     for k, r in enumerate(ctxs):
-        _assert_same(r.read_accum(), ref, f"bench options, context {k}")
+        same(r.read_accum(), ref, f"bench options, context {k}")
     for r in ctxs:
         r.close()
 
@@ -200,7 +184,7 @@ def test_mixed_lanes_static_and_measured_schedules():
         r.synchronize()
         seen.add(r.mixed_info()[0])
         if k in (0, 11):
-            _assert_same(r.read_accum(), ref, f"mixed lanes, frame {k}, schedule {r.mixed_info()}")
+            same(r.read_accum(), ref, f"mixed lanes, frame {k}, schedule {r.mixed_info()}")
     sched, items, measured = r.mixed_info()
     assert sched == 2 and measured >= 2 and items > 0, r.mixed_info()
     assert 0 in seen   # uniform lanes while the costs are measured
@@ -210,7 +194,7 @@ def test_mixed_lanes_static_and_measured_schedules():
     r.render(0, 8)
     assert r.mixed_info()[0] == 0
     ref2, _ = _oracle(v, i, n, 1920, 1080, nb=8, cam=cam2)
-    _assert_same(r.read_accum(), ref2, "mixed lanes after a camera change")
+    same(r.read_accum(), ref2, "mixed lanes after a camera change")
 
 
 @pytest.mark.parametrize("budget,spl,nb,first", [(50, 4, 8, 0), (1000, 4, 3, 2), (100, 8, 13, 0), (7, 2, 5, 1)])
@@ -229,7 +213,7 @@ def test_mixed_lanes_static_budgets(budget, spl, nb, first):
     r.render(first, nb)
     assert r.mixed_info()[0] == 1
     ref, _ = _oracle(v, i, n, W, H, first=0, nb=first + nb)
-    _assert_same(r.read_accum(), ref, f"mixed budget {budget} spl {spl} nb {nb} first {first}")
+    same(r.read_accum(), ref, f"mixed budget {budget} spl {spl} nb {nb} first {first}")
 
 
 def test_culled_items_written_once_per_layout():
@@ -249,34 +233,34 @@ def test_culled_items_written_once_per_layout():
     want1_5, _ = _oracle(v, i, n, W, H, nb=5)
     want2_2, _ = _oracle(v, i, n, W, H, nb=2, cam=cam2)
     r.render(0, 2)
-    _assert_same(r.read_accum(), want1_2, "first frame")
+    same(r.read_accum(), want1_2, "first frame")
     r.render(0, 2)
-    _assert_same(r.read_accum(), want1_2, "repeat (fill skipped)")
+    same(r.read_accum(), want1_2, "repeat (fill skipped)")
     r.render(2, 3)
-    _assert_same(r.read_accum(), want1_5, "continuation")
+    same(r.read_accum(), want1_5, "continuation")
     r.set_camera(cam2)
     r.render(0, 2)
-    _assert_same(r.read_accum(), want2_2, "another camera")
+    same(r.read_accum(), want2_2, "another camera")
     r.set_camera(scenes.DEFAULT_CAMERA)
     r.render(0, 2)
-    _assert_same(r.read_accum(), want1_2, "back to the first camera")
+    same(r.read_accum(), want1_2, "back to the first camera")
     r.clear()
     r.render(0, 2)
-    _assert_same(r.read_accum(), want1_2, "after a clear")
+    same(r.read_accum(), want1_2, "after a clear")
     nanbuf = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda:0")
     r.bind_accum(nanbuf.data_ptr(), W, H)
     r.set_option(ptamd.PT_OPT_FRESH_BATCH0, 1)
     for k in range(2):
         r.render(0, 2)
-        _assert_same(r.read_accum(), want1_2, f"fresh frame {k} over NaN")
+        same(r.read_accum(), want1_2, f"fresh frame {k} over NaN")
     r.set_option(ptamd.PT_OPT_FRESH_BATCH0, 0)
     r.render(0, 2)
-    _assert_same(r.read_accum(), want1_2, "reference semantics after fresh frames")
+    same(r.read_accum(), want1_2, "reference semantics after fresh frames")
     nanbuf.fill_(float("nan"))   # written behind the library's back: bind again
     r.bind_accum(nanbuf.data_ptr(), W, H)
     r.set_option(ptamd.PT_OPT_FRESH_BATCH0, 1)
     r.render(0, 2)
-    _assert_same(r.read_accum(), want1_2, "fresh frame over a re-bound NaN buffer")
+    same(r.read_accum(), want1_2, "fresh frame over a re-bound NaN buffer")
     r.close()
 
 
@@ -296,7 +280,7 @@ def test_partition_sum_is_bit_exact():
             r.render(0, nb)
             part = r.read_accum()
             acc = (acc + part).astype(np.float32)
-        _assert_same(acc, want, f"sum over {nranks} ranks")
+        same(acc, want, f"sum over {nranks} ranks")
 
 
 def test_fresh_batch0_ignores_stale_accumulator():
@@ -307,10 +291,10 @@ def test_fresh_batch0_ignores_stale_accumulator():
     r.render(0, 3)          # leaves a finished frame in the buffer
     r.render(0, 4)          # restarts at batch 0 without clearing
     ref, _ = _oracle(v, i, n, 64, 40, nb=4)
-    _assert_same(r.read_accum(), ref, "fresh restart")
+    same(r.read_accum(), ref, "fresh restart")
     r.render(4, 2)          # continuing batches still read the accumulator
     ref, _ = _oracle(v, i, n, 64, 40, nb=6)
-    _assert_same(r.read_accum(), ref, "fresh + continue")
+    same(r.read_accum(), ref, "fresh + continue")
 
 
 @pytest.mark.parametrize("nranks", [2, 3, 8])
@@ -336,7 +320,7 @@ def test_tile_gather_assembles_frame(nranks):
         root.tiles_unpack(buf.data_ptr(), rank, frame.data_ptr())
         root.synchronize()
     ref, _ = _oracle(v, i, n, W, H, nb=8)
-    _assert_same(frame.cpu().numpy().reshape(-1), ref, f"gather over {nranks}")
+    same(frame.cpu().numpy().reshape(-1), ref, f"gather over {nranks}")
 
 
 @pytest.mark.parametrize("ntri,int_bits", [(1, False), (2, False), (1000, False), (20000, True), (40000, False)])
@@ -350,7 +334,7 @@ def test_random_triangles(ntri, int_bits):
     r.render(0, 2)
     gpu = r.read_accum()
     ref, _ = _oracle(v, i, n, 96, 64, nb=2, cam=cam, int_bits=int_bits)
-    _assert_same(gpu, ref, f"random {ntri}")
+    same(gpu, ref, f"random {ntri}")
 
 
 @pytest.mark.parametrize("lds", [0, 1])
@@ -368,7 +352,7 @@ def test_grid_ties_and_two_lights(lds):
     r.render(3, 2)
     gpu = r.read_accum()
     ref, _ = _oracle(v, i, n, 64, 64, first=3, nb=2, depth=3, sss=2, cam=cam, lights=lights)
-    _assert_same(gpu, ref, "grid")
+    same(gpu, ref, "grid")
 
 
 @pytest.mark.parametrize("lds", [0, 1])
@@ -380,7 +364,7 @@ def test_edge_params(lds):
         r.resize_and_clear(48, 40)
         r.render(0, 2)
         ref, _ = _oracle(v, i, n, 48, 40, nb=2, depth=depth, sss=sss, lights=lights)
-        _assert_same(r.read_accum(), ref, f"depth={depth} sss={sss} lights={lights.size // 16}")
+        same(r.read_accum(), ref, f"depth={depth} sss={sss} lights={lights.size // 16}")
 
 
 @pytest.mark.parametrize("lds", [0, 1])
@@ -393,7 +377,7 @@ def test_displaced_sphere_substitute(lds):
     r.resize_and_clear(80, 60)
     r.render(0, 2)
     ref, _ = _oracle(v, i, n, 80, 60, nb=2, cam=cam)
-    _assert_same(r.read_accum(), ref, "sphere")
+    same(r.read_accum(), ref, "sphere")
 
 
 def test_errors_are_reported():
@@ -432,7 +416,7 @@ def test_primary_culling_is_exact(cam, W, H):
         r.set_option(ptamd.PT_OPT_PRIMARY_CULL, cull)
         r.resize_and_clear(W, H)
         r.render(0, 4)
-        _assert_same(r.read_accum(), ref, f"cull={cull} cam {cam} {W}x{H}")
+        same(r.read_accum(), ref, f"cull={cull} cam {cam} {W}x{H}")
 
 
 def test_primary_culling_with_stale_accumulator():
@@ -451,10 +435,10 @@ def test_primary_culling_with_stale_accumulator():
         r.render(0, 2)
         r.set_camera(camB)
         r.render(2, 3)
-        _assert_same(r.read_accum(), ref, f"spl {spl} first>0 over stale")
+        same(r.read_accum(), ref, f"spl {spl} first>0 over stale")
         r.set_camera(camC)
         r.render(0, 2)
-        _assert_same(r.read_accum(), ref2, f"spl {spl} first=0 over stale")
+        same(r.read_accum(), ref2, f"spl {spl} first=0 over stale")
 
 
 def test_progressive_loop_camera_reset_and_async_readback():
@@ -478,12 +462,12 @@ def test_progressive_loop_camera_reset_and_async_readback():
     img2 = r.readback_end(t2)
     img1 = r.readback_end(t1)
     refA, _ = _oracle(v, i, n, W, H, first=0, nb=2, cam=camA)
-    _assert_same(img1, refA, "readback after camA 0-1")
+    same(img1, refA, "readback after camA 0-1")
     acc = refA.copy()
     acc, _ = _oracle(v, i, n, W, H, first=2, nb=1, cam=camA, accum=acc)
     acc, _ = _oracle(v, i, n, W, H, first=0, nb=4, cam=camB, accum=acc)
-    _assert_same(img2, acc, "camB 0-3 over camA image")
-    _assert_same(r.read_accum(), acc, "accumulator")
+    same(img2, acc, "camB 0-3 over camA image")
+    same(r.read_accum(), acc, "accumulator")
     with pytest.raises(ptamd.PTError):
         r.readback_end(t2)                        # already collected
 
@@ -538,7 +522,7 @@ def test_sparse_item_exchange_assembles_frame(nranks, cam, mode):
     rs[0].items_unpack_all(src.data_ptr(), src.shape[1], frame.data_ptr())
     rs[0].synchronize()
     ref, _ = _oracle(v, i, n, W, H, nb=8, cam=camera)
-    _assert_same(frame.cpu().numpy().reshape(-1), ref, f"sparse exchange over {nranks}")
+    same(frame.cpu().numpy().reshape(-1), ref, f"sparse exchange over {nranks}")
     if cam == 5:
         assert sum(counts) * per >= W * H
     else:
@@ -579,11 +563,11 @@ def test_render_packed_assembles_previous_frame(nranks, cam, kernel):
             rs[k].render_packed(8, src[1][k].data_ptr())
         rs[k].synchronize()
     ref, _ = _oracle(v, i, n, W, H, nb=8, cam=camera)
-    _assert_same(frame.cpu().numpy().reshape(-1), ref, f"frame 1 assembled in frame 2's launch, {nranks} ranks")
+    same(frame.cpu().numpy().reshape(-1), ref, f"frame 1 assembled in frame 2's launch, {nranks} ranks")
     frame2 = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda")
     rs[0].items_unpack_all(src[1].data_ptr(), slot, frame2.data_ptr())
     rs[0].synchronize()
-    _assert_same(frame2.cpu().numpy().reshape(-1), ref, "frame 2")
+    same(frame2.cpu().numpy().reshape(-1), ref, "frame 2")
     rs[0].resize_and_clear(W + 16, H)   # another item layout
     with pytest.raises(ptamd.PTError):
         rs[0].render_packed(8, src[0][0].data_ptr(), src[1].data_ptr(), slot, frame.data_ptr())
@@ -600,7 +584,7 @@ def test_wavefront_kernel_box(lds, spl):
     r.resize_and_clear(70, 45)
     r.render(1, 5)
     ref, _ = _oracle(v, i, n, 70, 45, first=1, nb=5)
-    _assert_same(r.read_accum(), ref, f"wavefront box lds={lds} spl={spl}")
+    same(r.read_accum(), ref, f"wavefront box lds={lds} spl={spl}")
 
 
 @pytest.mark.parametrize("case", range(6))
@@ -613,7 +597,7 @@ def test_wavefront_kernel_scenes(case):
     r.resize_and_clear(56, 40)
     r.render(0, 3)
     ref, _ = _oracle(v, i, n, 56, 40, nb=3, depth=depth, sss=sss, cam=cam, lights=lights)
-    _assert_same(r.read_accum(), ref, f"wavefront {name}")
+    same(r.read_accum(), ref, f"wavefront {name}")
 
 
 @pytest.mark.parametrize("paths", [1, 3000, 7000])
@@ -632,7 +616,7 @@ def test_wavefront_batch_chunks(paths):
     r.render(0, 3)
     r.set_camera(camB)
     r.render(3, 7)
-    _assert_same(r.read_accum(), ref, f"wavefront chunks of {paths} paths")
+    same(r.read_accum(), ref, f"wavefront chunks of {paths} paths")
 
 
 @pytest.mark.parametrize("cam", range(len(CULL_CAMS)))
@@ -651,7 +635,7 @@ def test_wavefront_culling_and_partition(cam):
         r.render(0, 4)
         got = r.read_accum().reshape(H, W, 4)
         own = ptamd.partition_owned(W, H, nranks, rank)
-        _assert_same(got[own].reshape(-1), ref[own].reshape(-1), f"wavefront cam {cam} rank {rank}/{nranks}")
+        same(got[own].reshape(-1), ref[own].reshape(-1), f"wavefront cam {cam} rank {rank}/{nranks}")
 
 
 def test_wavefront_rejects_stats_mode():
@@ -687,7 +671,7 @@ def test_shadow_skip_light_intensities(lds, kernel):
     nan_g, nan_r = np.isnan(gpu), np.isnan(ref)
     assert np.array_equal(nan_g, nan_r), f"NaN pattern differs in {np.count_nonzero(nan_g != nan_r)} floats"
     assert nan_r.any() and (~nan_r).any()
-    _assert_same(np.where(nan_g, 0, gpu).astype(np.float32), np.where(nan_r, 0, ref).astype(np.float32),
+    same(np.where(nan_g, 0, gpu).astype(np.float32), np.where(nan_r, 0, ref).astype(np.float32),
                  f"kernel {kernel} lds {lds}")
 
 
@@ -713,7 +697,7 @@ def test_launch_timing_sampling_and_span():
         assert t.size == timed and np.all(t > 0), (every, t)
         span, n_cov = r.launch_span_ms()
         assert n_cov == covered and span >= t.max() > 0, (every, span, n_cov)
-        _assert_same(r.read_accum(), want, f"timing every {every}")
+        same(r.read_accum(), want, f"timing every {every}")
     r.set_option(ptamd.PT_OPT_LAUNCH_TIMING, 0)
     r.reset_launch_times()
     r.render(0, 2)
@@ -756,7 +740,7 @@ def test_render_packed_on_alternating_streams(kernel):
     torch.cuda.synchronize()
     ref, _ = _oracle(v, i, n, W, H, nb=4, cam=CULL_CAMS[1])
     for k in range(4):
-        _assert_same(frames[k].cpu().numpy().reshape(-1), ref, f"kernel {kernel} frame {k}")
+        same(frames[k].cpu().numpy().reshape(-1), ref, f"kernel {kernel} frame {k}")
 
 
 # ---- slotted partition (pt_set_partition_slots) -----------------------------
@@ -782,7 +766,7 @@ def test_partition_slots_sum_and_sparse_exchange(slots):
         owned = ptamd.partition_owned(W, H, N, rank, slots).reshape(-1)
         assert r.tiles_owned() * 256 >= np.count_nonzero(owned)
         rs.append(r)
-    _assert_same(acc, want, f"sum over slots {slots}")
+    same(acc, want, f"sum over slots {slots}")
     # dense tiles: pack every rank's owned tiles, unpack them all on rank 0
     frame = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda")
     for k, r in enumerate(rs):
@@ -791,7 +775,7 @@ def test_partition_slots_sum_and_sparse_exchange(slots):
         r.synchronize()
         rs[0].tiles_unpack(buf.data_ptr(), k, frame.data_ptr())
         rs[0].synchronize()
-    _assert_same(frame.cpu().numpy().reshape(-1), want, f"tile gather, slots {slots}")
+    same(frame.cpu().numpy().reshape(-1), want, f"tile gather, slots {slots}")
     # sparse: render_packed on every rank, assembly on the root
     per = rs[0].items_live(0)[1]
     counts = [rs[0].items_live(k)[0] for k in range(N)]
@@ -804,7 +788,7 @@ def test_partition_slots_sum_and_sparse_exchange(slots):
     frame2 = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda")
     rs[0].items_unpack_all(src.data_ptr(), slot, frame2.data_ptr())
     rs[0].synchronize()
-    _assert_same(frame2.cpu().numpy().reshape(-1), want, f"sparse exchange, slots {slots}")
+    same(frame2.cpu().numpy().reshape(-1), want, f"sparse exchange, slots {slots}")
     for bad in ([0] + slots[1:], [65] + slots[1:]):   # 1..64 slots per rank
         with pytest.raises(ptamd.PTError):
             rs[0].set_partition(N, 0, bad)
@@ -830,7 +814,7 @@ def test_reslotting_one_renderer_keeps_item_lists_right():
             r.resize_and_clear(W, H)
             r.render(0, nb)
             acc = (acc + r.read_accum()).astype(np.float32)
-        _assert_same(acc, want, f"sum after re-slotting to {slots}")
+        same(acc, want, f"sum after re-slotting to {slots}")
         per = rs[0].items_live(0)[1]
         slot = max(max(rs[0].items_live(k)[0] for k in range(3)) * per * 4, 4)
         recv = torch.zeros((3, slot), dtype=torch.float32, device="cuda")
@@ -840,7 +824,7 @@ def test_reslotting_one_renderer_keeps_item_lists_right():
         frame = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda")
         rs[0].items_unpack_all(recv.data_ptr(), slot, frame.data_ptr())
         rs[0].synchronize()
-        _assert_same(frame.cpu().numpy().reshape(-1), want, f"sparse exchange after re-slotting to {slots}")
+        same(frame.cpu().numpy().reshape(-1), want, f"sparse exchange after re-slotting to {slots}")
 
 
 @pytest.mark.parametrize("scene", ["box", "sphere"])
@@ -871,7 +855,7 @@ def test_count_traced_mode(scene):
         r.resize_and_clear(W, H)
         r.reset_stats()
         r.render(0, nb)
-        _assert_same(r.read_accum(), ref, f"{scene} {name} counting")
+        same(r.read_accum(), ref, f"{scene} {name} counting")
         assert r.last_kernel() == kernel
         counts[name] = r.traced()
     first = next(iter(counts.values()))
@@ -902,7 +886,7 @@ def test_count_traced_mode(scene):
     r.reset_stats()
     r.render(0, nb)
     assert r.traced()["primaries"] == W * H * nb
-    _assert_same(r.read_accum(), ref, f"{scene} counting, culling off")
+    same(r.read_accum(), ref, f"{scene} counting, culling off")
 
 
 # ---- culled wide walk (PT_OPT_WIDE, wide_walk.h) ---------------------------
@@ -952,7 +936,7 @@ def test_wide_walk_matches_oracle(case, mode, build, node):
     r.resize_and_clear(80, 52)
     r.render(1, 4)
     ref, _ = _oracle(v, i, n, 80, 52, first=1, nb=4, cam=cam, lights=lights, int_bits=int_bits)
-    _assert_same(r.read_accum(), ref, f"wide walk {case} mode {mode}")
+    same(r.read_accum(), ref, f"wide walk {case} mode {mode}")
 
 
 def test_wide_walk_refused_tree_keeps_exact_walk():
@@ -971,7 +955,7 @@ def test_wide_walk_refused_tree_keeps_exact_walk():
     r.resize_and_clear(48, 40)
     r.render(0, 2)
     ref, _ = _oracle(v, i, n, 48, 40, nb=2, cam=scenes.camera((0.0, 0.5, 3.0)))
-    _assert_same(r.read_accum(), ref, "refused wide tree")
+    same(r.read_accum(), ref, "refused wide tree")
 
 
 @pytest.mark.parametrize("tail", [1 << 30, 3000, 1])
@@ -999,7 +983,7 @@ def test_wavefront_tail_kernel_matches_oracle(case, node, mode, tail):
     r.resize_and_clear(W, H)
     r.render(0, 2)
     r.render(2, 3)
-    _assert_same(r.read_accum(), ref, f"tail kernel {case} node {node} mode {mode} tail {tail}")
+    same(r.read_accum(), ref, f"tail kernel {case} node {node} mode {mode} tail {tail}")
 
 
 @pytest.mark.parametrize("case", ["sphere", "cloud_int_bits"])
@@ -1021,13 +1005,13 @@ def test_wavefront_tail_kernel_counts_and_two_streams(case):
         r.reset_stats()
         r.resize_and_clear(W, H)
         r.render(0, nb)
-        _assert_same(r.read_accum(), ref, f"counting tail {tail} {case}")
+        same(r.read_accum(), ref, f"counting tail {tail} {case}")
         got[tail] = r.traced()
         r.set_option(ptamd.PT_OPT_COUNT_TRACED, 0)
         r.set_option(ptamd.PT_OPT_WF_STREAMS, 2)
         r.resize_and_clear(W, H)
         r.render(0, nb)
-        _assert_same(r.read_accum(), ref, f"two streams tail {tail} {case}")
+        same(r.read_accum(), ref, f"two streams tail {tail} {case}")
     for tail in (1 << 30, 5000):
         assert got[tail]["closest_walks"] == got[0]["closest_walks"], (tail, got)
         assert got[tail]["primaries"] == got[0]["primaries"], (tail, got)
@@ -1049,7 +1033,7 @@ def test_wavefront_two_streams(case):
     r.resize_and_clear(W, H)
     r.render(0, 2)
     r.render(2, 3)
-    _assert_same(r.read_accum(), ref, f"two streams {case}")
+    same(r.read_accum(), ref, f"two streams {case}")
 
 
 @pytest.mark.parametrize("case", ["sphere", "cloud_int_bits"])
@@ -1075,7 +1059,7 @@ def test_wide_walk_partitioned_ranks_sum_to_oracle(case):
             r.resize_and_clear(W, H)
             r.render(0, nb)
             acc = (acc + r.read_accum()).astype(np.float32)
-        _assert_same(acc, ref.reshape(-1), f"wide walk {case}, {nranks} ranks, slots {slots}")
+        same(acc, ref.reshape(-1), f"wide walk {case}, {nranks} ranks, slots {slots}")
 
 
 def test_wide_walk_reupload_deeper_scene():
@@ -1101,7 +1085,7 @@ def test_wide_walk_reupload_deeper_scene():
         r.resize_and_clear(72, 56)
         r.render(0, 2)
         ref, _ = _oracle(v, i, n, 72, 56, nb=2, cam=cam)
-        _assert_same(r.read_accum(), ref, f"re-upload, stack bound {info[1]}")
+        same(r.read_accum(), ref, f"re-upload, stack bound {info[1]}")
     assert depths[1] > depths[0], depths
 
 
@@ -1122,7 +1106,7 @@ def test_wide_walk_fused_shadow_rays(case, fuse):
     r.resize_and_clear(W, H)
     r.render(0, 1)
     r.render(1, 3)
-    _assert_same(r.read_accum(), ref, f"fuse {fuse} {case}")
+    same(r.read_accum(), ref, f"fuse {fuse} {case}")
 
 
 @pytest.mark.parametrize("first,nb", [(0, 16), (3, 6), (7, 9), (1000, 3)])
@@ -1146,7 +1130,7 @@ def test_one_lane_fold_over_stale_accumulator(first, nb):
     r.render(first, nb)
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, W, H, first_batch=first,
                       n_batches=nb, accum=stale.copy())
-    _assert_same(r.read_accum(), ref, f"one-lane fold from batch {first}, {nb} batches")
+    same(r.read_accum(), ref, f"one-lane fold from batch {first}, {nb} batches")
 
 
 def test_wavefront_grid_fraction_is_output_invariant():
@@ -1169,7 +1153,7 @@ def test_wavefront_grid_fraction_is_output_invariant():
         assert r.last_kernel() == ptamd.KERNEL_WAVEFRONT
         frames.append(r.read_accum())
     for (g, rf), f in zip(cases[1:], frames[1:]):
-        _assert_same(f, frames[0], f"grid {g} %, refill at {rf} idle lanes")
+        same(f, frames[0], f"grid {g} %, refill at {rf} idle lanes")
     with pytest.raises(ptamd.PTError):
         r.set_option(ptamd.PT_OPT_WF_GRID, 0)
     with pytest.raises(ptamd.PTError):

@@ -14,6 +14,7 @@ import pytest
 import plan_cases
 import ptamd
 import scenes
+from support import built, renderer, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -23,23 +24,15 @@ GPU_ROWS = [r for r in plan_cases.ROWS if r["gpu"]]
 @functools.lru_cache(maxsize=None)
 def _scene(name):
     if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        s = ptamd.Scene.from_arrays(*scenes.displaced_sphere(int(name.split(":")[1]))).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
+        return scene("box")
+    return built(*scenes.displaced_sphere(int(name.split(":")[1])))
 
 
 def _renderer(r):
     v, i, n = _scene(r["gpu"]["scene"])
     assert i.size // 3 == r["facts"]["tris"], "the row's facts are the scene's"
-    rd = ptamd.Renderer(0)
-    for k, val in r["opts"].items():
-        rd.set_option(getattr(ptamd, "PT_OPT_" + k), val)
-    rd.upload_scene(v, i, n)
-    rd.upload_lights(scenes.REFERENCE_LIGHT)
-    rd.set_camera(scenes.camera((0.0, 0.5, 3.0)) if r["gpu"]["scene"] != "box" else scenes.DEFAULT_CAMERA)
-    rd.set_params(4, 3)
+    rd = renderer((v, i, n), scenes.camera((0.0, 0.5, 3.0)) if r["gpu"]["scene"] != "box" else scenes.DEFAULT_CAMERA,
+                  options=[(getattr(ptamd, "PT_OPT_" + k), val) for k, val in r["opts"].items()])
     if r["stats"]:
         rd.set_stats_mode(True)
     if r["ranks"] > 1:

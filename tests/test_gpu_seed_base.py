@@ -12,6 +12,7 @@ import denoise_var_ref as V
 import oracle_lib as O
 import ptamd
 import scenes
+from support import bits, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -21,37 +22,9 @@ FRAMES = {"box": (scenes.DEFAULT_CAMERA, 64, 48), "sphere": (CAM_324, 67, 45)}  
 LANES, MIX = ptamd.PT_OPT_SAMPLE_LANES, ptamd.PT_OPT_MIXED_LANES
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = np.argwhere(_bits(got).reshape(-1) != _bits(want).reshape(-1))
-    assert bad.size == 0, f"{what}: {len(bad)} of {np.size(got)} floats differ, first at {bad[0]}"
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        s = ptamd.Scene.from_arrays(*scenes.displaced_sphere(subdiv=3)).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
-
-
 def _renderer(name, options=(), moments=0):
     cam, W, H = FRAMES[name]
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_MOMENTS, moments)
-    for k, v in options:
-        r.set_option(k, v)
-    r.upload_scene(*_scene(name))
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(cam)
-    r.set_params(4, 3)
-    r.resize_and_clear(W, H)
-    return r
+    return renderer(scene(name), cam, size=(W, H), options=[(ptamd.PT_OPT_MOMENTS, moments)] + list(options))
 
 
 def _frame(r, base, n):
@@ -64,13 +37,13 @@ def _frame(r, base, n):
 @pytest.mark.parametrize("name", ["box", "sphere"])
 def test_one_sample_at_base_b_is_the_oracles_batch_b(name):
     cam, W, H = FRAMES[name]
-    v, i, n = _scene(name)
+    v, i, n = scene(name)
     r = _renderer(name)
     for B in (0, 1, 3, 7):
         want, _ = O.render(v, i, n.reshape(-1), cam, scenes.REFERENCE_LIGHT, W, H, first_batch=B, n_batches=1)
         got = _frame(r, B, 1)
         # the oracle's last operation on a zero image: (0 * B + c) / float(B + 1)
-        _same(got / F(B + 1), want, f"{name}: base {B}")
+        same(got / F(B + 1), want, f"{name}: base {B}")
     assert ptamd.lib().pt_set_option(r._c, ptamd.PT_OPT_SEED_BASE, -1) == -1   # PT_ERR_INVALID
     r.set_option(ptamd.PT_OPT_SEED_BASE, 2**31 - 1)
 
@@ -86,11 +59,11 @@ def test_fused_launch_folds_like_one_sample_renders(name):
         acc = ((acc * F(j) + c) / F(j + 1)).astype(F)
         mom = V.fold_moments(mom, c, j)
     got = _frame(r, 5, 4)
-    _same(got, acc, f"{name}: render(0, 4) at base 5")
+    same(got, acc, f"{name}: render(0, 4) at base 5")
     m, n = r.read_moments()
     assert n == 4
-    _same(m, mom, f"{name}: moments at base 5")
-    assert not np.array_equal(_bits(got), _bits(_frame(r, 0, 4)))             # another base, another frame
+    same(m, mom, f"{name}: moments at base 5")
+    assert not np.array_equal(bits(got), bits(_frame(r, 0, 4)))             # another base, another frame
 
 
 BOX_PATHS = {
@@ -129,8 +102,8 @@ def test_every_kernel_path_gives_the_same_frame(name, path):
     want = _reference_frames(name)
     r = _renderer(name, (BOX_PATHS if name == "box" else SPHERE_PATHS)[path])
     for B in (5, 2**31 - 1):
-        _same(_frame(r, B, 4), want[B], f"{name}, {path}: base {B}")
-    assert not np.array_equal(_bits(want[5]), _bits(want[2**31 - 1]))
+        same(_frame(r, B, 4), want[B], f"{name}, {path}: base {B}")
+    assert not np.array_equal(bits(want[5]), bits(want[2**31 - 1]))
 
 
 @pytest.mark.parametrize("mode", ["stats", "counting", "group"])
@@ -143,7 +116,7 @@ def test_stats_counting_and_group_members_follow(name, mode):
     r = ptamd.Renderer(devices=[0, 0]) if mode == "group" else ptamd.Renderer(0)
     if mode == "counting":
         r.set_option(ptamd.PT_OPT_COUNT_TRACED, 1)
-    r.upload_scene(*_scene(name))
+    r.upload_scene(*scene(name))
     r.upload_lights(scenes.REFERENCE_LIGHT)
     r.set_camera(cam)
     r.set_params(4, 3)
@@ -151,7 +124,7 @@ def test_stats_counting_and_group_members_follow(name, mode):
     if mode == "stats":
         r.set_stats_mode(True)
     for B in (5, 2**31 - 1):
-        _same(_frame(r, B, 4), want[B], f"{name}, {mode}: base {B}")
+        same(_frame(r, B, 4), want[B], f"{name}, {mode}: base {B}")
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -163,9 +136,9 @@ def test_dispatch_and_progressive_follow(name):
     r.clear()
     for b in range(4):
         r.dispatch(b)
-    _same(r.read_accum(), want, f"{name}: dispatch")
+    same(r.read_accum(), want, f"{name}: dispatch")
     r.clear()
     assert r.progressive_camera(cam)
     assert r.progressive_advance(3) == (0, 3)
     assert r.progressive_advance(8, limit=4) == (3, 1)
-    _same(r.read_accum(), want, f"{name}: progressive")
+    same(r.read_accum(), want, f"{name}: progressive")

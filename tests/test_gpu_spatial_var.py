@@ -17,24 +17,15 @@ import torch
 import ptamd
 import scenes
 import spatial_var_ref as S
+from support import PKG, bits, dev, mse, read_device, read_pfm, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PKG = os.path.dirname(os.path.abspath(ptamd.__file__))
 PT_OK, PT_ERR_INVALID, PT_ERR_UNSUPPORTED = 0, -1, -5
 START = {"box": (0.0, 0.0, 5.0), "sphere": (3.0, 2.0, 4.0)}
 SIZE = {"box": (64, 48), "sphere": (67, 45)}                  # the frame sizes of test_gpu_temporal.py
 SEED_BASE, REF_SEED_BASE, REF_SPP = 1000, 1000 + (1 << 20), 256
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = np.argwhere(_bits(got).reshape(-1) != _bits(want).reshape(-1))
-    assert bad.size == 0, f"{what}: {len(bad)} of {np.size(got)} floats differ, first at {bad[0]}"
 
 
 def _orbit(name, degrees):
@@ -43,46 +34,9 @@ def _orbit(name, degrees):
     return scenes.camera((x * np.cos(a) + z * np.sin(a), y, z * np.cos(a) - x * np.sin(a)))
 
 
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        s = ptamd.Scene.from_arrays(*scenes.displaced_sphere(subdiv=3)).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
-
-
 def _renderer(name, moments=1, seed_base=SEED_BASE, size=None):
-    w, h = size or SIZE[name]
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_MOMENTS, moments)
-    r.set_option(ptamd.PT_OPT_SEED_BASE, seed_base)
-    r.upload_scene(*_scene(name))
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(_orbit(name, 0))
-    r.set_params(4, 3)
-    r.resize_and_clear(w, h)
-    return r
-
-
-@functools.lru_cache(maxsize=None)
-def _hip():
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    return ctypes.CDLL(path)
-
-
-def _read_device(r, ptr, shape):
-    """A library-owned float image, copied behind the context's work."""
-    r.synchronize()
-    out = np.empty(shape, F)
-    assert _hip().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(out.nbytes), 2) == 0
-    return out
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, F)).cuda()
+    return renderer(scene(name), _orbit(name, 0), size=size or SIZE[name],
+                    options=[(ptamd.PT_OPT_MOMENTS, moments), (ptamd.PT_OPT_SEED_BASE, seed_base)])
 
 
 def _inputs():
@@ -97,7 +51,7 @@ def test_device_matches_host_and_restatement(radius):
     r = ptamd.Renderer(0)
     for W, H, tag, d in _inputs():
         keys = ("moments", "length", "variance", "guide")
-        ins = [_dev(d[k]) for k in keys]
+        ins = [dev(d[k]) for k in keys]
         for params in (None if radius == 1 else (2, radius, 1.0, 1.0), (4, radius, 0.5, 0.25), (65536, radius, 0.25, 1.0),
                        (1, radius, 1.0, 1.0)):
             out = torch.full((H, W), -7.0, dtype=torch.float32, device="cuda")        # the sentinel
@@ -107,17 +61,12 @@ def test_device_matches_host_and_restatement(radius):
             got = out.cpu().numpy()
             host = ptamd.spatial_variance_host(*[d[k] for k in keys], W, H, params)
             ref = S.spatial_variance(*[d[k] for k in keys], W, H, S.DEFAULTS if params is None else params)
-            _same(got, host, f"{W}x{H} {tag} {params}: device against host")
-            _same(got, ref, f"{W}x{H} {tag} {params}: device against the restatement")
+            same(got, host, f"{W}x{H} {tag} {params}: device against host")
+            same(got, ref, f"{W}x{H} {tag} {params}: device against the restatement")
             if params is not None and params[0] == 1:
-                _same(got, d["variance"], "below 1: the variance itself")
+                same(got, d["variance"], "below 1: the variance itself")
         for t, k in zip(ins, keys):
-            _same(t.cpu().numpy(), d[k], f"input {k} after the calls")
-
-
-def _mse(a, b, mask):
-    d = a[..., :3].astype(np.float64)[mask] - b[..., :3].astype(np.float64)[mask]
-    return float(np.mean(d * d))
+            same(t.cpu().numpy(), d[k], f"input {k} after the calls")
 
 
 @functools.lru_cache(maxsize=None)
@@ -136,7 +85,7 @@ def _capture(r, name, degrees, n):
     and what the host makes of the same planes."""
     W, H = SIZE[name]
     c, m, l = r.read_temporal()
-    v = _read_device(r, r.temporal_ptr(3), (H, W))
+    v = read_device(r, r.temporal_ptr(3), (H, W))
     guide = r.read_guide()
     raw = r.read_accum().reshape(H, W, 4)
     plain = r.temporal_denoise()
@@ -148,7 +97,7 @@ def _capture(r, name, degrees, n):
     torch.cuda.synchronize()
     assert r.temporal_denoise_spatial(None, None, dst.data_ptr()) is None
     r.synchronize()
-    after = r.read_temporal() + (_read_device(r, r.temporal_ptr(3), (H, W)),)
+    after = r.read_temporal() + (read_device(r, r.temporal_ptr(3), (H, W)),)
     return {"c": c, "m": m, "l": l, "v": v, "guide": guide, "raw": raw, "plain": plain, "spatial": spatial,
             "spatial_dst": dst.cpu().numpy(), "after": after, "degrees": degrees, "n": n}
 
@@ -178,15 +127,15 @@ def test_temporal_denoise_spatial_equals_the_host(name, case):
     assert np.any(s["l"] == 1)
     assert np.all(s["l"] == 1) == (case == "first")
     plane = ptamd.spatial_variance_host(s["m"], s["l"], s["v"], s["guide"], W, H)
-    _same(plane, S.spatial_variance(s["m"], s["l"], s["v"], s["guide"], W, H), f"{name} {case}: host estimate")
+    same(plane, S.spatial_variance(s["m"], s["l"], s["v"], s["guide"], W, H), f"{name} {case}: host estimate")
     assert np.any(plane[s["l"] == 1] > 0) and np.all(s["v"][s["l"] == 1] == 0)
     want = ptamd.denoise_var_plane_host(s["c"], plane, s["guide"], W, H)
     for staged in (0, 1):
-        _same(s["spatial"][staged], want, f"{name} {case}: staged {staged}")
-    _same(s["spatial_dst"], want, f"{name} {case}: caller-owned destination")
+        same(s["spatial"][staged], want, f"{name} {case}: staged {staged}")
+    same(s["spatial_dst"], want, f"{name} {case}: caller-owned destination")
     for a, b, what in zip(s["after"], (s["c"], s["m"], s["l"], s["v"]), ("colour", "moments", "length", "variance")):
-        _same(a, b, f"{name} {case}: the temporal {what} after the calls")
-    assert np.any(_bits(s["spatial"][1]) != _bits(s["plain"]))             # the estimate changes the image
+        same(a, b, f"{name} {case}: the temporal {what} after the calls")
+    assert np.any(bits(s["spatial"][1]) != bits(s["plain"]))             # the estimate changes the image
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -197,9 +146,9 @@ def test_two_samples_and_below_two_is_temporal_denoise(name):
         r.temporal_advance(_orbit(name, degrees), 2)
         assert r.read_temporal()[2].min() == 2
         for filt in (None, (2, 0.75, 0.5, 0.25)):
-            _same(r.temporal_denoise_spatial(filt, (2, 3, 0.5, 0.5)), r.temporal_denoise(filt), f"{name} {degrees} {filt}")
+            same(r.temporal_denoise_spatial(filt, (2, 3, 0.5, 0.5)), r.temporal_denoise(filt), f"{name} {degrees} {filt}")
     # and with a threshold above 2 it is not
-    assert np.any(_bits(r.temporal_denoise_spatial(None, (3, 1, 1.0, 1.0))) != _bits(r.temporal_denoise()))
+    assert np.any(bits(r.temporal_denoise_spatial(None, (3, 1, 1.0, 1.0))) != bits(r.temporal_denoise()))
 
 
 def test_error_paths():
@@ -251,14 +200,6 @@ def test_error_paths():
     assert L.pt_temporal_denoise_spatial(g._c, None, None, None) == PT_ERR_UNSUPPORTED
 
 
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = map(int, f.readline().split())
-        assert float(f.readline()) < 0   # little-endian
-        return np.fromfile(f, "<f4").reshape(h, w, 3)
-
-
 def test_pt_render_temporal_spatial_flag(tmp_path):
     W, H, spp, K = 64, 48, 1, 3
     exe = os.path.join(PKG, "pt_render")
@@ -277,8 +218,8 @@ def test_pt_render_temporal_spatial_flag(tmp_path):
                 cam[o], cam[o + 2] = x * c2 + z * s2, z * c2 - x * s2
         r.temporal_advance(cam, spp)
     want = r.temporal_denoise_spatial()
-    _same(_read_pfm(out), want[..., :3], "pt_render -temporal 3 -spp 1 -temporal-spatial")
-    assert np.any(_bits(want) != _bits(r.temporal_denoise()))
+    same(read_pfm(out), want[..., :3], "pt_render -temporal 3 -spp 1 -temporal-spatial")
+    assert np.any(bits(want) != bits(r.temporal_denoise()))
     res = subprocess.run([exe, scenes.BOX_OBJ, "-temporal-spatial"], capture_output=True, text=True)   # needs -temporal K
     assert res.returncode == 2
 
@@ -304,7 +245,7 @@ def test_quality(name):
         assert np.count_nonzero(mask) > 50
         for img in (s["plain"], s["spatial"][1]):
             assert np.all(np.isfinite(img))
-        e = tuple(_mse(x, ref, mask) for x in (s["raw"], s["plain"], s["spatial"][1]))
+        e = tuple(mse(x, ref, mask) for x in (s["raw"], s["plain"], s["spatial"][1]))
         err[case] = e
         print(f"spatial variance quality {name} {case}: {np.count_nonzero(mask)} pixels "
               f"({np.count_nonzero(hit & (s['l'] == 1))} of {np.count_nonzero(hit)} first-hit pixels short), mse raw = "

@@ -4,59 +4,28 @@ Every comparison is bitwise: each frame with the sweep on and with it off
 equals the oracle's, hence each other.  pt_sweep_info tells which walk a
 launch takes, so a case cannot pass by silently running the threaded walk.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import ptamd
 import scenes
+from support import TWO_LIGHTS, lit_pixels, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
-TWO_LIGHTS = np.concatenate([scenes.REFERENCE_LIGHT,
-                             ptamd.pack_light([0.5, 0.5, 1.5], [0, 0, -1], [2, 4, 8], [0.5, 1.0])])
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        kind, n = name.split(":")
-        s = ptamd.Scene.from_arrays(*(scenes.grid_mesh(int(n)) if kind == "grid"
-                                      else scenes.random_triangles(int(n)))).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
-
-
-def _same(gpu, ref, what):
-    assert gpu.shape == ref.shape
-    if not np.array_equal(gpu.view(np.uint32), ref.view(np.uint32)):
-        bad = np.flatnonzero(gpu.view(np.uint32) != ref.view(np.uint32))
-        raise AssertionError(f"{what}: {bad.size} of {gpu.size} floats differ; first at pixel {bad[0] // 4} "
-                             f"gpu={gpu[bad[0]]} ref={ref[bad[0]]}")
-
 
 def _renderer(name, cam, lights, depth, sss, sweep):
-    v, i, n = _scene(name)
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_SMALL_SWEEP, sweep)
-    r.upload_scene(v, i, n)
-    r.upload_lights(lights)
-    r.set_camera(cam)
-    r.set_params(depth, sss)
-    return r
+    return renderer(scene(name), cam, lights, depth, sss, options=[(ptamd.PT_OPT_SMALL_SWEEP, sweep)])
 
 
 def _both(name, cam, lights, W, H, first, nb, depth, sss, in_force=True, lanes=None):
     """Renders with the sweep on and off, checks pt_sweep_info and both frames
     against the oracle."""
-    v, i, n = _scene(name)
+    v, i, n = scene(name)
     ref, _ = O.render(v, i, n.reshape(-1), cam, lights, W, H, first_batch=first, n_batches=nb, max_depth=depth,
                       sss_bounces=sss)
-    assert np.count_nonzero(np.any(ref.reshape(-1, 4)[:, :3] != 0, axis=1)) >= 20, "the frame shows the scene lit"
+    assert lit_pixels(ref) >= 20, "the frame shows the scene lit"
     for sweep in (1, 0):
         r = _renderer(name, cam, lights, depth, sss, sweep)
         if lanes:
@@ -68,7 +37,7 @@ def _both(name, cam, lights, W, H, first, nb, depth, sss, in_force=True, lanes=N
             assert (boxes, leaves) == (0, 0)
         r.resize_and_clear(W, H)
         r.render(first, nb)
-        _same(r.read_accum(), ref, f"{name} sweep={sweep} lanes={lanes}")
+        same(r.read_accum(), ref, f"{name} sweep={sweep} lanes={lanes}")
         r.close()
 
 
@@ -84,7 +53,7 @@ def test_grid_two_lights(n):
 
 
 def _facing_light(name):
-    v, i, _ = _scene(name)
+    v, i, _ = scene(name)
     p = v.reshape(-1, 3)[i.reshape(-1, 3)].astype(np.float64)
     nrm = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
     to_light = scenes.REFERENCE_LIGHT[0:3] - p.mean(1)
@@ -98,7 +67,7 @@ def _aimed(name, tri):
     light, looking at its centroid through a 1 degree field of view: the
     generator's triangles are 0.02 across and fill a good part of such a
     frame."""
-    v, i, _ = _scene(name)
+    v, i, _ = scene(name)
     p = v.reshape(-1, 3)[i.reshape(-1, 3)[tri]].astype(np.float64)
     c = p.mean(0)
     d = np.cross(p[1] - p[0], p[2] - p[0])
@@ -138,7 +107,7 @@ def test_default_takes_the_sweep_up_to_its_measured_bound(name, boxes):
     distinct boxes; 21 (grid_mesh(3), where the two walks measured within each
     other's scatter) and 31 (16 random triangles, grid_mesh(4), where the
     threaded walk measured faster) keep it (profiles/sweep/sweep_sizes.log)."""
-    v, i, n = _scene(name)
+    v, i, n = scene(name)
     r = ptamd.Renderer(0)
     r.upload_scene(v, i, n)
     assert r.sweep_info() == (boxes, i.size // 3 if boxes else 0)
@@ -152,7 +121,7 @@ def test_default_takes_the_sweep_up_to_its_measured_bound(name, boxes):
 def test_count_traced_keeps_the_threaded_walk():
     """The counting kernels run the threaded walk whatever the sweep option:
     same image bit for bit, same counts."""
-    v, i, n = _scene("box")
+    v, i, n = scene("box")
     ref, _ = O.render(v, i, n.reshape(-1), scenes.DEFAULT_CAMERA, scenes.REFERENCE_LIGHT, 64, 48, first_batch=2,
                       n_batches=3)
     counts = []
@@ -162,7 +131,7 @@ def test_count_traced_keeps_the_threaded_walk():
         r.resize_and_clear(64, 48)
         r.reset_stats()
         r.render(2, 3)
-        _same(r.read_accum(), ref, f"count_traced sweep={sweep}")
+        same(r.read_accum(), ref, f"count_traced sweep={sweep}")
         counts.append(r.traced())
         r.close()
     assert counts[0] == counts[1]

@@ -4,16 +4,13 @@ forced on and off as in test_gpu_sweep.py.  One kernel runs every table, so
 the cases span them: general and flat boxes in one table, the 63 boxes and
 leaf bit 31 of 32 random triangles, quads at three depths under two lights.
 """
-import functools
-
 import numpy as np
 import pytest
 
-import oracle_lib as O
 import ptamd
 import scenes
-import test_sweep_fold
-from test_gpu_sweep import TWO_LIGHTS, _same
+from support import TWO_LIGHTS, lit_pixels, oracle_frame, renderer, same, scene
+from sweep_support import visit_order
 
 pytestmark = pytest.mark.gpu
 
@@ -21,44 +18,27 @@ pytestmark = pytest.mark.gpu
 TILTED = np.float32([[1.2, -0.9, 0.5], [1.4, 0.8, 0.8], [2.6, -0.3, -0.4]])
 
 
-def _arrays(scene):
-    v, i, n, _, _ = scene.build_bvh().arrays()
-    return v, i, n
+def _box_and_tilted():
+    v, i, _ = scene("box")
+    nv = v.size // 3
+    return (np.concatenate([v.reshape(-1), TILTED.reshape(-1)]).astype(np.float32),
+            np.concatenate([i.reshape(-1), [nv, nv + 1, nv + 2]]).astype(np.uint32))
 
 
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        return _arrays(ptamd.Scene.load_obj(scenes.BOX_OBJ))
-    if name == "box+tilted":
-        v, i, _ = _scene("box")
-        nv = v.size // 3
-        return _arrays(ptamd.Scene.from_arrays(np.concatenate([v.reshape(-1), TILTED.reshape(-1)]).astype(np.float32),
-                                               np.concatenate([i.reshape(-1), [nv, nv + 1, nv + 2]]).astype(np.uint32)))
-    kind, n = name.split(":")
-    return _arrays(ptamd.Scene.from_arrays(*(scenes.grid_mesh(int(n)) if kind == "grid"
-                                             else scenes.random_triangles(int(n)))))
+MAKERS = {"box+tilted": _box_and_tilted}
 
 
 def _oracle(name, cam, lights, W, H, first, nb, depth, sss):
-    v, i, n = _scene(name)
-    ref, _ = O.render(v, i, n.reshape(-1), cam, lights, W, H, first_batch=first, n_batches=nb, max_depth=depth,
-                      sss_bounces=sss)
-    return ref
+    return oracle_frame(scene(name, MAKERS), cam, lights, W, H, first, nb, depth, sss)
 
 
 def _both(name, cam, lights, W, H, first, nb, depth, sss):
     """Sweep on (in force, by pt_sweep_info) and off: both frames equal the oracle's."""
-    v, i, n = _scene(name)
+    v, i, n = scene(name, MAKERS)
     ref = _oracle(name, cam, lights, W, H, first, nb, depth, sss)
-    assert np.count_nonzero(np.any(ref.reshape(-1, 4)[:, :3] != 0, axis=1)) >= 20, "the frame shows the scene lit"
+    assert lit_pixels(ref) >= 20, "the frame shows the scene lit"
     for sweep in (1, 0):
-        r = ptamd.Renderer(0)
-        r.set_option(ptamd.PT_OPT_SMALL_SWEEP, sweep)
-        r.upload_scene(v, i, n)
-        r.upload_lights(lights)
-        r.set_camera(cam)
-        r.set_params(depth, sss)
+        r = renderer((v, i, n), cam, lights, depth, sss, options=[(ptamd.PT_OPT_SMALL_SWEEP, sweep)])
         boxes, leaves = r.sweep_info()
         if sweep:
             assert leaves == i.size // 3 and 1 <= boxes <= 2 * leaves - 1
@@ -66,7 +46,7 @@ def _both(name, cam, lights, W, H, first, nb, depth, sss):
             assert (boxes, leaves) == (0, 0)
         r.resize_and_clear(W, H)
         r.render(first, nb)
-        _same(r.read_accum(), ref, f"{name} sweep={sweep}")
+        same(r.read_accum(), ref, f"{name} sweep={sweep}")
         r.close()
     return ref
 
@@ -74,7 +54,7 @@ def _both(name, cam, lights, W, H, first, nb, depth, sss):
 def test_box_and_a_tilted_triangle():
     """13 triangles: the box's flat face boxes and the tilted triangle's
     general one (and the root's) in one table."""
-    v, i, n = _scene("box+tilted")
+    v, i, n = scene("box+tilted", MAKERS)
     assert i.size // 3 == 13
     nd = n.reshape(-1, 8)
     flat = (nd[:, 0:3] == nd[:, 4:7]).any(1)
@@ -90,7 +70,7 @@ def _aimed_and_lit(name, tri):
     geometric normal, looking at its centroid through a 1 degree field of
     view, and a light on the same side, off the line of sight, facing it: the
     shader shades with the geometric normal, so the triangle is lit."""
-    v, i, _ = _scene(name)
+    v, i, _ = scene(name, MAKERS)
     p = v.reshape(-1, 3)[i.reshape(-1, 3)[tri]].astype(np.float64)
     c = p.mean(0)
     d = np.cross(p[1] - p[0], p[2] - p[0])
@@ -113,8 +93,8 @@ def _aimed_and_lit(name, tri):
 def test_32_triangles_first_and_last_leaf(leaf):
     """63 boxes, 32 leaves: the frame looks at the triangle of leaf 0 and at
     the one of leaf 31 (bit 31 of the masks), by the table's visit order."""
-    v, i, n = _scene("tri:32")
-    slots = test_sweep_fold.visit_order(v, i, n.reshape(-1))
+    v, i, n = scene("tri:32", MAKERS)
+    slots = visit_order(v, i, n.reshape(-1))
     assert len(slots) == 32 and sorted(slots) == list(range(32))
     cam, light = _aimed_and_lit("tri:32", int(slots[leaf]))
     _both("tri:32", cam, light, 96, 64, 0, 2, 4, 3)
@@ -122,7 +102,7 @@ def test_32_triangles_first_and_last_leaf(leaf):
 
 def test_grid_flat_leaf_boxes_two_lights():
     """grid_mesh(2): eight triangles in quads at constant z, so every leaf's box is flat."""
-    _, i, n = _scene("grid:2")
+    _, i, n = scene("grid:2", MAKERS)
     nd = n.reshape(-1, 8)
     assert (nd[:, 2] == nd[:, 6]).sum() >= i.size // 3
     _both("grid:2", scenes.camera((0.0, 0.0, 3.0)), TWO_LIGHTS, 48, 48, 0, 2, 3, 2)

@@ -16,11 +16,11 @@ import torch
 import ptamd
 import scenes
 import temporal_ref as T
+from support import PKG, dev, mse, read_device, read_pfm, renderer, same, scene
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PKG = os.path.dirname(os.path.abspath(ptamd.__file__))
 PT_OK, PT_ERR_INVALID, PT_ERR_UNSUPPORTED = 0, -1, -5
 START = {"box": (0.0, 0.0, 5.0), "sphere": (3.0, 2.0, 4.0)}
 SIZE = {"box": (64, 48), "sphere": (67, 45)}                  # edge tiles in both directions
@@ -30,15 +30,6 @@ AWAY[6] = 1.0
 PREV = {"identical": CUR, "orbit2": T.rotate_y(CUR, -2.0), "away": AWAY, "orbit60": T.rotate_y(CUR, -60.0)}
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = np.argwhere(_bits(got).reshape(-1) != _bits(want).reshape(-1))
-    assert bad.size == 0, f"{what}: {len(bad)} of {np.size(got)} floats differ, first at {bad[0]}"
-
-
 def _orbit(name, degrees):
     """scenes.camera of the scene's start position rotated about +y."""
     x, y, z = START[name]
@@ -46,49 +37,13 @@ def _orbit(name, degrees):
     return scenes.camera((x * np.cos(a) + z * np.sin(a), y, z * np.cos(a) - x * np.sin(a)))
 
 
-@functools.lru_cache(maxsize=None)
-def _scene(name):
-    if name == "box":
-        s = ptamd.Scene.load_obj(scenes.BOX_OBJ).build_bvh()
-    else:
-        s = ptamd.Scene.from_arrays(*scenes.displaced_sphere(subdiv=3)).build_bvh()
-    v, i, n, _, _ = s.arrays()
-    return v, i, n
-
-
 def _renderer(name, W=None, H=None, moments=1):
     w, h = SIZE[name]
-    r = ptamd.Renderer(0)
-    r.set_option(ptamd.PT_OPT_MOMENTS, moments)
-    r.upload_scene(*_scene(name))
-    r.upload_lights(scenes.REFERENCE_LIGHT)
-    r.set_camera(_orbit(name, 0))
-    r.set_params(4, 3)
-    r.resize_and_clear(W or w, H or h)
-    return r
-
-
-@functools.lru_cache(maxsize=None)
-def _hip():
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    return ctypes.CDLL(path)
-
-
-def _read_device(r, ptr, shape):
-    """A library-owned float image, copied behind the context's work."""
-    r.synchronize()
-    out = np.empty(shape, F)
-    assert _hip().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(out.nbytes), 2) == 0
-    return out
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, F)).cuda()
+    return renderer(scene(name), _orbit(name, 0), size=(W or w, H or h), options=[(ptamd.PT_OPT_MOMENTS, moments)])
 
 
 def _device_reproject(r, cur, prev, W, H, n, color, moments, guide, history, params=None):
-    ins = [_dev(color), _dev(moments), _dev(guide)] + ([None] * 4 if history is None else [_dev(a) for a in history])
+    ins = [dev(color), dev(moments), dev(guide)] + ([None] * 4 if history is None else [dev(a) for a in history])
     outs = [torch.full((H, W, k), -7.0, dtype=torch.float32, device="cuda") for k in (4, 2, 1, 1)]
     torch.cuda.synchronize()
     im = ptamd.ReprojectImages(*[None if t is None else t.data_ptr() for t in ins + outs])
@@ -111,14 +66,14 @@ def test_device_matches_host_and_restatement(W, H, cam):
         *ref, _ = T.reproject(CUR, prev, W, H, n, d["color"], d["moments"], d["guide"], history,
                               T.DEFAULTS if params is None else params)
         for g, h_, f_, what in zip(got, host, ref, ("colour", "moments", "length", "variance")):
-            _same(g, h_, f"{cam} {W}x{H} {params}: device against host, {what}")
-            _same(g, f_, f"{cam} {W}x{H} {params}: device against the restatement, {what}")
+            same(g, h_, f"{cam} {W}x{H} {params}: device against host, {what}")
+            same(g, f_, f"{cam} {W}x{H} {params}: device against the restatement, {what}")
         ins = [d["color"], d["moments"], d["guide"]] + ([None] * 4 if history is None else list(history))
         for a, b in zip(after, ins):
             if b is not None:
-                _same(a, b, "an input image after the call")
+                same(a, b, "an input image after the call")
         if history is None:
-            _same(got[0], d["color"], "null history: colour")
+            same(got[0], d["color"], "null history: colour")
             assert np.all(got[2] == F(n))
 
 
@@ -149,11 +104,11 @@ def _loop(name, frames=8, n=2):
         want = ptamd.reproject_host(cam, cam if prev_cam is None else prev_cam, W, H, n, accum, moments, guide, hist)
         r.temporal_advance(cam, n)
         c, m, l = r.read_temporal()
-        v = _read_device(r, r.temporal_ptr(3), (H, W))
+        v = read_device(r, r.temporal_ptr(3), (H, W))
         for g, w_, what in zip((c, m, l, v), want, ("colour", "moments", "length", "variance")):
-            _same(g, w_, f"{name}: frame {k}, {what}")
-        _same(r.read_accum(), accum, f"{name}: frame {k}, the accumulation image")
-        _same(r.read_moments()[0], moments, f"{name}: frame {k}, the moments")
+            same(g, w_, f"{name}: frame {k}, {what}")
+        same(r.read_accum(), accum, f"{name}: frame {k}, the accumulation image")
+        same(r.read_moments()[0], moments, f"{name}: frame {k}, the moments")
         assert r.temporal_info() == (k + 1, (k + 1) * n)
         hist, prev_cam = (want[0], want[1], want[2], guide), cam
         steps.append((cam, accum, moments, guide, want))
@@ -172,8 +127,8 @@ def test_the_loop_equals_the_host_chain(name):
     *ref, info = T.reproject(cam1, cam0, W, H, 2, a1, m1, g1, hist)
     assert info["blended"] > 0 and info["miss"] > 0
     for g, w_, f_, what in zip(got, w1, ref, ("colour", "moments", "length", "variance")):
-        _same(g, w_, f"{name}: pt_reproject of rendered frames, {what}")
-        _same(g, f_, f"{name}: the restatement on rendered frames, {what}")
+        same(g, w_, f"{name}: pt_reproject of rendered frames, {what}")
+        same(g, f_, f"{name}: the restatement on rendered frames, {what}")
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -199,17 +154,17 @@ def test_temporal_denoise_equals_the_host_filter(name):
     _, _, _, guide, want = steps[-1]
     for params in (None, (2, 0.75, 0.5, 0.25)):
         ref = ptamd.denoise_var_plane_host(want[0], want[3], guide, W, H, params)
-        _same(ref, T.atrous_var_plane(want[0], want[3], guide, W, H, (4, 1.5, 1.0, 1.0) if params is None else params),
-              f"{name}: host filter against the restatement")
+        same(ref, T.atrous_var_plane(want[0], want[3], guide, W, H, (4, 1.5, 1.0, 1.0) if params is None else params),
+             f"{name}: host filter against the restatement")
         for staged in (0, 1):
             r.set_option(ptamd.PT_OPT_DENOISE_LDS, staged)
-            _same(r.temporal_denoise(params), ref, f"{name}: {params}, staged {staged}")
+            same(r.temporal_denoise(params), ref, f"{name}: {params}, staged {staged}")
         dst = torch.zeros(H, W, 4, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         assert r.temporal_denoise(params, dst.data_ptr()) is None
         r.synchronize()
-        _same(dst.cpu().numpy(), ref, f"{name}: caller-owned destination")
-    _same(r.read_temporal()[0], want[0], "the temporal colour after the filter")
+        same(dst.cpu().numpy(), ref, f"{name}: caller-owned destination")
+    same(r.read_temporal()[0], want[0], "the temporal colour after the filter")
     L = ptamd.lib()
     assert L.pt_temporal_denoise(r._c, None, dst.data_ptr() + 4) == PT_ERR_INVALID          # misaligned
     assert L.pt_temporal_denoise(r._c, None, r.temporal_ptr(0)) == PT_ERR_INVALID           # onto its source
@@ -260,7 +215,7 @@ def test_what_forgets_the_history():
     r.temporal_reset()
     assert r.temporal_info() == (0, 0) and r.temporal_ptr(0) is None
     forgotten("pt_temporal_reset")
-    for what, act in (("scene upload", lambda: r.upload_scene(*_scene(name))),
+    for what, act in (("scene upload", lambda: r.upload_scene(*scene(name))),
                       ("light upload", lambda: r.upload_lights(scenes.REFERENCE_LIGHT)),
                       ("pt_set_params", lambda: r.set_params(4, 3)),
                       ("resize", lambda: (r.resize_and_clear(W + 3, H), r.resize_and_clear(W, H)))):
@@ -278,7 +233,7 @@ def test_what_forgets_the_history():
     r.progressive_advance(2)
     r.render_guide()
     for a, b in zip(r.read_temporal(), before):
-        _same(a, b, "the temporal result after unrelated renders")
+        same(a, b, "the temporal result after unrelated renders")
     r.temporal_advance(cams[2], n)
     assert np.any(r.read_temporal()[2] > 2 * n)                # two frames of history behind it
     assert r.temporal_info() == (3, 3 * n)
@@ -292,7 +247,7 @@ def test_error_paths():
     assert adv(r) == PT_ERR_INVALID                             # moments off
     r.set_option(ptamd.PT_OPT_MOMENTS, 1)
     assert adv(r) == PT_ERR_INVALID                             # no scene
-    r.upload_scene(*_scene("box"))
+    r.upload_scene(*scene("box"))
     assert adv(r) == PT_ERR_INVALID                             # no lights
     r.upload_lights(scenes.REFERENCE_LIGHT)
     assert adv(r) == PT_ERR_INVALID                             # no frame
@@ -349,14 +304,6 @@ def test_error_paths():
     r.synchronize()
 
 
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = map(int, f.readline().split())
-        assert float(f.readline()) < 0   # little-endian
-        return np.fromfile(f, "<f4").reshape(h, w, 3)
-
-
 @pytest.mark.parametrize("denoise", [False, True])
 def test_pt_render_temporal_flag(tmp_path, denoise):
     W, H, spp, K = 64, 48, 2, 4
@@ -377,12 +324,7 @@ def test_pt_render_temporal_flag(tmp_path, denoise):
                 cam[o], cam[o + 2] = x * c2 + z * s2, z * c2 - x * s2
         r.temporal_advance(cam, spp)
     want = r.temporal_denoise() if denoise else r.read_temporal()[0]
-    _same(_read_pfm(out), want[..., :3], f"pt_render -temporal, denoise {denoise}")
-
-
-def _mse(a, b, mask):
-    d = a[..., :3].astype(np.float64)[mask] - b[..., :3].astype(np.float64)[mask]
-    return float(np.mean(d * d))
+    same(read_pfm(out), want[..., :3], f"pt_render -temporal, denoise {denoise}")
 
 
 @pytest.mark.parametrize("name", ["box", "sphere"])
@@ -410,7 +352,7 @@ def test_quality(name):
     q.set_option(ptamd.PT_OPT_SEED_BASE, 1000)
     q.render(0, 256)
     ref = q.read_accum().reshape(H, W, 4)
-    e_raw, e_t, e_f, e_rf = (_mse(x, ref, hit) for x in (raw, temporal, filtered, raw_filtered))
+    e_raw, e_t, e_f, e_rf = (mse(x, ref, hit) for x in (raw, temporal, filtered, raw_filtered))
     print(f"temporal quality {name} 64x64, {np.count_nonzero(hit)} first-hit pixels: mse raw = {e_raw:.4e}, "
           f"temporal = {e_t:.4e} ({e_t / e_raw:.3f} of raw), pt_temporal_denoise = {e_f:.4e} ({e_f / e_raw:.3f}), "
           f"pt_denoise_var of raw = {e_rf:.4e} ({e_rf / e_raw:.3f})")

@@ -11,6 +11,7 @@ import pytest
 import oracle_lib as O
 import ptamd
 import scenes
+from obj_cases import OBJ_CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,26 +102,6 @@ def test_bvh_errors():
         ptamd.Scene.from_arrays(np.zeros(9, np.float32), np.array([0, 1, 5], np.uint32)).build_bvh()
     with pytest.raises(ptamd.PTError):
         ptamd.Scene.from_arrays(np.zeros(9, np.float32), np.array([0, 1], np.uint32))
-
-
-OBJ_CASES = {
-    "formats": b"v 0 0 0\nv 1 0 0\nv 1 1 0\nv 0 1 0\nvt 0 0\nvn 0 0 1\n"
-               b"f 1/1/1 2/1/1 3/1/1\nf 1//1 3//1 4//1\nf -4 -2 -1\n",
-    "quads_both_diagonals": b"v 0 0 0\nv 2 0 0\nv 2 1 0\nv 0 1 0\nv 0 0 1\nv 1 0 1\nv 3 1 1\nv 0 1 1\n"
-                            b"f 1 2 3 4\nf 5 6 7 8\n",
-    "numbers": b"v 1.5e1 -.25 +3\nv 0.000000012345678 1E-3 -0\nv 123456789.123456789 7 1e+2\n"
-               b"v 0.1 0.2 0.3\nf 1 2 3\nf 2 3 4\n",
-    "shapes_and_comments": b"# c\no A\nv 0 0 0\nv 1 0 0\nv 0 1 0\ng B\nusemtl x\nv 0 0 1\n  f 1 2 3\nf 2 3 4\n",
-    "crlf": b"v 0 0 0\r\nv 1 0 0\r\nv 0 1 0\r\nf 1 2 3\r\n",
-    # n-gons: tinyobj ear clipping (tiny_obj_loader.h:1740-1955)
-    "ngon_convex_xy": b"v 0 0 0\nv 2 0 0\nv 3 1 0\nv 1 3 0\nv -1 1 0\nf 1 2 3 4 5\n",
-    "ngon_concave_offset": b"v 1 1 0\nv 5 1 0\nv 5 5 0\nv 3 2 0\nv 1 5 0\nv 0.5 3 0\nf 1 2 3 4 5 6\nf 6 5 4 3 2 1\n",
-    "ngon_planes": b"v 0 0 0\nv 0 2 0\nv 0 3 1\nv 0 1 3\nv 0 -1 1\nv 1 0 0\nv 3 0 1\nv 2 0 3\nv 0.5 0 2\nv 0 0 1\n"
-                   b"f 1 2 3 4 5\nf 6 7 8 9 10 1\n",
-    "ngon_collinear_start": b"v 0 0 0\nv 1 0 0\nv 2 0 0\nv 2 2 1\nv 0 2 1\nv -1 1 0.5\nv -0.5 0.2 0.1\nf 1 2 3 4 5 6 7\n",
-    "ngon_star": b"v 0 3 0\nv 1 1 0\nv 3 1 0\nv 1.5 -0.5 0\nv 2 -3 0\nv 0 -1.5 0\nv -2 -3 0\nv -1.5 -0.5 0\n"
-                 b"v -3 1 0\nv -1 1 0\nf 1 2 3 4 5 6 7 8 9 10\n",
-}
 
 
 @pytest.mark.parametrize("case", sorted(OBJ_CASES))

@@ -18,6 +18,7 @@ import pytest
 import oracle_lib as O
 import ptamd
 import scenes
+from support import read_pfm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "discovering-path-tracer_amd")
@@ -83,15 +84,6 @@ def test_integration_snippets_render_the_oracle_frame(tmp_path, mode):
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = map(int, f.readline().split())
-        scale = float(f.readline())
-        assert scale < 0   # little-endian
-        return np.fromfile(f, "<f4").reshape(h, w, 3)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [[], ["-fused"], ["-progressive", "8", "-chunk", "3"],
                                    ["-devices", "0,0,0", "-progressive", "8", "-chunk", "3"]])
@@ -107,6 +99,6 @@ def test_pt_render_cpp_driver_matches_oracle(tmp_path, flags):
     res = subprocess.run([exe, scenes.BOX_OBJ, "-w", str(W), "-h", str(H), "-spp", str(spp), "-o", out] + flags,
                          capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stderr[-3000:]
-    got = _read_pfm(out)   # rows bottom-to-top: buffer row 0 first
+    got = read_pfm(out)   # rows bottom-to-top: buffer row 0 first
     want = _oracle_box(W, H, spp).reshape(H, W, 4)[..., :3]
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))

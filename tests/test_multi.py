@@ -25,6 +25,7 @@ import torch.multiprocessing as mp
 import oracle_lib as O
 import ptamd
 import scenes
+from support import box_mesh, oracle_built
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,9 +34,7 @@ CAM = scenes.camera((3.0, 2.0, 4.0))   # the box off-centre: live and culled ite
 
 
 def _scene():
-    v, i, _ = O.obj_parse(open(scenes.BOX_OBJ, "rb").read())
-    ri, nodes = O.bvh_build(v, i)
-    return v, ri, nodes
+    return oracle_built(*box_mesh())
 
 
 def _rects(nodes):

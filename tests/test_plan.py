@@ -12,23 +12,14 @@ import subprocess
 
 import pytest
 
+import native
 import plan_cases
 from plan_cases import ROWS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "discovering-path-tracer_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "_build")
-
 
 def _harness():
-    src = os.path.join(ROOT, "tests", "plan_check.cpp")
-    exe = os.path.join(BUILD, "plan_check")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("pt_plan.h", "pt_context.h", "pt_device.h", "pt_group.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        os.makedirs(BUILD, exist_ok=True)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", CSRC,
-                               "-o", exe, src])
-    return exe
+    return native.build("plan_check", [os.path.join(native.TESTS, "plan_check.cpp")],
+                        ["-O1"] + native.COMMON[:2] + ["-I", native.CSRC])
 
 
 def line_of(r):

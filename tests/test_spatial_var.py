@@ -4,28 +4,20 @@ csrc/pt_denoise.h spatial_var_pixel) against the independent numpy-float32
 restatement of tests/spatial_var_ref.py, bit for bit; the argument checks; a
 checkerboard whose answer is derived by hand; and the stand-alone program."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import native
 import ptamd
 import spatial_var_ref as S
+from support import same
 
 PT_OK, PT_ERR_INVALID = 0, -1
 F = np.float32
 SIZES = [(16, 16), (37, 23), (64, 48)]
 RADII = [1, 2, 3]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = np.argwhere(_bits(got) != _bits(want))
-    assert bad.size == 0, f"{what}: {len(bad)} of {np.size(got)} floats differ, first at {bad[0]}"
 
 
 def test_symbols_and_defaults():
@@ -109,12 +101,12 @@ def test_host_matches_restatement(radius):
             ref = S.spatial_variance(d["moments"], d["length"], d["variance"], d["guide"], W, H,
                                      S.DEFAULTS if params is None else params)
             assert np.all(np.isfinite(got)) and np.all(got >= 0)
-            _same(got, ref, f"{W}x{H} {tag} {params}")
+            same(got, ref, f"{W}x{H} {tag} {params}")
             below = S.DEFAULTS[0] if params is None else params[0]
             keep = d["length"] >= below
-            _same(got[keep], d["variance"][keep], "pixels at or above the threshold")
+            same(got[keep], d["variance"][keep], "pixels at or above the threshold")
             if tag == "none" and below <= 8:
-                _same(got, d["variance"], "no short pixel: the variance itself")
+                same(got, d["variance"], "no short pixel: the variance itself")
             elif not tag:
                 assert np.any(got[~keep] > 0)
 
@@ -149,7 +141,7 @@ def test_argument_checks():
     for below in (0, 1):                                                           # select no pixel
         out[:] = -7.0
         assert call(params=(below, 3, 0.5, 0.5)) == PT_OK
-        _same(out, v, f"below {below}")
+        same(out, v, f"below {below}")
     with pytest.raises(ptamd.PTError):
         ptamd.spatial_variance_host(d["moments"], d["length"][:-1], d["variance"], d["guide"], W, H)
 
@@ -175,20 +167,14 @@ def test_checkerboard_has_a_known_answer(W, H):
     got = ptamd.spatial_variance_host(moments, length, variance, guide, W, H, (2, 1, 1.0, 1.0))
     want = np.full((H, W), 20.25, F)
     want[1:-1, 1:-1] = 20.0
-    _same(got, want, "checkerboard")
-    _same(ptamd.spatial_variance_host(moments, length, variance, guide, W, H, (1, 1, 1.0, 1.0)), variance, "below 1")
+    same(got, want, "checkerboard")
+    same(ptamd.spatial_variance_host(moments, length, variance, guide, W, H, (1, 1, 1.0, 1.0)), variance, "below 1")
 
 
 def test_stand_alone_check_program(tmp_path):
     """tests/spatial_var_check.cpp (the program sanitizer runs use), built
     plainly against the library and run."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.dirname(os.path.abspath(ptamd.__file__))
-    exe = str(tmp_path / "spatial_var_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(root, "include"), "-I", os.path.join(pkg, "csrc"),
-                           os.path.join(root, "tests", "spatial_var_check.cpp"), "-L", pkg, "-lptamd",
-                           "-Wl,-rpath," + pkg, "-o", exe])
+    exe = native.against_library("spatial_var_check", tmp_path)
     res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert res.stdout.startswith("ok:")

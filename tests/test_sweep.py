@@ -9,167 +9,16 @@ equal.  The rays include origins inside the root box, directions with a zero
 component (inv is infinite and the slab test sees NaNs) and rays lying in a
 face plane.
 """
-import ctypes
-import os
-import subprocess
-
-import numpy as np
 import pytest
 
-import oracle_lib
-import scenes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "discovering-path-tracer_amd", "csrc")
-SO = os.path.join(ROOT, "tests", "_build", "libsweep_check.so")
-_LIB = None
-
-
-def lib():
-    global _LIB
-    if _LIB is None:
-        srcs = [os.path.join(ROOT, "tests", "sweep_check.cpp"), os.path.join(CSRC, "scene", "small_sweep.cpp"),
-                os.path.join(CSRC, "scene", "threaded_bvh.cpp")]
-        deps = srcs + [os.path.join(CSRC, f) for f in ("sweep_walk.h", "pt_isect.h", "pt_math.h",
-                                                       os.path.join("scene", "small_sweep.h"),
-                                                       os.path.join("scene", "threaded_bvh.h"))]
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.check_call(
-                ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
-                 "-ffp-contract=off", "-fno-fast-math", "-I", CSRC, "-o", SO] + srcs)
-        L = ctypes.CDLL(SO)
-        F32P = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
-        U32P = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
-        U64P = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
-        I32P = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
-        sz = ctypes.c_size_t
-        L.sweep_info.argtypes = [F32P, sz, U32P, sz, F32P, sz, ctypes.c_int, I32P, ctypes.c_char_p, sz]
-        L.sweep_check.argtypes = [F32P, sz, U32P, sz, F32P, sz, ctypes.c_int, F32P, sz, U64P, ctypes.c_char_p, sz]
-        _LIB = L
-    return _LIB
-
-
-def _built(v, i):
-    idx, nodes = oracle_lib.bvh_build(v, i)
-    return np.ascontiguousarray(v, np.float32), idx, nodes
-
-
-def _box():
-    with open(scenes.BOX_OBJ, "rb") as f:
-        v, i, _ = oracle_lib.obj_parse(f.read())
-    return _built(v, i)
-
-
-def info(v, idx, nodes):
-    out = np.zeros(4, np.int32)
-    err = ctypes.create_string_buffer(256)
-    rc = lib().sweep_info(v, v.size, idx, idx.size // 3, nodes, nodes.size // 8, 0, out, err, 256)
-    assert rc in (0, 2), err.value.decode()
-    return rc == 0, out
-
-
-def _unit(a):
-    a = np.asarray(a, np.float32)
-    return (a / np.sqrt((a * a).sum(-1, keepdims=True))).astype(np.float32)
-
-
-def make_rays(v, idx, n, seed):
-    """n x 8 float32 {o, d, shadow limit, 0}: a mix of ray families."""
-    rng = np.random.default_rng(seed)
-    V = v.reshape(-1, 3)
-    lo, hi = V.min(0), V.max(0)
-    ext = np.maximum(hi - lo, np.float32(0.05))
-    k = n // 6
-    fam = []
-    # 1. origins around the scene, random directions
-    fam.append((rng.uniform(lo - ext, hi + ext, (k, 3)), _unit(rng.normal(size=(k, 3)))))
-    # 2. origins inside the root box, random directions
-    fam.append((rng.uniform(lo, hi, (k, 3)), _unit(rng.normal(size=(k, 3)))))
-    # 3. from outside towards points on the triangles
-    P = V[idx.reshape(-1, 3)]
-    t = rng.integers(0, len(P), k)
-    b = rng.dirichlet([1, 1, 1], k).astype(np.float32)
-    # (placed by the scene's bounds: (0.3, 0.2, 3.0) for the box's [-1, 1]^3)
-    o = np.tile(((lo + hi) / 2 + ext.max() * np.float32([0.15, 0.1, 1.5])).astype(np.float32), (k, 1))
-    fam.append((o, _unit((P[t] * b[:, :, None]).sum(1) - o)))
-    # 4. one or two zero direction components, origins anywhere (half of them inside)
-    o = rng.uniform(lo - ext * 0.5, hi + ext * 0.5, (k, 3))
-    d = _unit(rng.normal(size=(k, 3)))
-    d[np.arange(k), rng.integers(0, 3, k)] = 0.0
-    two = rng.random(k) < 0.3
-    d[two, (rng.integers(0, 3, k))[two]] = 0.0
-    d[(d == 0).all(1)] = np.float32([0, 0, -1])
-    fam.append((o, _unit(d)))
-    # 5. origin on a face plane of the root box or on a vertex coordinate, direction free
-    o = rng.uniform(lo, hi, (k, 3))
-    ax = rng.integers(0, 3, k)
-    pick = V[rng.integers(0, len(V), k), ax]
-    side = rng.random(k)
-    o[np.arange(k), ax] = np.where(side < 0.33, lo[ax], np.where(side < 0.66, hi[ax], pick))
-    fam.append((o, _unit(rng.normal(size=(k, 3)))))
-    # 6. rays lying in such a plane: the origin's coordinate on it, that direction component zero
-    k6 = n - 5 * k
-    o = rng.uniform(lo - ext * 0.5, hi + ext * 0.5, (k6, 3))
-    ax = rng.integers(0, 3, k6)
-    pick = V[rng.integers(0, len(V), k6), ax]
-    side = rng.random(k6)
-    o[np.arange(k6), ax] = np.where(side < 0.33, lo[ax], np.where(side < 0.66, hi[ax], pick))
-    d = _unit(rng.normal(size=(k6, 3)))
-    d[np.arange(k6), ax] = 0.0
-    fam.append((o, _unit(d)))
-    rays = np.zeros((n, 8), np.float32)
-    rays[:, 0:3] = np.concatenate([f[0] for f in fam]).astype(np.float32)
-    rays[:, 3:6] = np.concatenate([f[1] for f in fam]).astype(np.float32)
-    rays[:, 6] = rng.uniform(0.0, 4.0, n).astype(np.float32)
-    return rays
-
-
-def check(v, idx, nodes, rays):
-    st = np.zeros(8, np.uint64)
-    err = ctypes.create_string_buffer(256)
-    rays = np.ascontiguousarray(rays, np.float32)
-    rc = lib().sweep_check(v, v.size, idx, idx.size // 3, nodes, nodes.size // 8, 0, rays, rays.shape[0], st, err, 256)
-    assert rc in (0, 2), err.value.decode()
-    return rc == 0, st
-
-
-def _box_mesh():
-    with open(scenes.BOX_OBJ, "rb") as f:
-        v, i, _ = oracle_lib.obj_parse(f.read())
-    return v, i
-
-
-# Tiny scenes away from the origin-centred, unit-sized, non-degenerate ones:
-# name -> (vertices, indices) before the BVH build (shared with the GPU tests).
-HOSTILE = {
-    "box@300": lambda: (scenes.transformed(_box_mesh()[0], 1.0, (300, 300, -300)), _box_mesh()[1]),
-    "box*50": lambda: (scenes.transformed(_box_mesh()[0], 50.0, (0, 0, 0)), _box_mesh()[1]),
-    "box*0.01": lambda: (scenes.transformed(_box_mesh()[0], 0.01, (0, 0, 0)), _box_mesh()[1]),
-    "box:copies2": lambda: scenes.coincident_copies(*_box_mesh(), 2),
-    "tri4:copies8": lambda: scenes.coincident_copies(*scenes.random_triangles(4), 8),
-    "flat_quad": scenes.flat_quad,
-    "tri8:degenerate": lambda: scenes.with_degenerates(*scenes.random_triangles(8)),
-}
-# (distinct boxes, leaves) of the tables where the scene fixes them
-HOSTILE_TABLES = {"box:copies2": (7, 24), "tri4:copies8": (7, 32), "flat_quad": (1, 2), "tri8:degenerate": (15, 8)}
-
-
-def _scene(name):
-    if name == "box":
-        return _box()
-    if name in HOSTILE:
-        return _built(*HOSTILE[name]())
-    kind, n = name.split(":")
-    return _built(*(scenes.grid_mesh(int(n)) if kind == "grid" else scenes.random_triangles(int(n))))
-
+from sweep_support import HOSTILE, HOSTILE_TABLES, check, info, make_rays, scene
 
 SCENES = ["box", "grid:2", "grid:3", "grid:4", "tri:1", "tri:2", "tri:3", "tri:7", "tri:16", "tri:32"] + sorted(HOSTILE)
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_sweep_equals_threaded_walk(name):
-    v, idx, nodes = _scene(name)
+    v, idx, nodes = scene(name)
     has, inf = info(v, idx, nodes)
     rays = make_rays(v, idx, 6000, seed=len(name) * 131 + idx.size)
     ok, st = check(v, idx, nodes, rays)
@@ -186,7 +35,7 @@ def test_sweep_equals_threaded_walk(name):
 
 
 def test_box_has_at_most_nine_boxes():
-    v, idx, nodes = _box()
+    v, idx, nodes = scene("box")
     has, inf = info(v, idx, nodes)
     assert has
     assert inf[0] <= 9 and inf[1] == 12
@@ -194,7 +43,7 @@ def test_box_has_at_most_nine_boxes():
 
 
 def test_no_table_past_32_leaves():
-    v, idx, nodes = _scene("tri:33")
+    v, idx, nodes = scene("tri:33")
     has, inf = info(v, idx, nodes)
     assert not has and inf[0] == 0 and inf[1] == 0
     ok, _ = check(v, idx, nodes, make_rays(v, idx, 60, seed=1))

@@ -11,88 +11,22 @@ shadow answer taken from the new mask with the threaded walk's, bit for bit.
 It also checks every box's under word against its definition from need[],
 the table's order (root, general, x-, y-, z-flat boxes) against the boxes, and
 the flat loops' slab test against slab on every ray and flat box.
-The rays are test_sweep.make_rays': zero direction components (NaNs in the
+The rays are sweep_support.make_rays': zero direction components (NaNs in the
 slab test), origins inside the root and on face planes, and a family aimed at
 every triangle.
 """
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import test_sweep
-
-ROOT = test_sweep.ROOT
-CSRC = test_sweep.CSRC
-SRC = os.path.join(ROOT, "tests", "sweep_fold_check.cpp")
-BUILD = os.path.join(ROOT, "tests", "_build")
-SO = os.path.join(BUILD, "libsweep_fold_check.so")
-FLAGS = ["-std=c++17", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off", "-fno-fast-math", "-I", CSRC,
-         "-I", os.path.join(ROOT, "tests")]
-_LIB = None
-
-
-def _sources():
-    srcs = [SRC, os.path.join(CSRC, "scene", "small_sweep.cpp"), os.path.join(CSRC, "scene", "threaded_bvh.cpp")]
-    deps = srcs + [os.path.join(ROOT, "tests", "sweep_check.cpp")] + [
-        os.path.join(CSRC, f) for f in ("sweep_walk.h", "pt_isect.h", "pt_math.h", os.path.join("scene", "small_sweep.h"),
-                                        os.path.join("scene", "threaded_bvh.h"))]
-    return srcs, deps
-
-
-def _stale(out, deps):
-    return not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
-
-
-def lib():
-    global _LIB
-    if _LIB is None:
-        srcs, deps = _sources()
-        if _stale(SO, deps):
-            os.makedirs(BUILD, exist_ok=True)
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-fPIC", "-shared"] + FLAGS + ["-o", SO] + srcs)
-        L = ctypes.CDLL(SO)
-        F32P = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
-        U32P = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
-        U64P = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
-        I32P = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
-        sz = ctypes.c_size_t
-        L.sweep_fold_check.argtypes = [F32P, sz, U32P, sz, F32P, sz, ctypes.c_int, F32P, sz, U64P, I32P, I32P,
-                                       ctypes.c_char_p, sz]
-        _LIB = L
-    return _LIB
-
-
-def fold_check(v, idx, nodes, rays):
-    """(stats[16], boxes, leaves, slot per leaf in visit order, flat boxes) of tests/sweep_fold_check.cpp."""
-    st = np.zeros(16, np.uint64)
-    info = np.zeros(3, np.int32)
-    slots = np.full(32, -1, np.int32)
-    err = ctypes.create_string_buffer(256)
-    rays = np.ascontiguousarray(rays, np.float32)
-    v = np.ascontiguousarray(v, np.float32).reshape(-1)
-    idx = np.ascontiguousarray(idx, np.uint32).reshape(-1)
-    nodes = np.ascontiguousarray(nodes, np.float32).reshape(-1)
-    rc = lib().sweep_fold_check(v, v.size, idx, idx.size // 3, nodes, nodes.size // 8, 0, rays, rays.shape[0], st, info,
-                                slots, err, 256)
-    assert rc == 0, (rc, err.value.decode())
-    return st, int(info[0]), int(info[1]), slots[:int(info[1])].copy(), int(info[2])
-
-
-def visit_order(v, idx, nodes):
-    """The triangle slot of each leaf of the scene's sweep table, in visit order."""
-    return fold_check(v, idx, nodes, np.zeros((1, 8), np.float32) + np.float32(1.0))[3]
-
+from sweep_support import fold_check, make_rays, run_main, scene
 
 SCENES = ["box", "grid:2", "grid:3", "tri:1", "tri:3", "tri:8", "tri:32"]
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_fold_equals_two_passes_and_threaded_walk(name):
-    v, idx, nodes = test_sweep._scene(name)
-    rays = test_sweep.make_rays(v, idx, 6000, seed=len(name) * 131 + idx.size)
+    v, idx, nodes = scene(name)
+    rays = make_rays(v, idx, 6000, seed=len(name) * 131 + idx.size)
     st, boxes, leaves, slots, flat = fold_check(v, idx, nodes, rays)
     first = int(st[5])
     where = f"{name}: first bad ray {first}: {rays[first % len(rays)]}"
@@ -126,11 +60,5 @@ def test_standalone_program():
     """The harness's own main (the program meant for host sanitizer runs)
     builds and passes on its built-in scene: a cube of flat face boxes plus a
     tilted triangle."""
-    srcs, deps = _sources()
-    exe = os.path.join(BUILD, "sweep_fold_check")
-    if _stale(exe, deps):
-        os.makedirs(BUILD, exist_ok=True)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-g", "-DSWEEP_FOLD_MAIN"] + FLAGS + ["-o", exe] + srcs)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "leaves=13 flat_boxes=6 mask=0 none=0 riding=0 hit=0 shadow=0 under=0 flat=0 order=0" in out.stdout, out.stdout
+    out = run_main("sweep_fold_check", "SWEEP_FOLD_MAIN")
+    assert "leaves=13 flat_boxes=6 mask=0 none=0 riding=0 hit=0 shadow=0 under=0 flat=0 order=0" in out, out

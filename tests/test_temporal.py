@@ -4,16 +4,17 @@ csrc/pt_denoise.h) against the independent numpy-float32 restatements of
 tests/temporal_ref.py, bit for bit; the no-history branches; the argument
 checks; and a one-pixel camera shift that must read the neighbour's history."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import denoise_var_ref as V
+import native
 import ptamd
 import scenes
 import temporal_ref as T
+from support import same
 
 PT_OK, PT_ERR_INVALID = 0, -1
 F = np.float32
@@ -28,15 +29,6 @@ CAMERAS = {
     "orbit60": (T.rotate_y(CUR, -60.0), {"miss", "outside", "no_valid"}),
 }
 SIZES = [(16, 16), (37, 23), (64, 48)]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = np.argwhere(_bits(got) != _bits(want))
-    assert bad.size == 0, f"{what}: {len(bad)} of {np.size(got)} floats differ, first at {bad[0]}"
 
 
 def test_symbols_and_defaults():
@@ -83,11 +75,11 @@ def test_host_matches_restatement(W, H, cam):
                                  T.DEFAULTS if params is None else params)
         for g, r, what in zip(got, ref, ("colour", "moments", "length", "variance")):
             assert np.all(np.isfinite(g)), what
-            _same(g, r, f"{cam} {W}x{H} {params}: {what}")
+            same(g, r, f"{cam} {W}x{H} {params}: {what}")
         taken = {k for k in ("miss", "behind", "outside", "no_valid") if info[k] > 0}
         assert taken == branches, info
         assert (info["blended"] > 0) == (cam != "away"), info
-        _same(got[0][..., 3], d["color"][..., 3], "alpha passes through")
+        same(got[0][..., 3], d["color"][..., 3], "alpha passes through")
         cap = 64 if params is None else params[0]
         assert got[2].min() == n and got[2].max() <= cap + n
         if cam != "away":
@@ -98,17 +90,17 @@ def test_null_history_gives_the_new_frame():
     W, H, n = 37, 23, 3
     d = T.make_inputs(W, H, 11, CUR, CUR)
     c, m, l, v = ptamd.reproject_host(CUR, CAMERAS["orbit2"][0], W, H, n, d["color"], d["moments"], d["guide"], None)
-    _same(c, d["color"], "colour")
-    _same(m, d["moments"], "moments")
+    same(c, d["color"], "colour")
+    same(m, d["moments"], "moments")
     assert np.all(l == F(n))
     m1, m2 = d["moments"][..., 0], d["moments"][..., 1]
-    _same(v, np.maximum(F(0), m2 - m1 * m1) / F(n - 1), "variance of the mean")
+    same(v, np.maximum(F(0), m2 - m1 * m1) / F(n - 1), "variance of the mean")
     assert np.any(v == 0) and np.any(v > 0)
     ref = T.reproject(CUR, CUR, W, H, n, d["color"], d["moments"], d["guide"], None)
-    _same(v, ref[3], "variance against the restatement")
+    same(v, ref[3], "variance against the restatement")
     # one sample: the divisor is fmax(n - 1, 1) = 1
     v1 = ptamd.reproject_host(CUR, CUR, W, H, 1, d["color"], d["moments"], d["guide"], None)[3]
-    _same(v1, np.maximum(F(0), m2 - m1 * m1), "variance at n = 1")
+    same(v1, np.maximum(F(0), m2 - m1 * m1), "variance at n = 1")
 
 
 def test_argument_checks():
@@ -210,11 +202,11 @@ def test_filter_from_a_variance_plane(W, H, iterations):
     params = (iterations, 1.5, 0.35, 0.25)
     got = ptamd.denoise_var_plane_host(rgba, plane, guide, W, H, params)
     assert np.all(np.isfinite(got))
-    _same(got, T.atrous_var_plane(rgba, plane, guide, W, H, params), "plane filter")
+    same(got, T.atrous_var_plane(rgba, plane, guide, W, H, params), "plane filter")
     # pt_denoise_var_host is the plane filter after its own var0, and still equals its restatement
     host = ptamd.denoise_var_host(rgba, moments, n, guide, W, H, params)
-    _same(host, V.atrous_var(rgba, moments, n, guide, W, H, params), "pt_denoise_var_host")
-    _same(host, ptamd.denoise_var_plane_host(rgba, V.var_of_mean(moments, n), guide, W, H, params), "var0 then plane")
+    same(host, V.atrous_var(rgba, moments, n, guide, W, H, params), "pt_denoise_var_host")
+    same(host, ptamd.denoise_var_plane_host(rgba, V.var_of_mean(moments, n), guide, W, H, params), "var0 then plane")
 
 
 def test_filter_plane_rejects_bad_arguments():
@@ -235,13 +227,7 @@ def test_filter_plane_rejects_bad_arguments():
 def test_stand_alone_check_program(tmp_path):
     """tests/temporal_check.cpp (the program sanitizer runs use), built plainly
     against the library and run."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.dirname(os.path.abspath(ptamd.__file__))
-    exe = str(tmp_path / "temporal_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(root, "include"), "-I", os.path.join(pkg, "csrc"),
-                           os.path.join(root, "tests", "temporal_check.cpp"), "-L", pkg, "-lptamd",
-                           "-Wl,-rpath," + pkg, "-o", exe])
+    exe = native.against_library("temporal_check", tmp_path)
     res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert res.stdout.startswith("ok:")

@@ -12,38 +12,29 @@ shadow limits just around the hit distance.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import native
 import oracle_lib
 import scenes
+from oracle_lib import F32P, F64P, I32P, U32P, U64P
+from scenes import WIDE_HOSTILE as HOSTILE
+from support import box_mesh, oracle_built
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "discovering-path-tracer_amd", "csrc")
-SO = os.path.join(ROOT, "tests", "_build", "libwide_check.so")
 _LIB = None
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        srcs = [os.path.join(ROOT, "tests", "wide_check.cpp"), os.path.join(CSRC, "scene", "wide_bvh.cpp")]
-        deps = srcs + [os.path.join(CSRC, f) for f in ("wide_walk.h", "pt_isect.h", "pt_math.h")]
         oracle_lib.lib()   # builds liboracle.so if needed
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.check_call(
-                ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
-                 "-ffp-contract=off", "-fno-fast-math", "-I", CSRC, "-o", SO] + srcs +
-                ["-L", os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle")])
-        L = ctypes.CDLL(SO)
-        F32P = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
-        U32P = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
-        U64P = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
-        I32P = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
-        F64P = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+        so = native.build("libwide_check.so", [os.path.join(native.TESTS, "wide_check.cpp"),
+                                               os.path.join(native.CSRC, "scene", "wide_bvh.cpp")],
+                          ["-O2"] + native.COMMON + ["-I", native.CSRC], shared=True,
+                          libs=["-L", oracle_lib.ORACLE_DIR, "-loracle", "-Wl,-rpath," + oracle_lib.ORACLE_DIR])
+        L = ctypes.CDLL(so)
         sz = ctypes.c_size_t
         L.wide_info.argtypes = [F32P, sz, U32P, sz, F32P, sz, ctypes.c_int, I32P, ctypes.c_char_p, sz]
         L.wide_check.argtypes = [F32P, sz, U32P, sz, F32P, sz, ctypes.c_int, F32P, sz, F32P, U64P,
@@ -57,11 +48,6 @@ def lib():
                                   sz]
         _LIB = L
     return _LIB
-
-
-def _scene(v, i):
-    idx, nodes = oracle_lib.bvh_build(v, i)
-    return np.ascontiguousarray(v, np.float32), idx, nodes
 
 
 # the two ways the wide nodes group the reference's leaves (scene/wide_bvh.h)
@@ -161,7 +147,7 @@ def make_rays(v, idx, n, seed):
 
 def run_scene(v, i, n_rays, seed, build=(WIDE_SAH, 64, 1), rays=None):
     """make_rays' mix (or the given rays(v, idx)) as closest-hit and as shadow queries."""
-    v, idx, nodes = _scene(v, i)
+    v, idx, nodes = oracle_built(v, i)
     mixed = rays is None
     rays = make_rays(v, idx, n_rays, seed) if mixed else rays(v, idx)
     out, st = check(v, idx, nodes, rays, build)     # closest
@@ -243,7 +229,7 @@ def test_wide_walk_grid_ties(build):
 
 @BUILDS
 def test_wide_walk_box_big_triangles(build):
-    v, i, _ = oracle_lib.obj_parse(open(scenes.BOX_OBJ, "rb").read())
+    v, i = box_mesh()
     run_scene(v, i, 40000, seed=14, build=build)
 
 
@@ -256,26 +242,6 @@ def test_wide_walk_dense_tiny_cloud(build):
     # (queued tests cull against a best hit that lags by up to a queue's worth;
     # an 8-wide node queues up to eight leaves at once)
     assert st[4] < (0.8 if not build[2] else 0.97 if build[1] == 80 else 0.95) * st[6], (int(st[4]), int(st[6]))
-
-
-# Scenes away from the [-1, 1]^3 the cases above live in.  The cull bound's
-# terms grow with |o - v0|, with the edge lengths and with the largest
-# coefficients below a node (wide_bvh.cpp: wide_tri_coeffs, node_cull_consts),
-# and the 64-byte nodes' 8-bit grid is rounded outward from each node's own
-# origin and scale.
-HOSTILE = {
-    "cloud_far": lambda: (scenes.transformed(scenes.random_triangles(20000, seed=7)[0], 1.0, (1000, -500, 2000)),
-                          scenes.random_triangles(20000, seed=7)[1]),
-    "sphere_at_300": lambda: (scenes.transformed(scenes.displaced_sphere(3)[0], 1.0, (300, 300, -300)),
-                              scenes.displaced_sphere(3)[1]),
-    "sphere_x50": lambda: (scenes.transformed(scenes.displaced_sphere(3)[0], 50.0, (0, 0, 0)),
-                           scenes.displaced_sphere(3)[1]),
-    "sphere_x0.05": lambda: (scenes.transformed(scenes.displaced_sphere(3)[0], 0.05, (0, 0, 0)),
-                             scenes.displaced_sphere(3)[1]),
-    "floor_and_cloud": scenes.floor_and_cloud,
-    "coincident_x6": lambda: scenes.coincident_copies(*scenes.displaced_sphere(2), 6),
-    "degenerates": lambda: scenes.with_degenerates(*scenes.random_triangles(3000, seed=8, spread=0.5, size=0.02)),
-}
 
 
 @BUILDS
@@ -325,7 +291,7 @@ def test_wide_walk_far_origins(build):
 
 def test_wide_info_and_refusals():
     v, i = scenes.random_triangles(1000, seed=3)
-    v, idx, nodes = _scene(v, i)
+    v, idx, nodes = oracle_built(v, i)
     info = np.zeros(2, np.int32)
     err = ctypes.create_string_buffer(256)
     L = lib()
@@ -357,7 +323,7 @@ def test_wide_tree_invariants(build):
     rank appears once; every inner child's box contains every leaf box below
     it; the SAH build is deterministic (threaded, same tree twice)."""
     sv, si = scenes.displaced_sphere(subdiv=4)
-    v, idx, nodes = _scene(sv, si)
+    v, idx, nodes = oracle_built(sv, si)
     W, rank_tri = _dump(v, idx, nodes, build)
     if build == WIDE_SAH:
         W2, rank_tri2 = _dump(v, idx, nodes, build)
