@@ -73,9 +73,13 @@ struct LightSample {
 __device__ __forceinline__ LightSample sample_light(const LightDev& L, v3 p, v3 n, uint32_t* rng) {
   const v3 lp = sample_area_light(L, rng);
   LightSample s;
-  s.dir = normalize(sub(lp, p));
+  // normalize and length take sqrt_ of the same dot: one evaluation serves both (the guarded sqrt_ has a
+  // ballot in it, which the compiler does not fold across the branch)
+  const v3 d = sub(lp, p);
+  const float len = sqrt_(dot(d, d));
+  s.dir = muls(d, rcp_(len));
   s.diff = fmax_(dot(n, s.dir), 0.0f);
-  s.dist = length(sub(lp, p));
+  s.dist = len;
   return s;
 }
 
@@ -266,7 +270,7 @@ __device__ v3 path_trace(const RenderParams& P, v3 ro, v3 rd, uint32_t seed, Ctr
       // (:406-407) never traced: its two draws only advance the stream (the
       // same state as sample_sphere's)
       if (STATS || k + 1 < P.sss_bounces) {
-        sss_thr = mul(sss_thr, muls(sss_albedo, exp_(-travel / (sss_radius * 1.5f))));
+        sss_thr = mul(sss_thr, muls(sss_albedo, exp_(div1p5_(-travel))));
         so = sub(cp, muls(sn, OFFSET));
         sd = sample_sphere(&rng);
       } else {
@@ -397,7 +401,7 @@ __device__ v3 path_trace_fused(const RenderParams& P, v3 ro, v3 rd, uint32_t see
         }
       }
       const v3 thr_k = mul(thr, sss_thr);
-      sss_thr = mul(sss_thr, muls(sss_albedo, exp_(-travel / (sss_radius * 1.5f))));
+      sss_thr = mul(sss_thr, muls(sss_albedo, exp_(div1p5_(-travel))));
       so = sub(cp, muls(sn, OFFSET));
       sd = sample_sphere(&rng);
       PT_WALK4(true, walk_pair<CNT>(P, NL > 0 && s_need, s_o, s_d, s_lim, &occ, k + 1 < P.sss_bounces, so, sd, cand, &sh, c));

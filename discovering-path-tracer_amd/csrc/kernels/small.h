@@ -137,20 +137,32 @@ __global__ __launch_bounds__(256) void math_kernel(int fn, const float* __restri
 // definitions (pt_math.h): every one of the 2^32 input bit patterns.
 // fn 0 rcp_ vs 1/x, 1 log_, 2 exp_, 3 acos_ (each vs its FAST=false
 // form).  NaN results compare equal when both are NaN.
+// The wave-uniform fast forms are checked on their pieces, since consecutive
+// inputs share a wave and the guarded function would answer the 63 inputs next
+// to a range boundary from the IEEE side: fn 4 sqrt_in_range(x) implies
+// sqrt_fast_(x) is __builtin_sqrtf(x), 5 rcp_in_range(x) implies rcp_fast_(x)
+// is 1/x, 7 div1p5_in_range(x) implies div1p5_fast_(x) is x / 1.5f (an input
+// out of range counts as equal).  fn 6: sincos_ against sin_ and cos_, both
+// results.
 __global__ __launch_bounds__(256) void exhaustive_kernel(int fn, unsigned long long* bad, uint32_t* first_bad) {
   unsigned long long nbad = 0;
   uint32_t first = 0xffffffffu;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32); i += stride) {
     const float x = __uint_as_float((uint32_t)i);
-    float a, b;
+    float a, b, a2 = 0.0f, b2 = 0.0f;
     switch (fn) {
       case 0: a = rcp_(x); b = 1.0f / x; break;
       case 1: a = log_(x); b = log_impl<false>(x); break;
       case 2: a = exp_(x); b = exp_impl<false>(x); break;
+      case 4: b = __builtin_sqrtf(x); a = sqrt_in_range(x) ? sqrt_fast_(x) : b; break;
+      case 5: b = 1.0f / x; a = rcp_in_range(x) ? rcp_fast_(x) : b; break;
+      case 6: sincos_(x, &a, &a2); b = sin_(x); b2 = cos_(x); break;
+      case 7: b = x / 1.5f; a = div1p5_in_range(x) ? div1p5_fast_(x) : b; break;
       default: a = acos_(x); b = acos_impl<false>(x); break;
     }
-    const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
+    const bool same = (__float_as_uint(a) == __float_as_uint(b) || (a != a && b != b)) &&
+                      (__float_as_uint(a2) == __float_as_uint(b2) || (a2 != a2 && b2 != b2));
     if (!same) {
       ++nbad;
       first = min(first, (uint32_t)i);

@@ -5,8 +5,11 @@
 // namespace ptd's anonymous namespace.
 
 // Ray generation + shading up to the primary trace (path_step from PH_BEGIN).
+// Four blocks per CU: left to itself the compiler takes 129 VGPRs behind the
+// wave-uniform rcp_ guards (119 with the per-lane ones) and drops to three
+// waves per SIMD; held at 128 it spills nothing.
 template <bool CNT>
-__global__ __launch_bounds__(256) void wf_gen_kernel(RenderParams P, WfBuffers B, long long n, long long g0) {
+__global__ __launch_bounds__(256, 4) void wf_gen_kernel(RenderParams P, WfBuffers B, long long n, long long g0) {
   const long long g = g0 + (long long)blockIdx.x * 256 + threadIdx.x;   // paths [g0, g0 + n)
   bool need = false, gen = false;
   Trav T;

@@ -35,7 +35,6 @@ PT_FN float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
 PT_FN float fmin_(float a, float b) { return __builtin_fminf(a, b); }
 PT_FN float fmax_(float a, float b) { return __builtin_fmaxf(a, b); }
 PT_FN float fabs_(float a) { return __builtin_fabsf(a); }
-PT_FN float sqrt_(float a) { return __builtin_sqrtf(a); }
 PT_FN float floor_(float a) { return __builtin_floorf(a); }
 // explicit fused multiply-add (one rounding; -ffp-contract=off never forms it)
 PT_FN float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -54,19 +53,91 @@ PT_FN float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 #define PT_FAST_DEV 0
 #endif
 
+// A fast form comes in two pieces: a per-lane predicate NAME_in_range(x) and
+// the unguarded form NAME_fast_(x), which is bitwise the IEEE result wherever
+// the predicate holds (pt_selftest_exhaustive checks exactly that implication
+// for all 2^32 inputs, on the pieces: consecutive inputs share a wave, so a
+// check through the guarded function would never run the fast form next to a
+// range boundary).  The guard is wave-uniform: the fast form runs only when no
+// active lane of the wave is out of range -- a ballot and one scalar branch
+// instead of a per-lane exec-mask sequence with its merge moves -- and
+// otherwise the whole wave takes the IEEE form, which is right for every lane.
+#if PT_FAST_DEV
+__device__ static inline bool wave_all_(bool ok) { return __builtin_amdgcn_ballot_w64(!ok) == 0ull; }
+#endif
+
 // RN(1/x): estimate y ~ 1/x (1 ulp), e = 1 - x*y exactly enough in one fma,
 // y + e*y rounds to 1/x.  Zeros, infinities, NaNs, subnormal x and |x| so
-// large that 1/x is subnormal take the IEEE division.
+// large that 1/x is subnormal are out of range.
+PT_FN bool rcp_in_range(float x) {
+  const float ax = __builtin_fabsf(x);
+  return ax >= 0x1p-126f && ax <= 0x1p126f;
+}
+#if defined(__HIP__)   // device functions: declared in both passes of a HIP compile
+__device__ static inline float rcp_fast_(float x) {
+  const float y = __builtin_amdgcn_rcpf(x);
+  const float e = __builtin_fmaf(-x, y, 1.0f);
+  return __builtin_fmaf(e, y, y);
+}
+#endif
 PT_FN float rcp_(float x) {
 #if PT_FAST_DEV
-  const float ax = __builtin_fabsf(x);
-  if (ax >= 0x1p-126f && ax <= 0x1p126f) {
-    const float y = __builtin_amdgcn_rcpf(x);
-    const float e = __builtin_fmaf(-x, y, 1.0f);
-    return __builtin_fmaf(e, y, y);
-  }
+  if (wave_all_(rcp_in_range(x))) return rcp_fast_(x);
 #endif
   return 1.0f / x;
+}
+
+// RN(sqrt(a)): the hardware estimate s (1 ulp), then the compiler's own
+// correction -- the candidates one ulp below and above s, chosen by the sign
+// of their fma residuals a - s_down * s and a - s_up * s -- without the
+// scaling by 2^32 and back and the class test that __builtin_sqrtf wraps
+// around it for inputs below 2^-96 (where the residual fma would underflow),
+// zeros and infinities.  Out of range: a < 2^-96 (zeros, -0 from a Gaussian
+// draw of exactly 1.0, subnormals, negatives), inf and NaN.
+PT_FN bool sqrt_in_range(float a) { return a >= 0x1p-96f && a <= 0x1.fffffep+127f; }
+#if defined(__HIP__)
+__device__ static inline float sqrt_fast_(float a) {
+  float s = __builtin_amdgcn_sqrtf(a);
+  const float dn = u2f(f2u(s) - 1u), up = u2f(f2u(s) + 1u);
+  const float rd = __builtin_fmaf(-dn, s, a);
+  const float ru = __builtin_fmaf(-up, s, a);
+  s = rd <= 0.0f ? dn : s;
+  s = ru > 0.0f ? up : s;
+  return s;
+}
+#endif
+PT_FN float sqrt_(float a) {
+#if PT_FAST_DEV
+  if (wave_all_(sqrt_in_range(a))) return sqrt_fast_(a);
+#endif
+  return __builtin_sqrtf(a);
+}
+
+// x / 1.5f (the SSS step's -travel / (sss_radius * 1.5f)) without the IEEE
+// division: y = RN(1 / 1.5f), q = x * y, one remainder correction.  Plain
+// C++, so tests/math_forms_check.cpp proves it on the host: for all 2^32 x,
+// div1p5_in_range(x) implies div1p5_fast_(x) is bitwise x / 1.5f
+// (pt_selftest_exhaustive fn 7: the same on the device).  The checker finds
+// three inputs at which the fast form differs, none of them finite and
+// nonzero: -0 (the remainder is +0 and its sign wins: +0 for -0) and the two
+// infinities (the remainder is NaN).  Subnormal x, q and r hold.  In range is
+// therefore every finite nonzero x.
+constexpr float kDiv1p5Lo = 0x1p-149f;
+PT_FN bool div1p5_in_range(float x) {
+  const float ax = __builtin_fabsf(x);
+  return ax >= kDiv1p5Lo && ax <= 0x1.fffffep+127f;
+}
+PT_FN float div1p5_fast_(float x) {
+  const float y = 0x1.555556p-1f;
+  const float q = x * y;
+  const float r = __builtin_fmaf(-1.5f, q, x);
+  return __builtin_fmaf(r, y, q);
+}
+PT_FN float div1p5_(float x) {
+#if PT_FAST_DEV
+  if (wave_all_(div1p5_in_range(x))) return div1p5_fast_(x);
+#endif
+  return x / 1.5f;
 }
 
 // a/b via q = a*RN(1/b) and one remainder correction (Markstein); used only
@@ -189,7 +260,11 @@ PT_FN float cos_(float x) {
   }
 }
 // sin and cos of one argument sharing the reduction: bitwise the same as
-// sin_(x) and cos_(x).
+// sin_(x) and cos_(x).  (A form that selects the two kernels by the quadrant's
+// low bit and flips their sign bits instead of switching is bitwise the same
+// on the host and the device -- tests/math_forms_check.cpp, pt_selftest_exhaustive
+// fn 6 -- and removes four saveexec a site, but measured no faster on the
+// headline frame: profiles/forms.)
 PT_FN void sincos_(float x, float* s, float* c) {
   int q;
   const float r = reduce_(x, &q);

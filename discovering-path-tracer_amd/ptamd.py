@@ -330,7 +330,9 @@ def device_math(fn, x, device=0):
 def device_math_exhaustive(fn, device=0):
     """pt_selftest_exhaustive: (mismatching inputs, smallest such bit pattern)
     of the device's fast-quotient fn (0 rcp, 1 log, 2 exp, 3 acos)
-    against its IEEE definition over all 2^32 inputs."""
+    against its IEEE definition over all 2^32 inputs; 4 sqrt, 5 rcp and
+    7 x / 1.5f check the unguarded fast form wherever its range predicate
+    holds, 6 sincos against sin and cos."""
     bad = ctypes.c_ulonglong(0)
     first = ctypes.c_uint32(0)
     _check(lib().pt_selftest_exhaustive(device, fn, ctypes.byref(bad), ctypes.byref(first)),

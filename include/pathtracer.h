@@ -937,6 +937,9 @@ int pt_reset_launch_times(pt_context* ctx);
 int pt_selftest_math(int device_ordinal, int fn, const float* x, float* y, size_t n);
 /* Exhaustive check of the device's fast-quotient math against its IEEE
  * definitions over all 2^32 inputs: fn 0 rcp (1/x), 1 log, 2 exp, 3 acos.
+ * The wave-uniform fast forms on their pieces (an input inside the form's
+ * range must give the IEEE bits from the unguarded form): fn 4 sqrt, 5 rcp,
+ * 7 x / 1.5f; fn 6 sincos against sin and cos, both results.
  * Writes the number of differing inputs and the smallest such
  * input's bit pattern (0xffffffff if none). */
 int pt_selftest_exhaustive(int device, int fn, unsigned long long* mismatches, uint32_t* first_bad);
