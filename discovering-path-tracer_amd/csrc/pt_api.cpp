@@ -679,11 +679,9 @@ static int render_params(pt_context* c, const LaunchPlan& plan, uint32_t first_b
   return PT_OK;
 }
 
-// The cull rectangles and the item lists of the frame; mixed lanes where the plan admits them and the
-// frame has rectangles.  (Stats mode derives no rectangles, so its launches never mix lanes.)
-static int cull_and_items(pt_context* c, const LaunchPlan& plan, uint32_t n_batches, ptd::RenderParams* p) {
+// The cull rectangles of the frame (stats mode derives none), loose and tight.
+static void cull_rectangles(const pt_context* c, ptd::RenderParams* p) {
   p->n_cull = -1;
-  c->last_mix = 0;
   if (c->opt_cull && !c->stats_mode)
     p->n_cull = ptd::cull_rects(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
                                 c->n_lights, &p->cull[0][0], ptd::kMaxCullRects);
@@ -696,6 +694,13 @@ static int cull_and_items(pt_context* c, const LaunchPlan& plan, uint32_t n_batc
                                       c->n_lights, &p->cull_tight[0][0], ptd::kMaxCullRects, ptd::kCullTightR);
     if (p->n_cull_tight != p->n_cull) p->n_cull_tight = -1;
   }
+}
+
+// The cull rectangles and the item lists of the frame; mixed lanes where the plan admits them and the
+// frame has rectangles.  (Stats mode derives no rectangles, so its launches never mix lanes.)
+static int cull_and_items(pt_context* c, const LaunchPlan& plan, uint32_t n_batches, ptd::RenderParams* p) {
+  c->last_mix = 0;
+  cull_rectangles(c, p);
   if (p->n_cull < 0) return PT_OK;
   MixPlan mix;
   const bool mixed = plan.mixed_eligible;
@@ -859,6 +864,7 @@ static int render_packed_wavefront(pt_context* c, const LaunchPlan& plan, ptd::R
 int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4* pack_out, const Assembly& as,
                 Launched* launched) {
   { const int rc = render_ready(c); if (rc) return rc; }
+  adaptive_forget(c);   // an ordinary render ends an adaptive one
   const bool packed = pack_out != nullptr;
   ptd::RenderParams p{};   // what is not set below is 0 or null: no wide walk, item list, packed output, assembly
   frame_params(c, c->stats_mode, &p);
@@ -913,6 +919,26 @@ int render_impl(pt_context* c, uint32_t first_batch, uint32_t n_batches, float4*
   { const int rc = timing_end(c, timer); if (rc) return rc; }
   moments_close(c, moments, first_batch, n_batches);
   culled_after(c, culled, packed, c->opt_fresh != 0, first_batch, n_batches);
+  return PT_OK;
+}
+
+// The parameters of an adaptive round's launch (pt_adaptive.cpp): render_impl's scene, frame, camera and
+// option fields under the adaptive plan, the cull rectangles, and neither item list nor packed output; the
+// batches are the live list's.
+int adaptive_render_params(pt_context* c, const AdaptivePlan& ap, int spl, ptd::RenderParams* p) {
+  { const int rc = render_ready(c); if (rc) return rc; }
+  if (c->n_lights < 1) return fail(PT_ERR_INVALID, "no lights uploaded");
+  frame_params(c, false, p);
+  LaunchPlan plan;
+  plan.spl = spl;
+  plan.lds = ap.lds;
+  plan.exit_skip = ap.exit_skip;
+  plan.sweep = ap.sweep != 0;
+  plan.sweep_hull = ap.sweep >= 2;
+  plan.sweep_cube = ap.sweep == 3;
+  { const int rc = render_params(c, plan, 0, 0, false, p); if (rc) return rc; }
+  p->moments = c->d_moments;
+  cull_rectangles(c, p);
   return PT_OK;
 }
 
@@ -1050,6 +1076,7 @@ int pt_destroy(pt_context* c) {
   dev_free(c->wf_block);
   dev_free(c->d_moments);
   post_release(c);
+  adaptive_release(c);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1135,6 +1162,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->has_scene = false;
   c->guide_valid = false;
   temporal_forget(c);
+  adaptive_forget(c);
   const int T = (int)(n_indices / 3);
   struct Staging {   // vertex/index copies live only until the triangle records are built
     float* v = nullptr;
@@ -1223,6 +1251,7 @@ int pt_upload_lights(pt_context* c, const pt_area_light* lights, size_t n) {
   c->n_lights = 0;
   c->lights_host.clear();
   temporal_forget(c);
+  adaptive_forget(c);
   if (n) {
     PT_HIP(hipMalloc((void**)&c->d_lights, n * sizeof(ptd::LightRec)));
     PT_HIP(hipMalloc((void**)&c->d_lights_dev, n * sizeof(ptd::LightDev)));
@@ -1252,6 +1281,7 @@ int pt_set_params(pt_context* c, const pt_params* p) {
     return fail(PT_ERR_INVALID, "max_depth and sss_bounces must be in [0,64]");
   c->params = *p;
   temporal_forget(c);
+  adaptive_forget(c);
   return PT_OK;
 }
 
@@ -1287,6 +1317,7 @@ int pt_set_partition_slots(pt_context* c, int nranks, int rank, const int* slots
 
 // The moments image back to "no batches": zeros, on the context's stream.
 static int moments_zero(pt_context* c) {
+  adaptive_forget(c);   // a cleared or newly bound image holds no adaptive render
   c->moments_valid = false;
   c->moments_n = 0;
   const size_t n = (size_t)c->width * c->height;

@@ -3,7 +3,8 @@
 // (create/destroy, uploads, item lists, render_impl and its steps, options,
 // exchange, stats, timing); pt_plan.h the launch plan, every policy render_impl
 // carries out, as one pure function (plan_launch); pt_post.cpp the
-// post-processing chain (guide, filters, temporal accumulation); pt_dist.cpp
+// post-processing chain (guide, filters, temporal accumulation);
+// pt_adaptive.cpp adaptive sampling; pt_dist.cpp
 // the RCCL step loop; pt_group.cpp the multi-device context.  The fields of
 // pt_context are grouped in that order.
 #pragma once
@@ -275,6 +276,21 @@ struct pt_context {
   float* d_spatial_var = nullptr;      // pt_temporal_denoise_spatial's variance plane
   size_t spatial_var_cap = 0;
 
+  // ---- pt_adaptive.cpp: adaptive sampling (freed by adaptive_release) ---------------------
+  bool ad_active = false;              // between pt_adaptive_begin and what ends the state (adaptive_forget)
+  pt_adaptive_params ad_params{};
+  uint32_t ad_rounds_done = 0, ad_rounds = 0;   // rounds enqueued since begin; rounds that can change a count
+  int ad_tiles = 0;                    // tiles of the frame the state was begun on
+  uint32_t* d_ad_counts = nullptr;     // per tile (raster order): n_T once the enqueued rounds have run
+  uint32_t* d_ad_added = nullptr;      // ... and the batches the last round added (0: not live)
+  float* d_ad_errors = nullptr;        // ... and E_T of the last round's rule
+  int4* d_ad_list = nullptr;           // the last round's live list
+  size_t ad_cap[4] = {0, 0, 0, 0};     // tiles the four hold
+  int* d_ad_live = nullptr;            // the list's length
+  float* d_ad_var = nullptr;           // pt_adaptive_denoise's variance plane
+  size_t ad_var_cap = 0;
+  bool ad_var_valid = false;
+
   // ---- pt_dist.cpp, pt_group.cpp ------------------------------------------------------
   DistState* dist = nullptr;           // pt_dist_init
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -287,6 +303,13 @@ inline void temporal_forget(pt_context* c) {
   c->t_frames = 0;
   c->t_samples = 0;
   c->t_guide_aside = false;
+}
+
+// The adaptive state ends (a scene, light or params upload, a resize, a rebind, pt_clear_accum, any render):
+// pt_adaptive_advance and the reads then ask for a new pt_adaptive_begin.  The buffers stay.
+inline void adaptive_forget(pt_context* c) {
+  c->ad_active = false;
+  c->ad_var_valid = false;
 }
 
 // Before a launch that writes context-owned buffers: wait for the previous
@@ -397,6 +420,16 @@ int unpack_table(pt_context* c, const ptd::RenderParams& p, const std::vector<fl
 
 // ---- and what they give the core --------------------------------------------------------------
 void post_release(pt_context* c);      // frees what pt_post.cpp allocates (pt_destroy)
+void adaptive_release(pt_context* c);  // ... and pt_adaptive.cpp
+// ---- what pt_post.cpp gives pt_adaptive.cpp: the variance-guided filter's passes from a variance plane
+// (pt_post.cpp var_filter), and the validated filter parameters
+int post_var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,
+                    const float4* guide, float4* dst);
+int post_denoise_var_params(const pt_denoise_var_params* in, pt_denoise_var_params* p);
+// ---- what the core gives pt_adaptive.cpp: the checks and the parameters of a path-recursive launch of the
+// whole frame under an adaptive plan (no item list, no fill; the cull rectangles as render_impl derives them)
+struct AdaptivePlan;
+int adaptive_render_params(pt_context* c, const AdaptivePlan& ap, int spl, ptd::RenderParams* p);
 int dist_synchronize(pt_context* c);   // pt_synchronize's share of the step loop: its render and gather streams
 
 #pragma GCC visibility pop

@@ -25,7 +25,9 @@
 // (atrous_var_pixel: pt_denoise_var, pt_denoise_var_host), stated the same way,
 // temporal reprojection (reproject_pixel: pt_reproject, pt_reproject_host) and
 // the spatial variance estimate of pixels with a short history
-// (spatial_var_pixel: pt_spatial_variance, pt_spatial_variance_host).
+// (spatial_var_pixel: pt_spatial_variance, pt_spatial_variance_host), and
+// last the stopping rule of adaptive sampling (adaptive_error, adaptive_next:
+// pt_adaptive_select, pt_adaptive_select_host).
 #pragma once
 #include "pt_math.h"
 
@@ -448,9 +450,79 @@ struct SpatialImageFetch {
   }
 };
 
+// ---- adaptive sampling: the stopping rule (pt_adaptive_select) ---------------
+// Per 16x16 tile (raster order) with count n and each of its pixels p inside
+// the frame, from the moments {m1, m2}:
+//   finite_p = fabs(m1_p) <= FLT_MAX && fabs(m2_p) <= FLT_MAX
+//   e_p = finite_p ? sqrt_(var_of_mean(m1_p, m2_p, n)) / fmax_(m1_p, lum_floor) : +inf
+//   pixel converged: e_p <= threshold;   tile converged: every such pixel is
+//   E_T  = fmax_ over those pixels of e_p, from +0
+//   next = n if converged or n >= max_batches, else min(n + step, max_batches)
+// fmax_ is minNum/maxNum, which would swallow a NaN moment (the clamp gives var
+// 0, the floor the denominator): finite_p keeps such a pixel, and one with an
+// infinite moment, from ever counting as converged.  With finite moments e_p is
+// finite and >= +0 (the denominator is at least lum_floor > 0), so the all-of
+// predicate and the maximum do not depend on the order of the reduction.
+struct AdaptiveParams {
+  uint32_t min_batches, max_batches, step;
+  float threshold, lum_floor;
+};
+PT_FN bool adaptive_params_ok(uint32_t min_batches, uint32_t max_batches, uint32_t step, float threshold,
+                              float lum_floor) {
+  const float big = 3.40282347e38f;
+  return min_batches >= 2u && max_batches >= min_batches && max_batches <= 65536u && step >= 1u &&
+         threshold > 0.0f && threshold <= big && lum_floor > 0.0f && lum_floor <= big;
+}
+PT_FN float adaptive_error(float m1, float m2, uint32_t n, float lum_floor) {
+  const float big = 3.40282347e38f;
+  if (!(fabs_(m1) <= big && fabs_(m2) <= big)) return u2f(0x7f800000u);
+  return sqrt_(var_of_mean(m1, m2, n)) / fmax_(m1, lum_floor);
+}
+PT_FN uint32_t adaptive_next(uint32_t n, bool converged, const AdaptiveParams& a) {
+  if (converged || n >= a.max_batches) return n;
+  return a.max_batches - n < a.step ? a.max_batches : n + a.step;
+}
+// The rule over a whole W x H image on the host, tiles in raster order (pt_adaptive_select_host; the kernel is
+// pt_denoise.hip's adaptive_select_kernel): moments W*H*2 floats, counts, next and errors one per tile; errors
+// may be null.
+inline void adaptive_select_image(const float* moments, const uint32_t* counts, int W, int H, const AdaptiveParams& a,
+                                  uint32_t* next, float* errors) {
+  const int bx = (W + 15) / 16, by = (H + 15) / 16;
+  for (int ty = 0; ty < by; ++ty)
+    for (int tx = 0; tx < bx; ++tx) {
+      const int b = ty * bx + tx;
+      const uint32_t n = counts[b];
+      bool conv = true;
+      float e = 0.0f;
+      for (int y = ty * 16; y < ty * 16 + 16 && y < H; ++y)
+        for (int x = tx * 16; x < tx * 16 + 16 && x < W; ++x) {
+          const size_t i = (size_t)y * (size_t)W + (size_t)x;
+          const float ep = adaptive_error(moments[2 * i], moments[2 * i + 1], n, a.lum_floor);
+          conv = conv && ep <= a.threshold;
+          e = fmax_(e, ep);
+        }
+      next[b] = adaptive_next(n, conv, a);
+      if (errors) errors[b] = e;
+    }
+}
+
 }  // namespace ptdn
 
 namespace ptd {
+// The rule per tile (pt_denoise.hip adaptive_select_kernel): next and errors per tile in raster order; added
+// (or null) receives next - counts.  counts == next is allowed: a tile's wave reads its count before it writes.
+hipError_t launch_adaptive_select(const float2* moments, const uint32_t* counts, int width, int height,
+                                  const ptdn::AdaptiveParams& a, uint32_t* next, float* errors, uint32_t* added,
+                                  hipStream_t stream);
+// The live list of a round from `added` (tiles with added != 0, ascending): entries {x0, y0, first_batch =
+// counts - added, n_batches = added}, their number in *n_live.  One workgroup, a scan: the list's order is fixed.
+hipError_t launch_adaptive_compact(const uint32_t* counts, const uint32_t* added, int width, int height, int4* list,
+                                   int* n_live, hipStream_t stream);
+// counts = added = n for every tile (round 0: all tiles render batches 0..n-1).
+hipError_t launch_adaptive_fill(uint32_t* counts, uint32_t* added, int n_tiles, uint32_t n, hipStream_t stream);
+// var[p] = var_of_mean(m1_p, m2_p, counts[tile of p]).
+hipError_t launch_adaptive_var(const float2* moments, const uint32_t* counts, float* var, int width, int height,
+                               hipStream_t stream);
 // The estimate's launch (pt_denoise.hip spatial_var_kernel): out, distinct from
 // the four inputs, receives var where len >= below and the statement elsewhere.
 hipError_t launch_spatial_var(const float2* moments, const float* length, const float* variance, const float4* guide,

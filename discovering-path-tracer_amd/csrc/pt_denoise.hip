@@ -1,7 +1,9 @@
 // pt_denoise.hip — the edge-avoiding a-trous filter's pass kernels
 // (pt_denoise), those of the variance-guided filter (pt_denoise_var, below),
-// the temporal reprojection kernel (pt_reproject) and the spatial variance
-// estimate of short histories (pt_spatial_variance, last); the statements are
+// the temporal reprojection kernel (pt_reproject), the spatial variance
+// estimate of short histories (pt_spatial_variance) and the adaptive stopping
+// rule with its live list and variance plane (pt_adaptive_select,
+// pt_adaptive_advance, pt_adaptive_denoise; last); the statements are
 // pt_denoise.h, shared with the host.
 //
 // One pixel per lane, 16x16 pixels per workgroup, a wave a 16x4 strip: the
@@ -201,7 +203,133 @@ __global__ __launch_bounds__(256) void spatial_var_kernel(const float2* __restri
   out[i] = v;
 }
 
+// ---- adaptive sampling: the stopping rule per tile (pt_denoise.h adaptive_error) ----
+// One wave per 16x16 tile, four tiles per workgroup.  Lane l takes the pixels
+// (l & 15, (l >> 4) + 4k), k = 0..3: per k the wave reads four tile rows, 128
+// consecutive bytes of moments each.  A pixel outside the frame is not read and
+// counts as converged with e = +0 by a select, not a branch, so every lane of
+// the wave reaches the ballot and the shuffles; only whole waves past the last
+// tile leave, on a wave-uniform test.  The predicate is reduced by a ballot, the
+// error by a butterfly of maxima (order-free: e is never NaN); lane 0 writes.
+__global__ __launch_bounds__(256) void adaptive_select_kernel(const float2* __restrict__ moments,
+                                                              const uint32_t* __restrict__ counts, int W, int H,
+                                                              int blocks_x, int n_tiles, AdaptiveParams a,
+                                                              uint32_t* __restrict__ next, float* __restrict__ errors,
+                                                              uint32_t* __restrict__ added) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+  const int b = (int)blockIdx.x * 4 + wave;
+  if (b >= n_tiles) return;   // wave-uniform
+  const uint32_t n = counts[b];
+  const int x = (b % blocks_x) * 16 + (lane & 15);
+  const int y0 = (b / blocks_x) * 16 + (lane >> 4);
+  bool conv = true;
+  float e = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = y0 + 4 * k;
+    const bool in = x < W && y < H;
+    float2 m = make_float2(0.0f, 0.0f);
+    if (in) m = moments[(size_t)y * (size_t)W + (size_t)x];
+    const float ep = adaptive_error(m.x, m.y, n, a.lum_floor);   // of +0 moments: +0
+    conv = conv && (!in || ep <= a.threshold);
+    e = fmax_(e, in ? ep : 0.0f);
+  }
+  const bool tile_conv = __builtin_amdgcn_ballot_w64(!conv) == 0ull;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) e = fmax_(e, __shfl_xor(e, off, 64));
+  if (lane == 0) {
+    const uint32_t nx = adaptive_next(n, tile_conv, a);
+    next[b] = nx;
+    errors[b] = e;
+    if (added) added[b] = nx - n;
+  }
+}
+
+// The live list: thread t takes the tiles [t * per, (t + 1) * per), counts its live ones, the
+// workgroup scans the 256 counts (a wave's by shuffles, the four waves' totals through LDS), and
+// each thread writes its entries from its offset on -- ascending tile order, no atomics.
+__global__ __launch_bounds__(256) void adaptive_compact_kernel(const uint32_t* __restrict__ counts,
+                                                               const uint32_t* __restrict__ added, int blocks_x,
+                                                               int n_tiles, int4* __restrict__ list,
+                                                               int* __restrict__ n_live) {
+  __shared__ int wave_total[4];
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int per = (n_tiles + 255) / 256;
+  const int lo = min(t * per, n_tiles), hi = min(lo + per, n_tiles);
+  int mine = 0;
+  for (int b = lo; b < hi; ++b) mine += added[b] != 0u ? 1 : 0;
+  int incl = mine;   // inclusive scan within the wave
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  if (lane == 63) wave_total[wave] = incl;
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += wave_total[w];
+  int pos = base + incl - mine;
+  for (int b = lo; b < hi; ++b) {
+    const uint32_t ad = added[b];
+    if (ad == 0u) continue;
+    list[pos++] = make_int4((b % blocks_x) * 16, (b / blocks_x) * 16, (int)(counts[b] - ad), (int)ad);
+  }
+  if (t == 255) *n_live = base + incl;
+}
+
+__global__ __launch_bounds__(256) void adaptive_fill_kernel(uint32_t* __restrict__ counts, uint32_t* __restrict__ added,
+                                                            int n_tiles, uint32_t n) {
+  const int b = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (b >= n_tiles) return;
+  counts[b] = n;
+  added[b] = n;
+}
+
+// The variance plane of an adaptive render: the variance of the mean at each tile's own count.
+__global__ __launch_bounds__(256) void adaptive_var_kernel(const float2* __restrict__ moments,
+                                                           const uint32_t* __restrict__ counts,
+                                                           float* __restrict__ var, int W, int H) {
+  const int x = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+  const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const size_t i = (size_t)y * (size_t)W + (size_t)x;
+  const float2 m = moments[i];
+  var[i] = var_of_mean(m.x, m.y, counts[blockIdx.y * gridDim.x + blockIdx.x]);
+}
+
 }  // namespace
+
+hipError_t launch_adaptive_select(const float2* moments, const uint32_t* counts, int width, int height,
+                                  const AdaptiveParams& a, uint32_t* next, float* errors, uint32_t* added,
+                                  hipStream_t stream) {
+  if (width <= 0 || height <= 0) return hipErrorInvalidValue;
+  const int bx = (width + 15) / 16, n_tiles = bx * ((height + 15) / 16);
+  adaptive_select_kernel<<<(unsigned)((n_tiles + 3) / 4), 256, 0, stream>>>(moments, counts, width, height, bx, n_tiles,
+                                                                           a, next, errors, added);
+  return hipGetLastError();
+}
+
+hipError_t launch_adaptive_compact(const uint32_t* counts, const uint32_t* added, int width, int height, int4* list,
+                                   int* n_live, hipStream_t stream) {
+  if (width <= 0 || height <= 0) return hipErrorInvalidValue;
+  const int bx = (width + 15) / 16, n_tiles = bx * ((height + 15) / 16);
+  adaptive_compact_kernel<<<1, 256, 0, stream>>>(counts, added, bx, n_tiles, list, n_live);
+  return hipGetLastError();
+}
+
+hipError_t launch_adaptive_fill(uint32_t* counts, uint32_t* added, int n_tiles, uint32_t n, hipStream_t stream) {
+  if (n_tiles <= 0) return hipErrorInvalidValue;
+  adaptive_fill_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, stream>>>(counts, added, n_tiles, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_adaptive_var(const float2* moments, const uint32_t* counts, float* var, int width, int height,
+                               hipStream_t stream) {
+  if (width <= 0 || height <= 0) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+  adaptive_var_kernel<<<grid, 256, 0, stream>>>(moments, counts, var, width, height);
+  return hipGetLastError();
+}
 
 hipError_t launch_spatial_var(const float2* moments, const float* length, const float* variance, const float4* guide,
                               float* out, int width, int height, uint32_t below, int radius, float sn2, float sz2,

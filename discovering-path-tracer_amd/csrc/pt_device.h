@@ -221,6 +221,10 @@ inline size_t scene_lds_bytes(const RenderParams& p) {
 inline size_t sweep_lds_bytes(const RenderParams& p) { return (size_t)3 * p.sweep_leaves * 16; }
 // cnt: the fast kernel with traced-work counters (PT_OPT_COUNT_TRACED)
 hipError_t launch_render(const RenderParams& p, bool stats, bool lds_scene, hipStream_t stream, bool cnt = false);
+// One adaptive round (kernels/adaptive.h): blocks_total * spl workgroups; workgroup i serves part i % spl of
+// list[i / spl] = {x0, y0, first_batch, n_batches} and leaves when i / spl >= *n_live (both device memory).
+hipError_t launch_render_adaptive(const RenderParams& p, bool lds_scene, const int4* list, const int* n_live,
+                                  hipStream_t stream);
 // Wavefront pipeline (PT_OPT_KERNEL 3): one path per (pixel, sample) held in
 // HBM; generate, then alternate a persistent traversal kernel over the list of
 // paths waiting for a ray and a shading kernel that consumes the hits and
@@ -474,6 +478,52 @@ inline WfLaunch plan_wavefront(const RenderParams& p, long long cap, bool lds_sc
   return l;
 }
 
+// ... and of launch_render_adaptive's (an adaptive round, kernels/adaptive.h): the MOMENTS instantiations
+// of render_kernel have one sibling each, picked by the same rule (pick_render with moments and neither
+// stats, counters nor a packed output).
+struct AdaptiveVariant {   // render_adaptive_kernel<LDS, SWEEP, EXIT>
+  bool lds;
+  int sweep;
+  bool exit;
+};
+constexpr bool operator==(const AdaptiveVariant& a, const AdaptiveVariant& b) {
+  return a.lds == b.lds && a.sweep == b.sweep && a.exit == b.exit;
+}
+#define PT_ADAPTIVE_VARIANTS(X) \
+  X(true, 2, false) X(true, 1, false) X(true, 3, false) X(false, 0, true) X(false, 0, false) X(true, 0, false)
+#define PT_VARIANT_ROW(...) {__VA_ARGS__},
+constexpr AdaptiveVariant kAdaptiveVariants[] = {PT_ADAPTIVE_VARIANTS(PT_VARIANT_ROW)};
+#undef PT_VARIANT_ROW
+constexpr AdaptiveVariant pick_adaptive(bool lds_scene, int sweep_table, bool exit_skip) {
+  const RenderVariant v = pick_render(false, lds_scene, false, sweep_table, true, exit_skip, false).v;
+  return {v.lds, v.sweep, v.exit};
+}
+struct AdaptiveLaunch {
+  Launch what = Launch::Refused;
+  long long grid = 0;   // workgroups: every tile's parts, whatever the live list holds
+  size_t lds = 0;       // dynamic LDS bytes
+  AdaptiveVariant v = {};
+};
+// The launch over the frame's blocks_total tiles at p.spl lanes; the batches are the list's, p's are not read.
+inline AdaptiveLaunch plan_render_adaptive(const RenderParams& p, bool lds_scene) {
+  AdaptiveLaunch l;
+  if (!spl_valid(p.spl) || !p.moments || p.pack_out || p.items || p.mix || p.nranks != 1) return l;
+  l.grid = (long long)p.blocks_total * p.spl;
+  if (l.grid <= 0) {
+    l.what = Launch::Nothing;
+    return l;
+  }
+  if (l.grid > 0x7fffffffll) return l;
+  const int table = !p.sweep ? 0 : p.sweep_cube ? 3 : p.sweep_hull ? 2 : 1;
+  const AdaptiveVariant v = pick_adaptive(lds_scene, table, p.exit_skip != 0);
+  if (v.sweep && (p.sweep_boxes < 1 || p.sweep_boxes > 64 || p.sweep_leaves < 1 || p.sweep_leaves > 32)) return l;
+  l.lds = v.sweep ? sweep_lds_bytes(p) : lds_scene ? scene_lds_bytes(p) : 0;
+  if (l.lds > kMaxSceneLds) return l;
+  l.v = v;
+  l.what = Launch::Run;
+  return l;
+}
+
 // Every listed instantiation is one the picks above can return, and they return no other.
 template <class V, size_t N>
 constexpr bool all_met(const V (&)[N], unsigned met) { return met == (1u << N) - 1u; }
@@ -501,6 +551,17 @@ constexpr bool variant_lists_exact() {
          all_met(kWfShadeVariants, s) && all_met(kWfTailVariants, x);
 }
 static_assert(variant_lists_exact(), "the variant lists and the picks disagree");
+constexpr bool adaptive_list_exact() {
+  unsigned met = 0;
+  bool ok = true;
+  for (int f = 0; f < 16; ++f) {
+    const int i = variant_index(kAdaptiveVariants, pick_adaptive((f & 1) != 0, (f >> 2) & 3, (f & 2) != 0));
+    ok = ok && i >= 0;
+    met |= i >= 0 ? 1u << i : 0u;
+  }
+  return ok && all_met(kAdaptiveVariants, met);
+}
+static_assert(adaptive_list_exact(), "the adaptive variant list and its pick disagree");
 #pragma GCC visibility pop
 
 }  // namespace ptd

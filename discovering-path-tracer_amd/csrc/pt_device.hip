@@ -52,6 +52,7 @@ namespace {
 #include "kernels/wf_wide.h"
 #include "kernels/wf_shade.h"
 #include "kernels/guide.h"
+#include "kernels/adaptive.h"
 
 }  // namespace
 
@@ -310,6 +311,24 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
       if (e != hipSuccess) return e;
     }
   }
+  return hipGetLastError();
+}
+
+namespace {
+// ... and the adaptive round's (last: the kernels before it keep their places in the code object)
+typedef void (*AdaptiveKernel)(RenderParams, const int4*, const int*);
+#define PT_ROW(L, W, E) {{L, W, E}, render_adaptive_kernel<L, W, E>},
+const KernelEntry<AdaptiveVariant, AdaptiveKernel> kAdaptiveKernels[] = {PT_ADAPTIVE_VARIANTS(PT_ROW)};
+#undef PT_ROW
+}  // namespace
+
+hipError_t launch_render_adaptive(const RenderParams& p, bool lds_scene, const int4* list, const int* n_live,
+                                  hipStream_t stream) {
+  const AdaptiveLaunch l = plan_render_adaptive(p, lds_scene);
+  if (l.what == Launch::Nothing) return hipSuccess;
+  const AdaptiveKernel kern = l.what == Launch::Run ? find_kernel(kAdaptiveKernels, l.v) : nullptr;
+  if (!kern || !list || !n_live) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(256), l.lds, stream, p, list, n_live);
   return hipGetLastError();
 }
 

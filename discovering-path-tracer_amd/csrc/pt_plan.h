@@ -193,4 +193,56 @@ inline LaunchPlan plan_launch(const pt_context& c, long long n_tiles, uint32_t n
   return pl;
 }
 
+// The plan of an adaptive render (pt_adaptive_begin / pt_adaptive_advance): what it refuses, the
+// instantiation its rounds run, their lane counts and how many rounds can still change a count.  The
+// walk, LDS and exit-skip choices are plan_launch's for a path-recursive launch; the wavefront pipeline
+// is refused when asked for and never chosen under auto (plan_launch is asked about no tile, so no launch
+// is ever large enough for it).  Lanes: round 0 renders min_batches everywhere and is planned for them,
+// every later round for `step` -- one lane count per launch, never more lanes than samples.
+constexpr const char* kAdaptiveBadParams =
+    "pt_adaptive_params: 2 <= min_batches <= max_batches <= 65536, step >= 1; threshold and lum_floor finite and > 0";
+struct AdaptivePlan {
+  int refuse_code = PT_OK;      // PT_OK / nullptr, or what the call is refused with
+  const char* refuse = nullptr;
+  int spl0 = 0, spl = 0;        // sample lanes of round 0 and of the later rounds
+  bool lds = false;             // the scene is staged in LDS
+  int sweep = 0;                // the sweep walk (0 none, 1 plain, 2 hull, 3 cube)
+  int exit_skip = 0;
+  uint32_t rounds = 0;          // ceil((max_batches - min_batches) / step)
+  ptd::AdaptiveVariant v = {};  // render_adaptive_kernel's instantiation
+};
+inline AdaptivePlan plan_adaptive(const pt_context& c, const pt_adaptive_params& a) {
+  AdaptivePlan ap;
+  auto refuse = [&ap](int code, const char* msg) {
+    if (ap.refuse) return;
+    ap.refuse_code = code;
+    ap.refuse = msg;
+  };
+  if (!(a.min_batches >= 2u && a.max_batches >= a.min_batches && a.max_batches <= 65536u && a.step >= 1u &&
+        a.threshold > 0.0f && a.threshold <= 3.40282347e38f && a.lum_floor > 0.0f && a.lum_floor <= 3.40282347e38f))
+    refuse(PT_ERR_INVALID, kAdaptiveBadParams);
+  if (c.group) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not on a multi-device context (pt_create_multi)");
+  if (c.nranks > 1) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not on a partition of more than one rank");
+  if (c.stats_mode) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not in stats mode");
+  if (c.opt_count) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not with PT_OPT_COUNT_TRACED");
+  if (c.opt_kernel == 3) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: the path-recursive kernel only (PT_OPT_KERNEL 3)");
+  if (!c.opt_moments) refuse(PT_ERR_INVALID, "adaptive sampling: needs PT_OPT_MOMENTS 1");
+  if (ap.refuse) return ap;
+  const LaunchPlan p0 = plan_launch(c, 0, a.min_batches, false);
+  const LaunchPlan p1 = plan_launch(c, 0, a.step, false);
+  if (p0.refuse) {
+    refuse(p0.refuse_code, p0.refuse);
+    return ap;
+  }
+  ap.spl0 = p0.spl;
+  ap.spl = p1.spl;
+  ap.lds = p0.lds;
+  ap.sweep = !p0.sweep ? 0 : p0.sweep_cube ? 3 : p0.sweep_hull ? 2 : 1;
+  ap.exit_skip = p0.exit_skip;
+  ap.rounds = (a.max_batches - a.min_batches + a.step - 1u) / a.step;
+  if (a.step > a.max_batches - a.min_batches) ap.rounds = a.max_batches > a.min_batches ? 1u : 0u;   // no overflow
+  ap.v = ptd::pick_adaptive(ap.lds, ap.sweep, ap.exit_skip != 0);
+  return ap;
+}
+
 #pragma GCC visibility pop

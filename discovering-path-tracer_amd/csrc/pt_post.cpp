@@ -701,3 +701,12 @@ int pt_temporal_denoise_spatial(pt_context* c, const pt_denoise_var_params* para
 }
 
 }  // extern "C"
+
+// ---- for pt_adaptive.cpp (pt_adaptive_denoise) ------------------------------------------
+int post_var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,
+                    const float4* guide, float4* dst) {
+  return var_filter(c, p, src, var0, guide, dst);
+}
+int post_denoise_var_params(const pt_denoise_var_params* in, pt_denoise_var_params* p) {
+  return denoise_var_params(in, p);
+}

@@ -7,6 +7,7 @@
 //             [-fused] [-o out.pfm] [-png out.png] [-device 0 | -devices 0,1,..]
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
 //             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
+//             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F]]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -31,6 +32,11 @@
 // parameters.  -temporal-spatial (with -temporal K) filters the final frame with
 // pt_temporal_denoise_spatial instead, both parameter sets at their defaults:
 // pixels with a short history take the spatial variance estimate.
+// -adaptive MIN MAX STEP THRESHOLD renders adaptively instead (pt_adaptive_begin,
+// then pt_adaptive_advance four rounds at a time, looking at pt_adaptive_info
+// after each four until no tile is live) and prints the samples it spent against
+// MAX samples for every pixel; -lum-floor sets the rule's floor (default: the
+// library's).  With -denoise-var the image written is pt_adaptive_denoise's.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -55,7 +61,7 @@ int main(int argc, char** argv) {
     fprintf(stderr,
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
             "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
-            "       [-progressive N [-chunk K] [-orbit-at B]]\n",
+            "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F]]\n",
             argv[0]);
     return 2;
   }
@@ -66,6 +72,9 @@ int main(int argc, char** argv) {
   int progressive = 0, chunk = 8, orbit_at = -1, temporal = 0;
   std::string cache_path, png_path, guide_path;
   bool denoise = false, denoise_var = false, temporal_spatial = false;
+  bool adaptive = false;
+  pt_adaptive_params ad;
+  pt_adaptive_default_params(&ad);
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -94,9 +103,21 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "-orbit-at")) orbit_at = atoi(next());
     else if (!strcmp(argv[i], "-temporal")) temporal = atoi(next());
     else if (!strcmp(argv[i], "-temporal-spatial")) temporal_spatial = true;
+    else if (!strcmp(argv[i], "-adaptive")) {
+      adaptive = true;
+      ad.min_batches = (uint32_t)atoi(next());
+      ad.max_batches = (uint32_t)atoi(next());
+      ad.step = (uint32_t)atoi(next());
+      ad.threshold = (float)atof(next());
+    }
+    else if (!strcmp(argv[i], "-lum-floor")) ad.lum_floor = (float)atof(next());
   }
   if (temporal_spatial && temporal <= 0) {
     fprintf(stderr, "-temporal-spatial needs -temporal K\n");
+    return 2;
+  }
+  if (adaptive && (temporal > 0 || progressive > 0 || denoise)) {
+    fprintf(stderr, "-adaptive goes with neither -temporal, -progressive nor -denoise\n");
     return 2;
   }
   pt_scene* scene = nullptr;
@@ -124,7 +145,7 @@ int main(int argc, char** argv) {
     check(pt_group_info(ctx, nullptr, nullptr, 0, &peer), "group_info");
     printf("devices: %zu (%s)\n", devices.size(), peer ? "peer stores into the first device's frame" : "packed tile copies");
   }
-  if (denoise_var || temporal > 0) check(pt_set_option(ctx, PT_OPT_MOMENTS, 1), "moments");
+  if (denoise_var || temporal > 0 || adaptive) check(pt_set_option(ctx, PT_OPT_MOMENTS, 1), "moments");
   check(pt_scene_upload(ctx, scene), "upload scene");
   const float pos[3] = {0.0f, 2.0f, 0.0f}, nrm[3] = {0.0f, -1.0f, 0.0f}, inten[3] = {10.0f, 10.0f, 10.0f},
               size[2] = {2.5f, 2.5f};   // VulkanRayTracer.cpp:149-162
@@ -191,6 +212,17 @@ int main(int argc, char** argv) {
         }
       check(pt_temporal_advance(ctx, cam, (uint32_t)spp), "temporal advance");
     }
+  } else if (adaptive) {
+    check(pt_adaptive_begin(ctx, &ad), "adaptive begin");
+    uint32_t rounds = 0, live = 0;
+    unsigned long long spent = 0;
+    do {   // nothing is waited for inside the four rounds; the look at the counts is the only wait
+      check(pt_adaptive_advance(ctx, 4), "adaptive advance");
+      check(pt_adaptive_info(ctx, &rounds, &live, &spent), "adaptive info");
+    } while (live > 0);
+    const double full = (double)ad.max_batches * W * H;
+    printf("adaptive: %u rounds, %llu samples spent of %.0f at %u spp everywhere (%.1f %%)\n", rounds, spent, full,
+           ad.max_batches, 100.0 * (double)spent / full);
   } else if (fused) {
     check(pt_render(ctx, 0, (uint32_t)spp), "render");
   } else {
@@ -201,6 +233,8 @@ int main(int argc, char** argv) {
   if (temporal > 0 && progressive == 0)
     printf("temporal: %d frames of %dx%d x %d spp in %.3f ms\n", temporal, W, H, spp,
            std::chrono::duration<double, std::milli>(r1 - r0).count());
+  else if (adaptive)
+    printf("rendered %dx%d adaptively in %.3f ms\n", W, H, std::chrono::duration<double, std::milli>(r1 - r0).count());
   else if (progressive == 0)
     printf("rendered %dx%d x %d spp in %.3f ms\n", W, H, spp, std::chrono::duration<double, std::milli>(r1 - r0).count());
   if (!out_path.empty() || !png_path.empty()) {
@@ -215,6 +249,9 @@ int main(int argc, char** argv) {
       } else {
         check(pt_read_temporal(ctx, rgba.data(), nullptr, nullptr), "read temporal");
       }
+    } else if (adaptive && denoise_var) {
+      check(pt_adaptive_denoise(ctx, nullptr, nullptr), "adaptive denoise");
+      check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
     } else if (denoise_var) {
       check(pt_denoise_var(ctx, nullptr, nullptr), "denoise-var");
       check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");

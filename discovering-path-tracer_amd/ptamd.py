@@ -72,6 +72,9 @@ EXPORTS = [
     "pt_temporal_default_params", "pt_reproject", "pt_reproject_host", "pt_temporal_advance", "pt_temporal_reset",
     "pt_temporal_info", "pt_temporal_device_ptr", "pt_read_temporal", "pt_temporal_denoise",
     "pt_spatial_var_default_params", "pt_spatial_variance_host", "pt_spatial_variance", "pt_temporal_denoise_spatial",
+    "pt_adaptive_default_params", "pt_adaptive_select_host", "pt_adaptive_select", "pt_adaptive_begin",
+    "pt_adaptive_advance", "pt_adaptive_info", "pt_adaptive_read_counts", "pt_adaptive_read_live",
+    "pt_adaptive_device_ptr", "pt_adaptive_denoise",
 ]
 
 
@@ -111,6 +114,11 @@ class TemporalParams(ctypes.Structure):
 class SpatialVarParams(ctypes.Structure):
     _fields_ = [("below", ctypes.c_uint32), ("radius", ctypes.c_int), ("sigma_normal", ctypes.c_float),
                 ("sigma_depth", ctypes.c_float)]
+
+
+class AdaptiveParams(ctypes.Structure):
+    _fields_ = [("min_batches", ctypes.c_uint32), ("max_batches", ctypes.c_uint32), ("step", ctypes.c_uint32),
+                ("threshold", ctypes.c_float), ("lum_floor", ctypes.c_float)]
 
 
 class ReprojectImages(ctypes.Structure):
@@ -216,6 +224,17 @@ def lib():
             "pt_spatial_variance": ([vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(SpatialVarParams), vp], i32),
             "pt_temporal_denoise_spatial": ([vp, ctypes.POINTER(DenoiseVarParams), ctypes.POINTER(SpatialVarParams),
                                              vp], i32),
+            "pt_adaptive_default_params": ([ctypes.POINTER(AdaptiveParams)], i32),
+            "pt_adaptive_select_host": ([vp, vp, i32, i32, ctypes.POINTER(AdaptiveParams), vp, vp], i32),
+            "pt_adaptive_select": ([vp, vp, vp, i32, i32, ctypes.POINTER(AdaptiveParams), vp, vp], i32),
+            "pt_adaptive_begin": ([vp, ctypes.POINTER(AdaptiveParams)], i32),
+            "pt_adaptive_advance": ([vp, u32], i32),
+            "pt_adaptive_info": ([vp, ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                  ctypes.POINTER(ctypes.c_ulonglong)], i32),
+            "pt_adaptive_read_counts": ([vp, vp, vp, sz], i32),
+            "pt_adaptive_read_live": ([vp, vp, sz, ctypes.POINTER(u32)], i32),
+            "pt_adaptive_device_ptr": ([vp, i32], vp),
+            "pt_adaptive_denoise": ([vp, ctypes.POINTER(DenoiseVarParams), vp], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -600,6 +619,43 @@ def spatial_variance_host(moments, length, variance, guide, width, height, param
     return out.reshape(height, width)
 
 
+def adaptive_default_params():
+    """pt_adaptive_default_params as an AdaptiveParams."""
+    p = AdaptiveParams()
+    _check(lib().pt_adaptive_default_params(ctypes.byref(p)), "pt_adaptive_default_params")
+    return p
+
+
+def _adaptive_params(params):
+    """None (the library's defaults), an AdaptiveParams, or (min_batches,
+    max_batches, step, threshold, lum_floor) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, AdaptiveParams):
+        return ctypes.byref(params)
+    lo, hi, step, thr, floor = params
+    return ctypes.byref(AdaptiveParams(int(lo), int(hi), int(step), float(thr), float(floor)))
+
+
+def adaptive_tiles(width, height):
+    """16x16 tiles of a frame: (blocks_x, blocks_y)."""
+    return (width + 15) // 16, (height + 15) // 16
+
+
+def adaptive_select_host(moments, counts, width, height, params=None):
+    """pt_adaptive_select_host: the stopping rule per 16x16 tile (raster
+    order) -> (next counts uint32, errors E_T float32)."""
+    bx, by = adaptive_tiles(width, height)
+    m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+    n = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+    if m.size != width * height * 2 or n.size != bx * by:
+        raise PTError("moments must hold width*height*2 floats, counts one per 16x16 tile")
+    nxt, err = np.empty(n.size, np.uint32), np.empty(n.size, np.float32)
+    _check(lib().pt_adaptive_select_host(m.ctypes.data, n.ctypes.data, width, height, _adaptive_params(params),
+                                         nxt.ctypes.data, err.ctypes.data), "pt_adaptive_select_host")
+    return nxt, err
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -864,6 +920,56 @@ class Renderer:
         _check(lib().pt_temporal_denoise_spatial(self._c, _denoise_var_params(params),
                                                  _spatial_var_params(spatial_params), dst_ptr),
                "pt_temporal_denoise_spatial")
+        if dst_ptr is not None:
+            return None
+        out = np.empty(self.width * self.height * 4, np.float32)
+        _check(lib().pt_read_denoised(self._c, out.ctypes.data, out.size), "pt_read_denoised")
+        return out.reshape(self.height, self.width, 4)
+
+    def adaptive_select(self, moments_ptr, counts_ptr, width, height, next_ptr, errors_ptr, params=None):
+        """pt_adaptive_select: enqueue the stopping rule over device images
+        (float2 moments, uint32 counts per tile) into next_ptr and errors_ptr."""
+        _check(lib().pt_adaptive_select(self._c, moments_ptr, counts_ptr, width, height, _adaptive_params(params),
+                                        next_ptr, errors_ptr), "pt_adaptive_select")
+
+    def adaptive_begin(self, params=None):
+        """pt_adaptive_begin: clear, then round 0 (every tile renders min_batches)."""
+        _check(lib().pt_adaptive_begin(self._c, _adaptive_params(params)), "pt_adaptive_begin")
+
+    def adaptive_advance(self, rounds=1):
+        """pt_adaptive_advance: enqueue up to `rounds` rounds of rule + render."""
+        _check(lib().pt_adaptive_advance(self._c, int(rounds)), "pt_adaptive_advance")
+
+    def adaptive_info(self):
+        """pt_adaptive_info: waits; (rounds done, live tiles, samples spent)."""
+        r, l, s = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_ulonglong(0)
+        _check(lib().pt_adaptive_info(self._c, ctypes.byref(r), ctypes.byref(l), ctypes.byref(s)), "pt_adaptive_info")
+        return int(r.value), int(l.value), int(s.value)
+
+    def adaptive_counts(self):
+        """pt_adaptive_read_counts: (counts uint32, errors float32), each (blocks_y, blocks_x)."""
+        bx, by = adaptive_tiles(self.width, self.height)
+        n, e = np.empty(bx * by, np.uint32), np.empty(bx * by, np.float32)
+        _check(lib().pt_adaptive_read_counts(self._c, n.ctypes.data, e.ctypes.data, n.size), "pt_adaptive_read_counts")
+        return n.reshape(by, bx), e.reshape(by, bx)
+
+    def adaptive_live(self):
+        """pt_adaptive_read_live: the last round's live list, (n, 4) int32
+        rows {x0, y0, first_batch, n_batches}."""
+        bx, by = adaptive_tiles(self.width, self.height)
+        ent, n = np.zeros((bx * by, 4), np.int32), ctypes.c_uint32(0)
+        _check(lib().pt_adaptive_read_live(self._c, ent.ctypes.data, bx * by, ctypes.byref(n)), "pt_adaptive_read_live")
+        return ent[:n.value].copy()
+
+    def adaptive_ptr(self, which):
+        """pt_adaptive_device_ptr: 0 counts, 1 errors, 2 variance plane; None when there is none."""
+        return lib().pt_adaptive_device_ptr(self._c, which)
+
+    def adaptive_denoise(self, params=None, dst_ptr=None):
+        """pt_adaptive_denoise: the variance-guided filter of the adaptive
+        result; with dst_ptr None the library-owned result is read back and
+        returned as (H, W, 4) float32."""
+        _check(lib().pt_adaptive_denoise(self._c, _denoise_var_params(params), dst_ptr), "pt_adaptive_denoise")
         if dst_ptr is not None:
             return None
         out = np.empty(self.width * self.height * 4, np.float32)

@@ -54,7 +54,11 @@ extern "C" {
  * pt_denoise_var_plane_host); the spatial variance estimate of short histories
  * (pt_spatial_var_params, pt_spatial_var_default_params,
  * pt_spatial_variance_host, pt_spatial_variance, pt_temporal_denoise_spatial);
- * the straight-line sweep of a cube table (PT_OPT_SWEEP_CUBE, pt_sweep_walk). */
+ * the straight-line sweep of a cube table (PT_OPT_SWEEP_CUBE, pt_sweep_walk);
+ * adaptive sampling (pt_adaptive_params, pt_adaptive_default_params,
+ * pt_adaptive_select_host, pt_adaptive_select, pt_adaptive_begin,
+ * pt_adaptive_advance, pt_adaptive_info, pt_adaptive_read_counts,
+ * pt_adaptive_read_live, pt_adaptive_device_ptr, pt_adaptive_denoise). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -527,6 +531,107 @@ int pt_spatial_variance(pt_context* ctx, const void* moments, const void* length
  * spatial_params.  When no pixel is short it gives pt_temporal_denoise's bits. */
 int pt_temporal_denoise_spatial(pt_context* ctx, const pt_denoise_var_params* filter_params,
                                 const pt_spatial_var_params* spatial_params, void* dst_device);
+
+/* ---- adaptive sampling: stop converged tiles, keep sampling the others ---
+ * pt_render gives every pixel the same number of samples.  The calls below
+ * feed the variance of the mean back into the sampler: each 16x16 tile of the
+ * frame (the partition unit; tiles are numbered in raster order here, b =
+ * by * blocks_x + bx, not in the partition's rotated order) carries its own
+ * sample count n_T, and a tile stops once every pixel of it is converged.
+ *
+ * The contract: seeds go by pixel and batch, so after an adaptive render every
+ * pixel of tile T inside the frame holds, in the accumulation image and in the
+ * moments image, exactly the bits pt_render(0, n_T) would leave there under
+ * the same options and seed base (PT_OPT_MOMENTS 1).
+ *
+ * The rule, shared by the kernel and the host function (every operation rounds
+ * once, the division and the square root are IEEE, nothing is fused; fmax is
+ * maxNum).  For a tile with count n and each pixel p of it inside the frame,
+ * from the moments {m1, m2}:
+ *   finite_p = fabs(m1_p) <= FLT_MAX && fabs(m2_p) <= FLT_MAX
+ *   e_p  = finite_p ? sqrt(fmax(0, m2_p - m1_p * m1_p) / float(n - 1)) / fmax(m1_p, lum_floor) : +inf
+ *   pixel converged:  e_p <= threshold
+ *   tile converged:   every pixel of it inside the frame converged
+ *   E_T  = fmax over those pixels of e_p, from +0      (reported; the decision is the predicate)
+ *   next = n                            if converged or n >= max_batches
+ *          min(n + step, max_batches)   otherwise
+ * maxNum would drop a NaN moment (the clamp makes its variance 0); finite_p
+ * keeps a pixel with a NaN or infinite moment from ever counting as converged:
+ * its tile stops at max_batches only.  For finite moments e_p is finite and
+ * >= +0, so neither the predicate nor the maximum depends on the order of the
+ * reduction.  A fully culled tile has zero moments, e_p = 0, and stops at
+ * min_batches.  n >= 2 (n - 1 divides).
+ *
+ * Parameters: 2 <= min_batches <= max_batches <= 65536, step >= 1, threshold
+ * and lum_floor finite and > 0; null: the defaults.  Anything else:
+ * PT_ERR_INVALID.  Defaults (pt_adaptive_default_params): min 4, max 64, step
+ * 15 (four rounds), threshold 0.09, lum_floor 2: the floor that gave the lowest
+ * error at equal samples on the box at 1080p, and the threshold that spent 16
+ * samples per pixel there.  lum_floor is in the scene's luminance units (the
+ * reference light's intensity is 10): below it the rule bounds the absolute
+ * standard error of the mean at threshold * lum_floor, above it the relative
+ * one. */
+typedef struct pt_adaptive_params {
+  uint32_t min_batches, max_batches, step;
+  float threshold, lum_floor;
+} pt_adaptive_params;
+int pt_adaptive_default_params(pt_adaptive_params* out);
+/* The rule on the host: moments W*H*2 floats, counts one per tile (raster
+ * order, each >= 2), next_counts and errors (E_T) one per tile; errors may be
+ * null.  Pure host function. */
+int pt_adaptive_select_host(const float* moments, const uint32_t* counts, int width, int height,
+                            const pt_adaptive_params* params, uint32_t* next_counts, float* errors);
+/* Enqueues the rule on the context's stream over the caller's device images:
+ * moments 8-B aligned, counts, next_counts and errors 4-B; next_counts may be
+ * counts.  The same bits as the host function. */
+int pt_adaptive_select(pt_context* ctx, const void* moments, const void* counts, int width, int height,
+                       const pt_adaptive_params* params, void* next_counts, void* errors);
+/* Starts an adaptive render: clears the accumulator and the moments, sets every
+ * count to 0 and enqueues round 0, in which every tile renders batches
+ * 0..min_batches-1 (at the seed base PT_OPT_SEED_BASE).  PT_ERR_INVALID without
+ * PT_OPT_MOMENTS 1, a scene, lights, a camera or a frame; PT_ERR_UNSUPPORTED on
+ * multi-device contexts, a partition of more than one rank, in stats mode, with
+ * PT_OPT_COUNT_TRACED and with PT_OPT_KERNEL 3 (under auto the adaptive calls
+ * run the path-recursive kernel). */
+int pt_adaptive_begin(pt_context* ctx, const pt_adaptive_params* params);
+/* Enqueues up to `rounds` rounds: the rule over all tiles, the list of the
+ * tiles whose count grew (ascending), and one launch that renders each listed
+ * tile's new batches.  Nothing is waited for: the launch is sized for every
+ * tile and reads the list's length from device memory.  After
+ * ceil((max_batches - min_batches) / step) rounds no count can change, and
+ * further rounds are no-ops.  PT_ERR_INVALID without pt_adaptive_begin. */
+int pt_adaptive_advance(pt_context* ctx, uint32_t rounds);
+/* Waits for the rounds enqueued so far.  rounds_done: rounds enqueued since
+ * pt_adaptive_begin (round 0 not counted); live_tiles: tiles the last round
+ * rendered (after pt_adaptive_begin alone: every tile), 0 once no round is
+ * left; samples_total: the sum over tiles of n_T times the tile's pixels
+ * inside the frame.  Each pointer may be null. */
+int pt_adaptive_info(pt_context* ctx, uint32_t* rounds_done, uint32_t* live_tiles, unsigned long long* samples_total);
+/* Waits and copies the tiles' counts n_T and the errors E_T of the last round's
+ * rule (0 before the first round); n_tiles must be the frame's tile count;
+ * either pointer may be null. */
+int pt_adaptive_read_counts(pt_context* ctx, uint32_t* counts, float* errors, size_t n_tiles);
+/* Waits and copies the last round's live list: up to max_entries entries of
+ * four ints {x0, y0, first_batch, n_batches}, their number in *n_live. */
+int pt_adaptive_read_live(pt_context* ctx, int* entries, size_t max_entries, uint32_t* n_live);
+/* Device memory of the adaptive state: which = 0 counts (uint32 per tile), 1
+ * errors (float per tile), 2 the variance plane pt_adaptive_denoise wrote (W*H
+ * floats); null when there is none. */
+void* pt_adaptive_device_ptr(pt_context* ctx, int which);
+/* pt_denoise_var's passes on the adaptive result: a kernel writes the variance
+ * plane var_p = fmax(0, m2_p - m1_p * m1_p) / float(n_T - 1) at each tile's own
+ * count, and the variance-plane passes run on it with the guide (rendered if
+ * there is none); the same bits as pt_denoise_var_plane_host fed with that
+ * plane.  dst_device as for pt_denoise_var.  PT_ERR_INVALID without an adaptive
+ * render.
+ *
+ * After an adaptive render pt_read_accum works as ever; the moments have no
+ * single n, so pt_read_moments reports n = 0 and pt_denoise_var refuses, as
+ * after a render with a gap.  The adaptive state ends with pt_upload_scene,
+ * pt_scene_upload, pt_upload_lights, pt_set_params, a change of frame size or
+ * of the bound buffer, pt_clear_accum and any render (pt_render, pt_dispatch,
+ * pt_render_packed, pt_temporal_advance). */
+int pt_adaptive_denoise(pt_context* ctx, const pt_denoise_var_params* params, void* dst_device);
 
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile
