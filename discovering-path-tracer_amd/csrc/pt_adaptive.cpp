@@ -3,7 +3,8 @@
 // (pt_adaptive_select_host, pt_adaptive_select; the statement is pt_denoise.h's
 // adaptive_error / adaptive_next), the rounds of an adaptive render
 // (pt_adaptive_begin, pt_adaptive_advance: rule, live list, one launch of
-// kernels/adaptive.h per round, nothing waited for), its reads, and the
+// kernels/adaptive.h per round, or with PT_OPT_ADAPTIVE_WF a round of the
+// wavefront pipeline, kernels/wf_adaptive.h; nothing waited for), its reads, and the
 // variance-guided filter of its result (pt_adaptive_denoise).  What the calls
 // refuse and which kernel they run is pt_plan.h's plan_adaptive.
 #include <stdint.h>
@@ -32,11 +33,20 @@ static ptdn::AdaptiveParams statement_params(const pt_adaptive_params& p) {
 
 static int tiles_of(int w, int h) { return ((w + 15) / 16) * ((h + 15) / 16); }
 
-// One round's launch at `spl` lanes over the list the stream has just been given.
-static int launch_round(pt_context* c, const AdaptivePlan& ap, int spl) {
+// One round's launch at `spl` lanes over the list the stream has just been given.  round: 0 = pt_adaptive_begin's,
+// k = the k-th of pt_adaptive_advance.  The path-recursive kernel takes the batches from the list's entries; a
+// wavefront round (ap.wf) takes them from the host, which knows them without reading the list: every tile starts at
+// min_batches, a tile is live only if it was live in every earlier round, and a live tile advances by
+// min(step, max - n), so all live entries of round k >= 1 hold {min + (k - 1) * step, min(step, max - that)}.
+static int launch_round(pt_context* c, const AdaptivePlan& ap, const pt_adaptive_params& a, uint32_t round, int spl) {
   ptd::RenderParams p{};
   const int rp = adaptive_render_params(c, ap, spl, &p);
   if (rp) return rp;
+  if (ap.wf) {
+    p.first_batch = round == 0 ? 0u : a.min_batches + (round - 1u) * a.step;   // < max_batches: the round exists
+    p.n_batches = round == 0 ? a.min_batches : std::min(a.step, a.max_batches - p.first_batch);
+    return adaptive_launch_wavefront(c, ap, std::max(a.min_batches, std::min(a.step, a.max_batches)), &p);
+  }
   PT_HIP(ptd::launch_render_adaptive(p, ap.lds, c->d_ad_list, c->d_ad_live, c->stream));
   return PT_OK;
 }
@@ -138,9 +148,9 @@ int pt_adaptive_begin(pt_context* c, const pt_adaptive_params* params) {
   PT_HIP(ptd::launch_adaptive_fill(c->d_ad_counts, c->d_ad_added, tiles, p.min_batches, c->stream));
   PT_HIP(ptd::launch_adaptive_compact(c->d_ad_counts, c->d_ad_added, c->width, c->height, c->d_ad_list, c->d_ad_live,
                                       c->stream));
-  rc = launch_round(c, ap, ap.spl0);
+  rc = launch_round(c, ap, p, 0, ap.spl0);
   if (rc) return rc;
-  c->last_kernel = 1;
+  c->last_kernel = ap.wf ? 3 : 1;
   c->ad_params = p;
   c->ad_rounds = ap.rounds;
   c->ad_rounds_done = 0;
@@ -165,7 +175,7 @@ int pt_adaptive_advance(pt_context* c, uint32_t rounds) {
                                        c->d_ad_errors, c->d_ad_added, c->stream));
     PT_HIP(ptd::launch_adaptive_compact(c->d_ad_counts, c->d_ad_added, c->width, c->height, c->d_ad_list,
                                         c->d_ad_live, c->stream));
-    const int rc = launch_round(c, ap, ap.spl);
+    const int rc = launch_round(c, ap, c->ad_params, c->ad_rounds_done + 1u, ap.spl);
     if (rc) return rc;
     c->ad_rounds_done++;
     c->ad_var_valid = false;

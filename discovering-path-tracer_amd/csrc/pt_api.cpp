@@ -936,9 +936,27 @@ int adaptive_render_params(pt_context* c, const AdaptivePlan& ap, int spl, ptd::
   plan.sweep = ap.sweep != 0;
   plan.sweep_hull = ap.sweep >= 2;
   plan.sweep_cube = ap.sweep == 3;
+  plan.wide_refill = ap.wide_refill;
   { const int rc = render_params(c, plan, 0, 0, false, p); if (rc) return rc; }
   p->moments = c->d_moments;
   cull_rectangles(c, p);
+  return PT_OK;
+}
+
+int adaptive_launch_wavefront(pt_context* c, const AdaptivePlan& ap, uint32_t reserve_batches, ptd::RenderParams* p) {
+  long long chunk_paths = 0;
+  const int rc = wf_reserve(c, (long long)p->blocks_total * 256, reserve_batches, &chunk_paths);
+  if (rc) return rc;
+  ptd::WfBuffers b = c->wf;
+  b.cap = chunk_paths;   // paths per chunk (the allocation may be larger)
+  if (ap.wide) {
+    const int rw = wide_params(c, p);
+    if (rw) return rw;
+    p->wide_handback = ap.wide_handback;
+    p->wf_fuse = ap.wf_fuse;
+    p->wf_tail = ap.wf_tail;
+  }
+  PT_HIP(ptd::launch_wavefront_adaptive(*p, b, ap.lds, c->d_ad_list, c->d_ad_live, c->stream));
   return PT_OK;
 }
 
@@ -1563,6 +1581,7 @@ static const IntOption kIntOptions[] = {
     {PT_OPT_SWEEP_HULL, &pt_context::opt_sweep_hull, 0, 1, "PT_OPT_SWEEP_HULL takes 0 or 1"},
     {PT_OPT_EXIT_SKIP, &pt_context::opt_exit_skip, 0, 1, "PT_OPT_EXIT_SKIP takes 0 or 1"},
     {PT_OPT_SWEEP_CUBE, &pt_context::opt_sweep_cube, 0, 1, "PT_OPT_SWEEP_CUBE takes 0 or 1"},
+    {PT_OPT_ADAPTIVE_WF, &pt_context::opt_adaptive_wf, 0, 1, "PT_OPT_ADAPTIVE_WF takes 0 or 1"},
 };
 
 int pt_set_option(pt_context* c, int key, int value) {

@@ -138,6 +138,7 @@ struct pt_context {
   int opt_denoise_lds = 1;    // PT_OPT_DENOISE_LDS
   int opt_moments = 0;        // PT_OPT_MOMENTS
   uint32_t opt_seed_base = 0; // PT_OPT_SEED_BASE
+  int opt_adaptive_wf = 0;    // PT_OPT_ADAPTIVE_WF: adaptive rounds on the wavefront pipeline
   bool stats_mode = false;    // pt_set_stats_mode
 
   // ---- pt_api.cpp: partition and item lists -------------------------------------
@@ -430,6 +431,10 @@ int post_denoise_var_params(const pt_denoise_var_params* in, pt_denoise_var_para
 // whole frame under an adaptive plan (no item list, no fill; the cull rectangles as render_impl derives them)
 struct AdaptivePlan;
 int adaptive_render_params(pt_context* c, const AdaptivePlan& ap, int spl, ptd::RenderParams* p);
+// ... and a round on the wavefront pipeline (ap.wf): batches p->first_batch .. + p->n_batches of the live list,
+// in path buffers reserved for every tile's pixels and reserve_batches batches (the same in every round of a
+// render, so the rounds do not reallocate)
+int adaptive_launch_wavefront(pt_context* c, const AdaptivePlan& ap, uint32_t reserve_batches, ptd::RenderParams* p);
 int dist_synchronize(pt_context* c);   // pt_synchronize's share of the step loop: its render and gather streams
 
 #pragma GCC visibility pop

@@ -263,6 +263,10 @@ inline int wf_max_rays(const RenderParams& p) {
 hipError_t launch_wavefront(const RenderParams& p, const WfBuffers& b, bool lds_scene, hipStream_t stream,
                             bool cnt = false, hipStream_t stream2 = nullptr, hipEvent_t ev_fork = nullptr,
                             hipEvent_t ev_join = nullptr);
+// One adaptive round on the wavefront pipeline (PT_OPT_ADAPTIVE_WF, kernels/wf_adaptive.h): batches
+// p.first_batch .. + p.n_batches of the tiles list[0 .. *n_live) (both device memory), on one stream.
+hipError_t launch_wavefront_adaptive(const RenderParams& p, const WfBuffers& b, bool lds_scene, const int4* list,
+                                     const int* n_live, hipStream_t stream);
 // First-hit guide image of the whole frame (pt_render_guide): float4 {n.xyz, t}
 // per pixel from p's camera, size and scene.  p.wide set: the culled wide
 // walk; else the exact walk, staged in LDS with lds_scene.
@@ -520,6 +524,69 @@ inline AdaptiveLaunch plan_render_adaptive(const RenderParams& p, bool lds_scene
   l.lds = v.sweep ? sweep_lds_bytes(p) : lds_scene ? scene_lds_bytes(p) : 0;
   if (l.lds > kMaxSceneLds) return l;
   l.v = v;
+  l.what = Launch::Run;
+  return l;
+}
+
+// ... and of launch_wavefront_adaptive's (an adaptive round on the wavefront pipeline, kernels/wf_adaptive.h).
+// The host does not know how many tiles the round's list holds, so everything is sized for the worst case,
+// every tile live: blocks_total * 256 pixel slots, the round's batches in chunks of cap / px, a generation
+// grid of blocks_total * chunk workgroups and a fold grid of blocks_total.  The trace, tail and shading
+// kernels are pick_wavefront's, moments on and counters off.
+//
+// Path numbering inside a chunk of nb batches: path g = (e * 256 + q) * nb + s is sample s of pixel q
+// (x = list[e].x + q % 16, y = list[e].y + q / 16) of live entry e, and exists iff e < *n_live and the pixel
+// lies inside the frame.  256 * nb is a multiple of 256, so generation workgroup `block` lies inside entry
+// block / nb.  g is 64-bit: a grid of up to 2^31 - 1 workgroups numbers paths far past 2^31 (a chunk's never
+// are: px * chunk <= cap <= 2^31 - 1, which is what keeps the path ids of the lists in an int).
+struct WfAdaptivePath {
+  uint32_t entry, q, s;   // live entry, pixel within its 16x16 tile, sample within the chunk
+  long long g;            // the path: ((long long)entry * 256 + q) * nb + s
+};
+__host__ __device__ inline long long wf_adaptive_index(long long entry, int q, uint32_t s, uint32_t nb) {
+  return (entry * 256 + q) * (long long)nb + s;
+}
+// Thread `tid` of generation workgroup `block`, nb in 1..65536 (so 256 * nb fits 32 bits with room).
+__host__ __device__ inline WfAdaptivePath wf_adaptive_path(uint32_t block, uint32_t tid, uint32_t nb) {
+  WfAdaptivePath a;
+  a.entry = block / nb;                                    // workgroup-uniform
+  const uint32_t t = (block - a.entry * nb) * 256u + tid;   // the path within the entry's 256 * nb
+  a.q = t / nb;
+  a.s = t - a.q * nb;
+  a.g = (long long)block * 256 + tid;
+  return a;
+}
+struct WfAdaptiveLaunch {
+  Launch what = Launch::Refused;
+  long long px = 0;          // pixel slots: every tile's
+  uint32_t chunk = 0;        // batches per chunk
+  long long gen_grid = 0;    // wf_gen_adaptive_kernel's workgroups for a full chunk (a shorter last one: blocks * nb)
+  long long fold_grid = 0;   // wf_fold_adaptive_kernel's
+  size_t lds_trace = 0;      // the trace kernel's dynamic LDS bytes
+  WfPick k = {};
+};
+// cap: WfBuffers::cap.  p.first_batch / p.n_batches: the round's, the same for every live tile.
+inline WfAdaptiveLaunch plan_wavefront_adaptive(const RenderParams& p, long long cap, bool lds_scene, int group4_tris) {
+  WfAdaptiveLaunch l;
+  if (!spl_valid(p.spl) || !p.moments || p.pack_out || p.items || p.mix || p.nranks != 1) return l;
+  if (p.n_batches > 65536u) return l;   // pt_adaptive_params' bound, wf_adaptive_path's
+  if (p.blocks_total <= 0 || p.n_batches == 0) {
+    l.what = Launch::Nothing;
+    return l;
+  }
+  l.px = (long long)p.blocks_total * 256;
+  if (l.px > cap || cap > 0x7fffffffll) return l;
+  const size_t lds = lds_scene ? scene_lds_bytes(p) : 0;
+  if (lds > kMaxSceneLds) return l;
+  const WfPick k = pick_wavefront(lds_scene, p.wide != nullptr, p.wide_qn != 0, false, p.exit_skip != 0, true,
+                                  p.wf_tail > 0, p.n_tris < group4_tris);
+  if (!k.ok) return l;
+  if (k.wide && p.wide_ovf_lanes < 256) return l;   // every lane needs its overflow stack area
+  l.chunk = (uint32_t)(cap / l.px < (long long)p.n_batches ? cap / l.px : (long long)p.n_batches);
+  l.gen_grid = (long long)p.blocks_total * l.chunk;   // <= cap / 256
+  l.fold_grid = p.blocks_total;
+  l.lds_trace = k.wide ? 0 : lds;
+  l.k = k;
   l.what = Launch::Run;
   return l;
 }

@@ -51,6 +51,7 @@ namespace {
 #include "kernels/wf_trace.h"
 #include "kernels/wf_wide.h"
 #include "kernels/wf_shade.h"
+#include "kernels/wf_adaptive.h"
 #include "kernels/guide.h"
 #include "kernels/adaptive.h"
 
@@ -218,6 +219,41 @@ long long wide_trace_lanes() {
   return most * 256;
 }
 
+namespace {
+// The kernels of a wavefront launch's ray rounds and their persistent grids: the trace kernel (the culled
+// wide walk, PT_OPT_WIDE, or the threaded one), the shading kernel, the tail kernel where planned
+// (PT_OPT_WF_TAIL); the exit skip picks the shading and tail kernels' EXIT instantiations (generation never
+// reaches a bounce).
+struct WfKernels {
+  WfKernel trace = nullptr, shade = nullptr, tail = nullptr;
+  unsigned grid_t = 0, grid_s = 0, grid_x = 0;
+};
+hipError_t wf_kernels(const WfPick& pick, size_t lds_t, const RenderParams& p0, WfKernels* k) {
+  k->trace = pick.wide ? find_kernel(kWfWideKernels, pick.wide_trace) : find_kernel(kWfTraceKernels, pick.trace);
+  k->shade = find_kernel(kWfShadeKernels, pick.shade);
+  k->tail = pick.tail ? find_kernel(kWfTailKernels, pick.tail_v) : nullptr;
+  if (!k->trace || !k->shade || (pick.tail && !k->tail)) return hipErrorInvalidValue;
+  long long blocks_t = 0, blocks_s = 0, blocks_x = 0;
+  hipError_t e = resident_blocks(k->trace, lds_t, 1, &blocks_t);
+  if (e == hipSuccess) e = resident_blocks(k->shade, 0, 1, &blocks_s);
+  if (e == hipSuccess && pick.tail) e = resident_blocks(k->tail, 0, 1, &blocks_x);
+  if (e != hipSuccess) return e;
+  k->grid_t = (unsigned)blocks_t;
+  k->grid_x = (unsigned)blocks_x;
+  // PT_OPT_WF_GRID: a smaller persistent grid gives each lane more rays per
+  // round (a shorter drain relative to the round) when other frames' launches
+  // fill the rest of the GPU
+  if (p0.wf_grid > 0 && p0.wf_grid < 100)
+    k->grid_t = std::max(1u, (unsigned)((unsigned long long)k->grid_t * p0.wf_grid / 100));
+  if (pick.wide) {   // every lane needs its overflow stack area
+    k->grid_t = std::min<unsigned>(k->grid_t, (unsigned)(p0.wide_ovf_lanes / 256));
+    k->grid_x = std::min<unsigned>(k->grid_x, (unsigned)(p0.wide_ovf_lanes / 256));
+  }
+  k->grid_s = (unsigned)blocks_s;
+  return hipSuccess;
+}
+}  // namespace
+
 hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds_scene, hipStream_t stream, bool cnt,
                             hipStream_t stream2, hipEvent_t ev_fork, hipEvent_t ev_join) {
   const WfLaunch l = plan_wavefront(p0, b.cap, lds_scene, cnt, kPixPerFill, kWfGroup4Tris);
@@ -227,28 +263,13 @@ hipError_t launch_wavefront(const RenderParams& p0, const WfBuffers& b, bool lds
   if (l.stop == WfStop::FillOnly) return hipGetLastError();
   if (l.stop == WfStop::FillRefused) return hipErrorInvalidValue;
   const long long px = l.px;
-  const bool wide = l.k.wide, tail = l.k.tail;   // the culled wide walk (PT_OPT_WIDE, default); PT_OPT_WF_TAIL
-  const WfKernel trace = wide ? find_kernel(kWfWideKernels, l.k.wide_trace) : find_kernel(kWfTraceKernels, l.k.trace);
-  // the exit skip: the shading and tail kernels' EXIT instantiations (generation never reaches a bounce)
-  const WfKernel shade = find_kernel(kWfShadeKernels, l.k.shade);
-  const WfKernel tailk = tail ? find_kernel(kWfTailKernels, l.k.tail_v) : nullptr;
-  if (!trace || !shade || (tail && !tailk)) return hipErrorInvalidValue;
-  const size_t lds_t = l.lds_trace;
-  long long blocks_t = 0, blocks_s = 0, blocks_x = 0;
-  hipError_t e = resident_blocks(trace, lds_t, 1, &blocks_t);
-  if (e == hipSuccess) e = resident_blocks(shade, 0, 1, &blocks_s);
-  if (e == hipSuccess && tail) e = resident_blocks(tailk, 0, 1, &blocks_x);
+  WfKernels k;
+  hipError_t e = wf_kernels(l.k, l.lds_trace, p0, &k);
   if (e != hipSuccess) return e;
-  unsigned grid_t = (unsigned)blocks_t, grid_x = (unsigned)blocks_x;
-  // PT_OPT_WF_GRID: a smaller persistent grid gives each lane more rays per
-  // round (a shorter drain relative to the round) when other frames' launches
-  // fill the rest of the GPU
-  if (p0.wf_grid > 0 && p0.wf_grid < 100) grid_t = std::max(1u, (unsigned)((unsigned long long)grid_t * p0.wf_grid / 100));
-  if (wide) {   // every lane needs its overflow stack area
-    grid_t = std::min<unsigned>(grid_t, (unsigned)(p0.wide_ovf_lanes / 256));
-    grid_x = std::min<unsigned>(grid_x, (unsigned)(p0.wide_ovf_lanes / 256));
-  }
-  const unsigned grid_s = (unsigned)blocks_s;
+  const bool tail = l.k.tail;
+  const WfKernel trace = k.trace, shade = k.shade, tailk = k.tail;
+  const size_t lds_t = l.lds_trace;
+  const unsigned grid_t = k.grid_t, grid_s = k.grid_s, grid_x = k.grid_x;
   const uint32_t chunk = (uint32_t)std::min<long long>((long long)p0.n_batches, b.cap / px);
   const int iters = wf_max_rays(p0);
   // Two halves of the chunk's pixels on two streams (PT_OPT_WF_STREAMS):
@@ -329,6 +350,50 @@ hipError_t launch_render_adaptive(const RenderParams& p, bool lds_scene, const i
   const AdaptiveKernel kern = l.what == Launch::Run ? find_kernel(kAdaptiveKernels, l.v) : nullptr;
   if (!kern || !list || !n_live) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(256), l.lds, stream, p, list, n_live);
+  return hipGetLastError();
+}
+
+namespace {
+// ... and the wavefront adaptive round's generation and fold (last again: kernels/wf_adaptive.h says why)
+typedef void (*WfAdaptiveKernel)(RenderParams, WfBuffers, const int4*, const int*);
+const WfAdaptiveKernel kWfGenAdaptive = wf_gen_adaptive_kernel<1>, kWfFoldAdaptive = wf_fold_adaptive_kernel<1>;
+}  // namespace
+
+// An adaptive round on the wavefront pipeline: launch_wavefront's chunk loop on one stream, with the live
+// list in place of item lists and no culled-item fill (the fold writes every listed tile's pixels).
+//
+// The invariant that lets the host number the round: every tile starts at min_batches, a tile is live in a
+// round only if it was live in every earlier one, and a live tile advances by min(step, max - n) -- so all
+// live entries of one round hold the same {first_batch, n_batches}, which the host knows without reading
+// the list.  They travel in p0 and advance per chunk as launch_wavefront's do; the list supplies origins only.
+// The second stream (PT_OPT_WF_STREAMS 2) is not used: the host cannot halve a live pixel count it does not know.
+// A round whose list is empty still enqueues everything; every workgroup finds nothing to do.
+hipError_t launch_wavefront_adaptive(const RenderParams& p0, const WfBuffers& b, bool lds_scene, const int4* list,
+                                     const int* n_live, hipStream_t stream) {
+  const WfAdaptiveLaunch l = plan_wavefront_adaptive(p0, b.cap, lds_scene, kWfGroup4Tris);
+  if (l.what == Launch::Nothing) return hipSuccess;
+  if (l.what != Launch::Run || !list || !n_live) return hipErrorInvalidValue;
+  WfKernels k;
+  hipError_t e = wf_kernels(l.k, l.lds_trace, p0, &k);
+  if (e != hipSuccess) return e;
+  const int iters = wf_max_rays(p0);
+  for (uint32_t b0 = 0; b0 < p0.n_batches; b0 += l.chunk) {
+    RenderParams p = p0;
+    p.first_batch = p0.first_batch + b0;
+    p.n_batches = std::min(l.chunk, p0.n_batches - b0);
+    e = hipMemsetAsync(b.counters, 0, 3 * sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    const unsigned gen_grid = (unsigned)((long long)p.blocks_total * p.n_batches);
+    hipLaunchKernelGGL(kWfGenAdaptive, dim3(gen_grid), dim3(256), 0, stream, p, b, list, n_live);
+    int cur = 0;
+    for (int it = 0; it < iters; ++it) {
+      hipLaunchKernelGGL(k.trace, dim3(k.grid_t), dim3(256), l.lds_trace, stream, p, b, cur);
+      if (l.k.tail) hipLaunchKernelGGL(k.tail, dim3(k.grid_x), dim3(256), 0, stream, p, b, cur);
+      hipLaunchKernelGGL(k.shade, dim3(k.grid_s), dim3(256), 0, stream, p, b, cur);
+      cur ^= 1;
+    }
+    hipLaunchKernelGGL(kWfFoldAdaptive, dim3((unsigned)l.fold_grid), dim3(256), 0, stream, p, b, list, n_live);
+  }
   return hipGetLastError();
 }
 

@@ -87,8 +87,10 @@ struct LaunchPlan {
 };
 
 // The plan of the render of n_batches batches over this rank's n_tiles tiles (packed: pt_render_packed,
-// a pt_dist_run frame).
-inline LaunchPlan plan_launch(const pt_context& c, long long n_tiles, uint32_t n_batches, bool packed) {
+// a pt_dist_run frame).  kernel: the kernel asked for where the caller's own option overrides PT_OPT_KERNEL
+// (plan_adaptive under PT_OPT_ADAPTIVE_WF), -1 = the option's.
+inline LaunchPlan plan_launch(const pt_context& c, long long n_tiles, uint32_t n_batches, bool packed,
+                              int kernel = -1) {
   LaunchPlan pl;
   auto refuse = [&pl](const char* msg, bool first) {
     if (pl.refuse) return;   // the first refusal is the one reported
@@ -156,7 +158,8 @@ inline LaunchPlan plan_launch(const pt_context& c, long long n_tiles, uint32_t n
   const bool wf_auto = wide_walk ? c.n_tris >= kWfWideAutoTris && paths >= (1ll << 20)
                                  : c.n_tris >= kWfAutoTris && paths >= (1ll << 20) &&
                                        (c.n_tris >= (1 << 20) || paths >= (1ll << 23));
-  pl.wf = c.opt_kernel == 3 || (c.opt_kernel == 0 && !pl.lds && !c.stats_mode && wf_auto);
+  const int asked = kernel < 0 ? c.opt_kernel : kernel;
+  pl.wf = asked == 3 || (asked == 0 && !pl.lds && !c.stats_mode && wf_auto);
   if (pl.wf && c.stats_mode) refuse("stats mode runs the path-recursive kernel only", false);
   pl.cnt = c.opt_count != 0 && !c.stats_mode;
   // the sweep walk (PT_OPT_SMALL_SWEEP): the plain LDS kernel of a scene with a table
@@ -195,10 +198,16 @@ inline LaunchPlan plan_launch(const pt_context& c, long long n_tiles, uint32_t n
 
 // The plan of an adaptive render (pt_adaptive_begin / pt_adaptive_advance): what it refuses, the
 // instantiation its rounds run, their lane counts and how many rounds can still change a count.  The
-// walk, LDS and exit-skip choices are plan_launch's for a path-recursive launch; the wavefront pipeline
-// is refused when asked for and never chosen under auto (plan_launch is asked about no tile, so no launch
-// is ever large enough for it).  Lanes: round 0 renders min_batches everywhere and is planned for them,
-// every later round for `step` -- one lane count per launch, never more lanes than samples.
+// walk, LDS and exit-skip choices are plan_launch's for a path-recursive launch; by default
+// (PT_OPT_ADAPTIVE_WF 0) the wavefront pipeline is refused when asked for and never chosen under auto
+// (plan_launch is asked about no tile, so no launch is ever large enough for it).  Lanes: round 0 renders
+// min_batches everywhere and is planned for them, every later round for `step` -- one lane count per launch,
+// never more lanes than samples.
+// PT_OPT_ADAPTIVE_WF 1: the rounds run on the wavefront pipeline (kernels/wf_adaptive.h) unless
+// PT_OPT_KERNEL 1 asks for the path-recursive kernel; the wide walk's settings and the LDS staging are
+// plan_launch's for a wavefront launch, so every option of the pipeline means what it means for pt_render.
+// Its second stream (PT_OPT_WF_STREAMS 2) is not used: the two streams split a chunk's pixels in halves, and
+// the host does not know how many pixels the round's live list holds.
 constexpr const char* kAdaptiveBadParams =
     "pt_adaptive_params: 2 <= min_batches <= max_batches <= 65536, step >= 1; threshold and lum_floor finite and > 0";
 struct AdaptivePlan {
@@ -210,6 +219,10 @@ struct AdaptivePlan {
   int exit_skip = 0;
   uint32_t rounds = 0;          // ceil((max_batches - min_batches) / step)
   ptd::AdaptiveVariant v = {};  // render_adaptive_kernel's instantiation
+  bool wf = false;              // the rounds run on the wavefront pipeline (PT_OPT_ADAPTIVE_WF)
+  bool wide = false;            // ... with the culled wide walk, and its settings (LaunchPlan's, 0 without it)
+  int wide_qn = 0, wide_handback = 0, wf_fuse = 0, wf_tail = 0;
+  int wide_refill = 0;
 };
 inline AdaptivePlan plan_adaptive(const pt_context& c, const pt_adaptive_params& a) {
   AdaptivePlan ap;
@@ -225,11 +238,14 @@ inline AdaptivePlan plan_adaptive(const pt_context& c, const pt_adaptive_params&
   if (c.nranks > 1) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not on a partition of more than one rank");
   if (c.stats_mode) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not in stats mode");
   if (c.opt_count) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: not with PT_OPT_COUNT_TRACED");
-  if (c.opt_kernel == 3) refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: the path-recursive kernel only (PT_OPT_KERNEL 3)");
+  if (c.opt_kernel == 3 && !c.opt_adaptive_wf)
+    refuse(PT_ERR_UNSUPPORTED, "adaptive sampling: the path-recursive kernel only (PT_OPT_KERNEL 3)");
   if (!c.opt_moments) refuse(PT_ERR_INVALID, "adaptive sampling: needs PT_OPT_MOMENTS 1");
   if (ap.refuse) return ap;
-  const LaunchPlan p0 = plan_launch(c, 0, a.min_batches, false);
-  const LaunchPlan p1 = plan_launch(c, 0, a.step, false);
+  ap.wf = c.opt_adaptive_wf != 0 && c.opt_kernel != 1;   // the explicit request for the path-recursive kernel wins
+  const int kernel = ap.wf ? 3 : -1;
+  const LaunchPlan p0 = plan_launch(c, 0, a.min_batches, false, kernel);
+  const LaunchPlan p1 = plan_launch(c, 0, a.step, false, kernel);
   if (p0.refuse) {
     refuse(p0.refuse_code, p0.refuse);
     return ap;
@@ -242,6 +258,12 @@ inline AdaptivePlan plan_adaptive(const pt_context& c, const pt_adaptive_params&
   ap.rounds = (a.max_batches - a.min_batches + a.step - 1u) / a.step;
   if (a.step > a.max_batches - a.min_batches) ap.rounds = a.max_batches > a.min_batches ? 1u : 0u;   // no overflow
   ap.v = ptd::pick_adaptive(ap.lds, ap.sweep, ap.exit_skip != 0);
+  ap.wide = p0.wide;
+  ap.wide_qn = p0.wide_qn;
+  ap.wide_handback = p0.wide_handback;
+  ap.wf_fuse = p0.wf_fuse;
+  ap.wf_tail = p0.wf_tail;
+  ap.wide_refill = ap.wf ? p0.wide_refill : 0;   // (plan_launch sets it for every launch)
   return ap;
 }
 

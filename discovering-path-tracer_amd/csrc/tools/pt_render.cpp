@@ -7,7 +7,7 @@
 //             [-fused] [-o out.pfm] [-png out.png] [-device 0 | -devices 0,1,..]
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
 //             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
-//             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F]]
+//             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -37,6 +37,7 @@
 // after each four until no tile is live) and prints the samples it spent against
 // MAX samples for every pixel; -lum-floor sets the rule's floor (default: the
 // library's).  With -denoise-var the image written is pt_adaptive_denoise's.
+// -adaptive-wf runs the rounds on the wavefront pipeline (PT_OPT_ADAPTIVE_WF 1).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -61,7 +62,7 @@ int main(int argc, char** argv) {
     fprintf(stderr,
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
             "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
-            "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F]]\n",
+            "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]\n",
             argv[0]);
     return 2;
   }
@@ -72,7 +73,7 @@ int main(int argc, char** argv) {
   int progressive = 0, chunk = 8, orbit_at = -1, temporal = 0;
   std::string cache_path, png_path, guide_path;
   bool denoise = false, denoise_var = false, temporal_spatial = false;
-  bool adaptive = false;
+  bool adaptive = false, adaptive_wf = false;
   pt_adaptive_params ad;
   pt_adaptive_default_params(&ad);
   std::vector<int> devices;   // -devices: a multi-device context
@@ -111,6 +112,7 @@ int main(int argc, char** argv) {
       ad.threshold = (float)atof(next());
     }
     else if (!strcmp(argv[i], "-lum-floor")) ad.lum_floor = (float)atof(next());
+    else if (!strcmp(argv[i], "-adaptive-wf")) adaptive_wf = true;
   }
   if (temporal_spatial && temporal <= 0) {
     fprintf(stderr, "-temporal-spatial needs -temporal K\n");
@@ -146,6 +148,7 @@ int main(int argc, char** argv) {
     printf("devices: %zu (%s)\n", devices.size(), peer ? "peer stores into the first device's frame" : "packed tile copies");
   }
   if (denoise_var || temporal > 0 || adaptive) check(pt_set_option(ctx, PT_OPT_MOMENTS, 1), "moments");
+  if (adaptive_wf) check(pt_set_option(ctx, PT_OPT_ADAPTIVE_WF, 1), "adaptive-wf");
   check(pt_scene_upload(ctx, scene), "upload scene");
   const float pos[3] = {0.0f, 2.0f, 0.0f}, nrm[3] = {0.0f, -1.0f, 0.0f}, inten[3] = {10.0f, 10.0f, 10.0f},
               size[2] = {2.5f, 2.5f};   // VulkanRayTracer.cpp:149-162

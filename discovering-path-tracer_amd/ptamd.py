@@ -47,6 +47,7 @@ PT_OPT_MOMENTS = 27
 PT_OPT_EXIT_SKIP = 28
 PT_OPT_SEED_BASE = 29
 PT_OPT_SWEEP_CUBE = 30
+PT_OPT_ADAPTIVE_WF = 31
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).

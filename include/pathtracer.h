@@ -591,8 +591,8 @@ int pt_adaptive_select(pt_context* ctx, const void* moments, const void* counts,
  * 0..min_batches-1 (at the seed base PT_OPT_SEED_BASE).  PT_ERR_INVALID without
  * PT_OPT_MOMENTS 1, a scene, lights, a camera or a frame; PT_ERR_UNSUPPORTED on
  * multi-device contexts, a partition of more than one rank, in stats mode, with
- * PT_OPT_COUNT_TRACED and with PT_OPT_KERNEL 3 (under auto the adaptive calls
- * run the path-recursive kernel). */
+ * PT_OPT_COUNT_TRACED and, unless PT_OPT_ADAPTIVE_WF is 1, with PT_OPT_KERNEL 3
+ * (under auto the adaptive calls then run the path-recursive kernel). */
 int pt_adaptive_begin(pt_context* ctx, const pt_adaptive_params* params);
 /* Enqueues up to `rounds` rounds: the rule over all tiles, the list of the
  * tiles whose count grew (ascending), and one launch that renders each listed
@@ -966,6 +966,20 @@ int pt_dist_finalize(pt_context* ctx);
  * hull walk.  A table with any other box runs the hull walk either way;
  * pt_sweep_walk tells which walk is in force.  Output is identical. */
 #define PT_OPT_SWEEP_CUBE 30
+/* PT_OPT_ADAPTIVE_WF: 1 = pt_adaptive_begin / pt_adaptive_advance run their
+ * rounds on the wavefront pipeline when PT_OPT_KERNEL is 0 or 3 (1, the
+ * explicit request for the path-recursive kernel, wins): every live tile's
+ * paths of the round in the path buffers, traced by the kernels pt_render's
+ * wavefront launches run -- the culled wide walk for a scene that has one and
+ * is not staged in LDS -- under the same options (PT_OPT_WIDE, PT_OPT_WIDE_NODE,
+ * PT_OPT_WF_FUSE, PT_OPT_WF_TAIL, PT_OPT_WF_REFILL, PT_OPT_WF_GRID,
+ * PT_OPT_WF_PATHS, PT_OPT_EXIT_SKIP, PT_OPT_SCENE_IN_LDS); PT_OPT_WF_STREAMS 2
+ * is not used by the rounds.  pt_last_kernel then reports 3 after
+ * pt_adaptive_begin.  0 (default) = the path-recursive rounds, and
+ * PT_OPT_KERNEL 3 is refused by the adaptive calls.  Every other refusal of the
+ * adaptive calls holds either way.  Output is identical: counts, live lists,
+ * accumulation image and moments. */
+#define PT_OPT_ADAPTIVE_WF 31
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
