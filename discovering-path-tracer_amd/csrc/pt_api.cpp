@@ -1095,6 +1095,7 @@ int pt_destroy(pt_context* c) {
   dev_free(c->d_moments);
   post_release(c);
   adaptive_release(c);
+  display_release(c);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1180,6 +1181,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->has_scene = false;
   c->guide_valid = false;
   temporal_forget(c);
+  display_forget(c);
   adaptive_forget(c);
   const int T = (int)(n_indices / 3);
   struct Staging {   // vertex/index copies live only until the triangle records are built
@@ -1377,6 +1379,7 @@ int pt_resize_and_clear(pt_context* c, int w, int h) {
     c->d_accum = nullptr;
     c->own_accum = false;
     temporal_forget(c);   // another size or another buffer
+    display_forget(c);
     PT_HIP(hipMalloc((void**)&c->d_accum, (size_t)w * h * sizeof(float4)));
     c->own_accum = true;
     c->width = w;
@@ -1393,7 +1396,10 @@ int pt_bind_accum(pt_context* c, void* ptr, int w, int h) {
   PT_HIP(hipSetDevice(c->device));
   { const int rc_ = quiesce(c); if (rc_) return rc_; }
   if (c->own_accum) dev_free(c->d_accum);
-  if (c->d_accum != (float4*)ptr || c->own_accum || c->width != w || c->height != h) temporal_forget(c);
+  if (c->d_accum != (float4*)ptr || c->own_accum || c->width != w || c->height != h) {
+    temporal_forget(c);
+    display_forget(c);
+  }
   c->d_accum = (float4*)ptr;
   c->own_accum = false;
   if (c->width != w || c->height != h) c->guide_valid = false;

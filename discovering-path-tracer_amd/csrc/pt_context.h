@@ -4,7 +4,7 @@
 // exchange, stats, timing); pt_plan.h the launch plan, every policy render_impl
 // carries out, as one pure function (plan_launch); pt_post.cpp the
 // post-processing chain (guide, filters, temporal accumulation);
-// pt_adaptive.cpp adaptive sampling; pt_dist.cpp
+// pt_adaptive.cpp adaptive sampling; pt_display.cpp the display transform; pt_dist.cpp
 // the RCCL step loop; pt_group.cpp the multi-device context.  The fields of
 // pt_context are grouped in that order.
 #pragma once
@@ -292,6 +292,25 @@ struct pt_context {
   size_t ad_var_cap = 0;
   bool ad_var_valid = false;
 
+  // ---- pt_display.cpp: the display transform (freed by display_release) -------------------
+  uint32_t* d_display = nullptr;       // pt_display's destination when the caller gives none: RGBA8 words
+  size_t display_cap = 0;
+  int display_w = 0, display_h = 0;    // size of the image d_display holds (0: none yet)
+  float* d_meter_sum = nullptr;        // the metering's partial per 16x16 tile: the sum of the terms
+  uint32_t* d_meter_n = nullptr;       // ... and the metered pixels
+  size_t meter_cap[2] = {0, 0};
+  void* d_meter_state = nullptr;       // ptdp::MeterState: the scale the last metering call used, its count
+  bool meter_have = false;             // ... and holds one: the next metering call has a previous scale
+  struct DisplayReadback {             // pt_display_readback_begin/end: as Readback, 4 B a pixel
+    uint32_t* dev = nullptr;
+    void* host = nullptr;
+    size_t bytes = 0;
+    hipEvent_t snap = nullptr, done = nullptr;
+    int ticket = 0;                    // 0 = free
+    int w = 0, h = 0;
+  } drb[2];
+  int drb_next_ticket = 1;
+
   // ---- pt_dist.cpp, pt_group.cpp ------------------------------------------------------
   DistState* dist = nullptr;           // pt_dist_init
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -305,6 +324,10 @@ inline void temporal_forget(pt_context* c) {
   c->t_samples = 0;
   c->t_guide_aside = false;
 }
+
+// The metering state of the display transform is forgotten (pt_display_reset; a new scene, frame size or
+// bound buffer): the next metering pt_display runs without a previous scale.
+inline void display_forget(pt_context* c) { c->meter_have = false; }
 
 // The adaptive state ends (a scene, light or params upload, a resize, a rebind, pt_clear_accum, any render):
 // pt_adaptive_advance and the reads then ask for a new pt_adaptive_begin.  The buffers stay.
@@ -422,6 +445,7 @@ int unpack_table(pt_context* c, const ptd::RenderParams& p, const std::vector<fl
 // ---- and what they give the core --------------------------------------------------------------
 void post_release(pt_context* c);      // frees what pt_post.cpp allocates (pt_destroy)
 void adaptive_release(pt_context* c);  // ... and pt_adaptive.cpp
+void display_release(pt_context* c);   // ... and pt_display.cpp
 // ---- what pt_post.cpp gives pt_adaptive.cpp: the variance-guided filter's passes from a variance plane
 // (pt_post.cpp var_filter), and the validated filter parameters
 int post_var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,

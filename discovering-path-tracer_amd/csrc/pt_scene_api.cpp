@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "pt_context.h"
+#include "pt_display.h"
 #include "scene/bvh.h"
 #include "scene/camera.h"
 #include "scene/light.h"
@@ -253,14 +254,45 @@ void png_chunk(FILE* f, const char* type, const std::vector<unsigned char>& data
   if (*ok) *ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
 }
 
-// linear -> 8-bit sRGB after clamping to [0,1]: what an sRGB swapchain shows
-// for the reference's RGBA32F image (VulkanRenderer copies it to a texture
-// that color_frag.frag outputs unchanged)
-unsigned char srgb8(float x) {
-  if (!(x > 0.0f)) return 0;
-  if (x >= 1.0f) return 255;
-  const double e = x <= 0.0031308f ? 12.92 * x : 1.055 * pow((double)x, 1.0 / 2.4) - 0.055;
-  return (unsigned char)(e * 255.0 + 0.5);
+// An 8-bit RGB PNG of a W x H image, zlib stream of stored (uncompressed) deflate blocks; rows
+// top-to-bottom, so the buffer's last row comes first.  channel(pixel, c): the byte of channel c.
+extern "C++" template <class Channel>
+bool write_png(FILE* f, int w, int h, const Channel& channel) {
+  bool ok = true;
+  static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+  ok = fwrite(sig, 1, 8, f) == 8;
+  std::vector<unsigned char> ihdr;
+  put_be32(&ihdr, (uint32_t)w);
+  put_be32(&ihdr, (uint32_t)h);
+  ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});   // 8-bit, truecolour, deflate, filter 0, no interlace
+  png_chunk(f, "IHDR", ihdr, &ok);
+  std::vector<unsigned char> raw;
+  raw.reserve((size_t)h * (1 + 3 * (size_t)w));
+  for (int y = h - 1; y >= 0; --y) {
+    raw.push_back(0);   // filter: none
+    for (int x = 0; x < w; ++x)
+      for (int c = 0; c < 3; ++c) raw.push_back(channel((size_t)y * w + x, c));
+  }
+  std::vector<unsigned char> z = {0x78, 0x01};
+  uint32_t a = 1, b = 0;   // Adler-32
+  for (size_t i = 0; i < raw.size(); ++i) {
+    a = (a + raw[i]) % 65521u;
+    b = (b + a) % 65521u;
+  }
+  for (size_t off = 0; off < raw.size() || off == 0; off += 65535) {
+    const size_t n = std::min<size_t>(65535, raw.size() - off);
+    z.push_back(off + n >= raw.size() ? 1 : 0);
+    z.push_back((unsigned char)(n & 0xff));
+    z.push_back((unsigned char)(n >> 8));
+    z.push_back((unsigned char)(~n & 0xff));
+    z.push_back((unsigned char)((~n >> 8) & 0xff));
+    z.insert(z.end(), raw.begin() + (long)off, raw.begin() + (long)(off + n));
+    if (raw.empty()) break;
+  }
+  put_be32(&z, (b << 16) | a);
+  png_chunk(f, "IDAT", z, &ok);
+  png_chunk(f, "IEND", {}, &ok);
+  return ok;
 }
 }  // namespace
 
@@ -281,42 +313,20 @@ int pt_write_image(const char* path, const float* rgba, int w, int h, int format
       ok = fwrite(rgb.data(), 4, rgb.size(), f) == rgb.size();
     }
   } else {
-    // 8-bit RGB PNG, zlib stream of stored (uncompressed) deflate blocks;
-    // rows top-to-bottom, so the accumulation buffer's last row comes first
-    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    ok = fwrite(sig, 1, 8, f) == 8;
-    std::vector<unsigned char> ihdr;
-    put_be32(&ihdr, (uint32_t)w);
-    put_be32(&ihdr, (uint32_t)h);
-    ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});   // 8-bit, truecolour, deflate, filter 0, no interlace
-    png_chunk(f, "IHDR", ihdr, &ok);
-    std::vector<unsigned char> raw;
-    raw.reserve((size_t)h * (1 + 3 * (size_t)w));
-    for (int y = h - 1; y >= 0; --y) {
-      raw.push_back(0);   // filter: none
-      for (int x = 0; x < w; ++x)
-        for (int c = 0; c < 3; ++c) raw.push_back(srgb8(rgba[((size_t)y * w + x) * 4 + c]));
-    }
-    std::vector<unsigned char> z = {0x78, 0x01};
-    uint32_t a = 1, b = 0;   // Adler-32
-    for (size_t i = 0; i < raw.size(); ++i) {
-      a = (a + raw[i]) % 65521u;
-      b = (b + a) % 65521u;
-    }
-    for (size_t off = 0; off < raw.size() || off == 0; off += 65535) {
-      const size_t n = std::min<size_t>(65535, raw.size() - off);
-      z.push_back(off + n >= raw.size() ? 1 : 0);
-      z.push_back((unsigned char)(n & 0xff));
-      z.push_back((unsigned char)(n >> 8));
-      z.push_back((unsigned char)(~n & 0xff));
-      z.push_back((unsigned char)((~n >> 8) & 0xff));
-      z.insert(z.end(), raw.begin() + (long)off, raw.begin() + (long)(off + n));
-      if (raw.empty()) break;
-    }
-    put_be32(&z, (b << 16) | a);
-    png_chunk(f, "IDAT", z, &ok);
-    png_chunk(f, "IEND", {}, &ok);
+    // the sRGB code of the colours clamped to [0,1] (pt_display.h srgb8_pow)
+    ok = write_png(f, w, h, [&](size_t i, int c) { return ptdp::srgb8_pow(rgba[i * 4 + c]); });
   }
+  if (fclose(f) != 0) ok = false;
+  if (!ok) return fail(PT_ERR_IO, std::string("write failed: ") + path);
+  return PT_OK;
+}
+
+int pt_write_png8(const char* path, const unsigned char* rgba8, int w, int h) {
+  if (!path || !rgba8) return fail(PT_ERR_INVALID, "null argument");
+  if (w <= 0 || h <= 0) return fail(PT_ERR_INVALID, "bad resolution");
+  FILE* f = fopen(path, "wb");
+  if (!f) return fail(PT_ERR_IO, std::string("cannot create ") + path);
+  bool ok = write_png(f, w, h, [&](size_t i, int c) { return rgba8[i * 4 + c]; });
   if (fclose(f) != 0) ok = false;
   if (!ok) return fail(PT_ERR_IO, std::string("write failed: ") + path);
   return PT_OK;

@@ -8,6 +8,7 @@
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
 //             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
 //             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]
+//             [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY]
 //
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
@@ -38,6 +39,12 @@
 // MAX samples for every pixel; -lum-floor sets the rule's floor (default: the
 // library's).  With -denoise-var the image written is pt_adaptive_denoise's.
 // -adaptive-wf runs the rounds on the wavefront pipeline (PT_OPT_ADAPTIVE_WF 1).
+// -display, -exposure and -auto-exposure send whatever image -png writes (raw,
+// filtered, temporal, ...) through the display transform on the device
+// (pt_display: tone map, exposure, metering with the given key; the other
+// parameters at their defaults) and write its bytes with pt_write_png8; a
+// filter then writes into an image of the driver's own.  Without any of the
+// three -png is pt_write_image's encode of the floats, as ever.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,6 +53,8 @@
 #include <chrono>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "pathtracer.h"
 
@@ -62,7 +71,8 @@ int main(int argc, char** argv) {
     fprintf(stderr,
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
             "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
-            "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]\n",
+            "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]\n"
+            "       [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY]\n",
             argv[0]);
     return 2;
   }
@@ -76,6 +86,9 @@ int main(int argc, char** argv) {
   bool adaptive = false, adaptive_wf = false;
   pt_adaptive_params ad;
   pt_adaptive_default_params(&ad);
+  bool display = false;
+  pt_display_params dp;
+  pt_display_default_params(&dp);
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -113,6 +126,21 @@ int main(int argc, char** argv) {
     }
     else if (!strcmp(argv[i], "-lum-floor")) ad.lum_floor = (float)atof(next());
     else if (!strcmp(argv[i], "-adaptive-wf")) adaptive_wf = true;
+    else if (!strcmp(argv[i], "-display")) {
+      const char* op = next();
+      display = true;
+      dp.tonemap = !strcmp(op, "reinhard") ? PT_TONEMAP_REINHARD : !strcmp(op, "aces") ? PT_TONEMAP_ACES
+                   : !strcmp(op, "clamp") ? PT_TONEMAP_CLAMP : -1;
+    }
+    else if (!strcmp(argv[i], "-exposure")) {
+      display = true;
+      dp.exposure = (float)atof(next());
+    }
+    else if (!strcmp(argv[i], "-auto-exposure")) {
+      display = true;
+      dp.auto_exposure = 1;
+      dp.key = (float)atof(next());
+    }
   }
   if (temporal_spatial && temporal <= 0) {
     fprintf(stderr, "-temporal-spatial needs -temporal K\n");
@@ -242,30 +270,56 @@ int main(int argc, char** argv) {
     printf("rendered %dx%d x %d spp in %.3f ms\n", W, H, spp, std::chrono::duration<double, std::milli>(r1 - r0).count());
   if (!out_path.empty() || !png_path.empty()) {
     std::vector<float> rgba((size_t)W * H * 4);
+    // With the display transform a filter writes into this image, which pt_display then reads
+    // (null: the library-owned one, read back as ever); src is the device image -png shows.
+    const bool shown = display && !png_path.empty();
+    void* filtered = nullptr;
+    const void* src = nullptr;   // null: the accumulation image
+    const bool filters = (temporal > 0 && progressive == 0) ? (temporal_spatial || denoise_var)
+                                                            : (denoise_var || denoise);
+    if (shown && filters && hipMalloc(&filtered, rgba.size() * sizeof(float)) != hipSuccess) {
+      fprintf(stderr, "no device memory for the filtered image\n");
+      return 1;
+    }
     if (temporal > 0 && progressive == 0) {
-      if (temporal_spatial) {
-        check(pt_temporal_denoise_spatial(ctx, nullptr, nullptr, nullptr), "temporal denoise spatial");
-        check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
-      } else if (denoise_var) {
-        check(pt_temporal_denoise(ctx, nullptr, nullptr), "temporal denoise");
-        check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
-      } else {
-        check(pt_read_temporal(ctx, rgba.data(), nullptr, nullptr), "read temporal");
-      }
+      if (temporal_spatial) check(pt_temporal_denoise_spatial(ctx, nullptr, nullptr, filtered), "temporal denoise spatial");
+      else if (denoise_var) check(pt_temporal_denoise(ctx, nullptr, filtered), "temporal denoise");
+      else src = pt_temporal_device_ptr(ctx, 0);
+      if (!filters) check(pt_read_temporal(ctx, rgba.data(), nullptr, nullptr), "read temporal");
     } else if (adaptive && denoise_var) {
-      check(pt_adaptive_denoise(ctx, nullptr, nullptr), "adaptive denoise");
-      check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+      check(pt_adaptive_denoise(ctx, nullptr, filtered), "adaptive denoise");
     } else if (denoise_var) {
-      check(pt_denoise_var(ctx, nullptr, nullptr), "denoise-var");
-      check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+      check(pt_denoise_var(ctx, nullptr, filtered), "denoise-var");
     } else if (denoise) {
-      check(pt_denoise(ctx, nullptr, nullptr, nullptr), "denoise");
-      check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+      check(pt_denoise(ctx, nullptr, nullptr, filtered), "denoise");
     } else {
       check(pt_read_accum(ctx, rgba.data(), rgba.size()), "read");
     }
+    if (filters && !filtered) check(pt_read_denoised(ctx, rgba.data(), rgba.size()), "read denoised");
+    if (filtered) {
+      src = filtered;
+      check(pt_synchronize(ctx), "sync");
+      if (hipMemcpy(rgba.data(), filtered, rgba.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        fprintf(stderr, "copy of the filtered image failed\n");
+        return 1;
+      }
+    }
     if (!out_path.empty()) check(pt_write_image(out_path.c_str(), rgba.data(), W, H, PT_IMAGE_PFM), "write pfm");
-    if (!png_path.empty()) check(pt_write_image(png_path.c_str(), rgba.data(), W, H, PT_IMAGE_PNG), "write png");
+    if (shown) {
+      std::vector<unsigned char> rgba8((size_t)W * H * 4);
+      check(pt_display(ctx, &dp, src, nullptr), "display");
+      check(pt_read_display(ctx, rgba8.data(), rgba8.size()), "read display");
+      check(pt_write_png8(png_path.c_str(), rgba8.data(), W, H), "write png");
+      if (dp.auto_exposure) {
+        float scale = 0.0f;
+        uint32_t n = 0;
+        check(pt_display_exposure(ctx, &scale, &n), "display exposure");
+        printf("display: auto exposure %.6g from %u metered pixels\n", scale, n);
+      }
+    } else if (!png_path.empty()) {
+      check(pt_write_image(png_path.c_str(), rgba.data(), W, H, PT_IMAGE_PNG), "write png");
+    }
+    if (filtered) (void)hipFree(filtered);
   }
   if (!guide_path.empty()) {
     std::vector<float> guide((size_t)W * H * 4);

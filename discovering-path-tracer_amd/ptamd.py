@@ -76,6 +76,8 @@ EXPORTS = [
     "pt_adaptive_default_params", "pt_adaptive_select_host", "pt_adaptive_select", "pt_adaptive_begin",
     "pt_adaptive_advance", "pt_adaptive_info", "pt_adaptive_read_counts", "pt_adaptive_read_live",
     "pt_adaptive_device_ptr", "pt_adaptive_denoise",
+    "pt_display_default_params", "pt_display", "pt_display_device_ptr", "pt_read_display", "pt_display_exposure",
+    "pt_display_reset", "pt_display_readback_begin", "pt_display_readback_end", "pt_display_host", "pt_write_png8",
 ]
 
 
@@ -120,6 +122,14 @@ class SpatialVarParams(ctypes.Structure):
 class AdaptiveParams(ctypes.Structure):
     _fields_ = [("min_batches", ctypes.c_uint32), ("max_batches", ctypes.c_uint32), ("step", ctypes.c_uint32),
                 ("threshold", ctypes.c_float), ("lum_floor", ctypes.c_float)]
+
+
+class DisplayParams(ctypes.Structure):
+    _fields_ = [("tonemap", ctypes.c_int), ("exposure", ctypes.c_float), ("auto_exposure", ctypes.c_int),
+                ("key", ctypes.c_float), ("white", ctypes.c_float), ("adapt", ctypes.c_float)]
+
+
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 
 
 class ReprojectImages(ctypes.Structure):
@@ -236,6 +246,15 @@ def lib():
             "pt_adaptive_read_live": ([vp, vp, sz, ctypes.POINTER(u32)], i32),
             "pt_adaptive_device_ptr": ([vp, i32], vp),
             "pt_adaptive_denoise": ([vp, ctypes.POINTER(DenoiseVarParams), vp], i32),
+            "pt_display_default_params": ([ctypes.POINTER(DisplayParams)], i32),
+            "pt_display": ([vp, ctypes.POINTER(DisplayParams), vp, vp], i32),
+            "pt_display_device_ptr": ([vp], vp), "pt_read_display": ([vp, vp, sz], i32),
+            "pt_display_exposure": ([vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(u32)], i32),
+            "pt_display_reset": ([vp], i32),
+            "pt_display_readback_begin": ([vp, ctypes.POINTER(DisplayParams), vp, ctypes.POINTER(i32)], i32),
+            "pt_display_readback_end": ([vp, i32, vp, sz], i32),
+            "pt_display_host": ([vp, i32, i32, ctypes.POINTER(DisplayParams), ctypes.POINTER(ctypes.c_float), vp], i32),
+            "pt_write_png8": ([ctypes.c_char_p, vp, i32, i32], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -447,6 +466,45 @@ def write_image(path, rgba, width, height, fmt="png"):
         raise PTError("rgba must hold width*height*4 floats")
     _check(lib().pt_write_image(str(path).encode(), a.ctypes.data, width, height, 1 if fmt == "png" else 0),
            "pt_write_image")
+
+
+def write_png8(path, rgba8, width, height):
+    """pt_write_png8: the PNG of (H, W, 4) uint8 pixels (display's), alpha dropped."""
+    a = np.ascontiguousarray(rgba8, np.uint8).reshape(-1)
+    if a.size != width * height * 4:
+        raise PTError("rgba8 must hold width*height*4 bytes")
+    _check(lib().pt_write_png8(str(path).encode(), a.ctypes.data, width, height), "pt_write_png8")
+
+
+def display_default_params():
+    """pt_display_default_params as a DisplayParams."""
+    p = DisplayParams()
+    _check(lib().pt_display_default_params(ctypes.byref(p)), "pt_display_default_params")
+    return p
+
+
+def _display_params(params):
+    """None (the library's defaults), a DisplayParams, or (tonemap, exposure,
+    auto_exposure, key, white, adapt) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, DisplayParams):
+        return ctypes.byref(params)
+    tm, ex, au, key, white, adapt = params
+    return ctypes.byref(DisplayParams(int(tm), float(ex), int(au), float(key), float(white), float(adapt)))
+
+
+def display_host(rgba, width, height, params=None, auto_scale=0.0):
+    """pt_display_host: ((H, W, 4) uint8, the auto scale the call used).
+    auto_scale: the previous scale, 0.0 for none (read only when metering)."""
+    a = np.ascontiguousarray(rgba, np.float32).reshape(-1)
+    if a.size != width * height * 4:
+        raise PTError("rgba must hold width*height*4 floats")
+    out = np.empty(a.size, np.uint8)
+    scale = ctypes.c_float(auto_scale)
+    _check(lib().pt_display_host(a.ctypes.data, width, height, _display_params(params), ctypes.byref(scale),
+                                 out.ctypes.data), "pt_display_host")
+    return out.reshape(height, width, 4), scale.value
 
 
 def default_camera():
@@ -975,6 +1033,43 @@ class Renderer:
             return None
         out = np.empty(self.width * self.height * 4, np.float32)
         _check(lib().pt_read_denoised(self._c, out.ctypes.data, out.size), "pt_read_denoised")
+        return out.reshape(self.height, self.width, 4)
+
+    def display(self, params=None, src_ptr=None, dst_ptr=None):
+        """pt_display: src (default: the accumulation image) through exposure,
+        tone map and the sRGB encode into dst; with dst_ptr None the
+        library-owned result is read back and returned as (H, W, 4) uint8."""
+        _check(lib().pt_display(self._c, _display_params(params), src_ptr, dst_ptr), "pt_display")
+        if dst_ptr is not None:
+            return None
+        return self.read_display()
+
+    def display_ptr(self):
+        return lib().pt_display_device_ptr(self._c)
+
+    def read_display(self):
+        out = np.empty(self.width * self.height * 4, np.uint8)
+        _check(lib().pt_read_display(self._c, out.ctypes.data, out.size), "pt_read_display")
+        return out.reshape(self.height, self.width, 4)
+
+    def display_exposure(self):
+        """(auto scale the last metering display used, pixels it metered); waits."""
+        s, n = ctypes.c_float(0), ctypes.c_uint32(0)
+        _check(lib().pt_display_exposure(self._c, ctypes.byref(s), ctypes.byref(n)), "pt_display_exposure")
+        return s.value, n.value
+
+    def display_reset(self):
+        _check(lib().pt_display_reset(self._c), "pt_display_reset")
+
+    def display_readback_begin(self, params=None, src_ptr=None):
+        t = ctypes.c_int(0)
+        _check(lib().pt_display_readback_begin(self._c, _display_params(params), src_ptr, ctypes.byref(t)),
+               "pt_display_readback_begin")
+        return t.value
+
+    def display_readback_end(self, ticket):
+        out = np.empty(self.width * self.height * 4, np.uint8)
+        _check(lib().pt_display_readback_end(self._c, ticket, out.ctypes.data, out.size), "pt_display_readback_end")
         return out.reshape(self.height, self.width, 4)
 
     def set_stats_mode(self, on):

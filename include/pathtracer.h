@@ -58,7 +58,11 @@ extern "C" {
  * adaptive sampling (pt_adaptive_params, pt_adaptive_default_params,
  * pt_adaptive_select_host, pt_adaptive_select, pt_adaptive_begin,
  * pt_adaptive_advance, pt_adaptive_info, pt_adaptive_read_counts,
- * pt_adaptive_read_live, pt_adaptive_device_ptr, pt_adaptive_denoise). */
+ * pt_adaptive_read_live, pt_adaptive_device_ptr, pt_adaptive_denoise); the
+ * display transform (pt_display_params, pt_display_default_params, pt_display,
+ * pt_display_device_ptr, pt_read_display, pt_display_exposure, pt_display_reset,
+ * pt_display_readback_begin, pt_display_readback_end, pt_display_host,
+ * pt_write_png8). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -633,6 +637,81 @@ void* pt_adaptive_device_ptr(pt_context* ctx, int which);
  * pt_render_packed, pt_temporal_advance). */
 int pt_adaptive_denoise(pt_context* ctx, const pt_denoise_var_params* params, void* dst_device);
 
+/* ---- display transform: exposure, tone map, 8-bit sRGB out ---------------
+ * The last step of the reference's loop on the device: a W x H float4 image
+ * becomes one packed RGBA8 word a pixel (r the lowest byte, alpha 255), in the
+ * row order of the source, so a display or an encoder reads a quarter of the
+ * bytes.  The statement (csrc/pt_display.h), per pixel, alpha not read:
+ *
+ *   v = c * scale              scale = exposure, or exposure * auto_scale
+ *   v = min(max(v, 0), 2^40)   IEEE minNum/maxNum: NaN -> 0, -x -> 0, +inf -> 2^40
+ *   PT_TONEMAP_CLAMP     nothing: an sRGB swapchain showing the float image
+ *   PT_TONEMAP_REINHARD  L = lum(v); Lp = (L * (1 + L / (white * white))) / (1 + L);
+ *                        v = v * (Lp / L) when L > 0
+ *   PT_TONEMAP_ACES      (x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14) per channel
+ *   code = the 8-bit sRGB code of v: exactly what PT_IMAGE_PNG encodes, for
+ *          every float (a table of 255 thresholds, checked against the
+ *          double-precision statement for all 2^32 bit patterns)
+ *
+ * With the default parameters the bytes are those pt_write_image puts into a
+ * PNG.  Every operation is a single IEEE fp32 operation in the stated order, so
+ * pt_display and pt_display_host give the same bytes.
+ *
+ * auto_exposure 1 meters the source first: the pixels whose luminance
+ * L = lum(max(c, 0)) is finite and > 0 (a culled background of exact zeros does
+ * not count), the sum of log(L) over them by a fixed tree (per 16x16 tile, then
+ * over the tiles; pt_display.h), mean = sum / n, target = key / exp(mean).  The
+ * first metering call after a reset uses auto_scale = target, a later one
+ * prev + (target - prev) * adapt (adapt 1: target), prev being the scale the
+ * call before used; a source with no metered pixel keeps prev, or 1 without
+ * one.  The scale lives in device memory and the display kernel reads it from
+ * there: nothing waits on the host.  It survives across calls (eye adaptation
+ * in a pt_temporal_advance loop); pt_display_reset, a change of frame size or
+ * of the bound buffer and a scene upload forget it. */
+#define PT_TONEMAP_CLAMP 0
+#define PT_TONEMAP_REINHARD 1
+#define PT_TONEMAP_ACES 2
+typedef struct pt_display_params {
+  int   tonemap;        /* PT_TONEMAP_CLAMP | _REINHARD | _ACES */
+  float exposure;       /* finite, > 0; default 1 */
+  int   auto_exposure;  /* 0 | 1; default 0 */
+  float key;            /* finite, > 0; default 0.18 */
+  float white;          /* finite, > 0, white*white finite non-zero; default 4 */
+  float adapt;          /* in (0, 1]; default 1 */
+} pt_display_params;
+int pt_display_default_params(pt_display_params* out);
+/* Enqueues the transform of src_device (null: the accumulation image; else any
+ * W x H float4 image of the context's frame size, 16-B aligned: pt_denoise's,
+ * pt_temporal_device_ptr's, ...) into dst_device (null: a library-owned image,
+ * pt_display_device_ptr / pt_read_display; else W*H 32-bit words, 4-B aligned,
+ * not overlapping the source).  params null: the defaults.  PT_ERR_INVALID for
+ * bad parameters or without an accumulation image (it gives the frame size);
+ * PT_ERR_UNSUPPORTED on a pt_create_multi context, as every call below that
+ * takes a context. */
+int pt_display(pt_context* ctx, const pt_display_params* params, const void* src_device, void* dst_device);
+/* The library-owned image of the last pt_display with a null destination; null
+ * when there is none of the current frame size. */
+void* pt_display_device_ptr(pt_context* ctx);
+/* Waits and copies that image: n_bytes >= W*H*4. */
+int pt_read_display(pt_context* ctx, unsigned char* rgba8, size_t n_bytes);
+/* Waits.  auto_scale: the scale the last metering pt_display used (1 when none
+ * has run since the state was forgotten); n_metered: the pixels it metered.
+ * Either pointer may be null. */
+int pt_display_exposure(pt_context* ctx, float* auto_scale, uint32_t* n_metered);
+int pt_display_reset(pt_context* ctx);
+/* The 8-bit sibling of pt_readback_begin/end: the display kernel writes the
+ * snapshot itself (4 B a pixel instead of a 16-B device-to-device copy), and
+ * the copy to pinned host memory on the second stream moves W*H*4 bytes.  Two
+ * slots and the same ticket rules: a third begin recycles the older slot, whose
+ * ticket is then unknown; a ticket is collected once. */
+int pt_display_readback_begin(pt_context* ctx, const pt_display_params* params, const void* src_device, int* ticket);
+int pt_display_readback_end(pt_context* ctx, int ticket, unsigned char* rgba8, size_t n_bytes);
+/* The same transform on the host, of a W x H RGBA32F image into W*H*4 bytes.
+ * auto_scale_io (metering only; may be null): in, the previous scale or 0 for
+ * none; out, the scale this call used. */
+int pt_display_host(const float* rgba, int w, int h, const pt_display_params* params,
+                    float* auto_scale_io, unsigned char* rgba8);
+
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile
  * b = by*blocks_x + (bx - by) mod blocks_x (rows rotated by their index, so
@@ -1095,6 +1174,10 @@ int pt_pack_light(const float position[3], const float normal[3], const float in
 #define PT_IMAGE_PFM 0
 #define PT_IMAGE_PNG 1
 int pt_write_image(const char* path, const float* rgba, int width, int height, int format);
+/* Writes W x H RGBA8 pixels (pt_read_display's) as the same PNG: top row = last
+ * buffer row, alpha dropped.  Of pt_display's bytes at the default parameters
+ * it is the file pt_write_image(PT_IMAGE_PNG) writes of the floats. */
+int pt_write_png8(const char* path, const unsigned char* rgba8, int width, int height);
 /* Camera getters for the reference's default orbit camera, as the UBO
  * (Camera.cpp:4-10, 84-106): pos (0,0,5) dir (0,0,-1) up (0,1,0) fov 60. */
 int pt_default_camera(float camera_ubo[16]);
