@@ -150,7 +150,7 @@ struct ImageFetch {
 // variance of the mean instead of a fixed sigma_color (Schied et al., SVGF, HPG
 // 2017), from the luminance moments the render kernels fold (PT_OPT_MOMENTS):
 //   lum(r,g,b) = (0.2126f * r + 0.7152f * g) + 0.0722f * b
-//   var0_p = fmax_(0, m2_p - m1_p * m1_p) / float(n - 1)
+//   var0_p = fmax_(0, m2_p - m1_p * m1_p) / float(n - 1)      (fmax_(0, x) here and below: clamp0_, x > 0 ? x : +0)
 //   pass i = 0 .. iterations-1, s = 1 << i, on colour c and variance v (v = var0 in pass 0):
 //     gv_p  = (sum of (g[|dx|] * g[|dy|]) * v_q) / (sum of g[|dx|] * g[|dy|])
 //             over q = p + (dx, dy), dy = -1..1 outer, dx = -1..1 inner, spacing 1,
@@ -164,7 +164,12 @@ struct ImageFetch {
 // sigma_lum is the same in every pass: the variance shrinks by itself.
 PT_FN float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
-PT_FN float var_of_mean(float m1, float m2, uint32_t n) { return fmax_(0.0f, m2 - m1 * m1) / (float)(n - 1u); }
+// The clamp of a variance at zero, the fmax_(0, x) of the statements: x where x > 0, else +0 -- for a NaN (as
+// maxNum gives) and for -0, which m2 = -0 beside m1 = +-0 produces.  maxNum may return either zero for (+0, -0),
+// and the host's compile of fmax_ did: -0 at one call site, +0 at another.  A comparison has one answer everywhere.
+PT_FN float clamp0_(float x) { return x > 0.0f ? x : 0.0f; }
+
+PT_FN float var_of_mean(float m1, float m2, uint32_t n) { return clamp0_(m2 - m1 * m1) / (float)(n - 1u); }
 
 PT_FN bool var_params_ok(int iterations, float sigma_lum, float sigma_normal, float sigma_depth) {
   if (iterations < 1 || iterations > kMaxIterations) return false;
@@ -372,7 +377,7 @@ PT_FN ReprojOut reproject_pixel(const HistImages& hist, const CamBasis& B, const
     o.m.y = hm2 + (m.y - hm2) * a;
     o.len = N + fn;
   }
-  o.var = fmax_(0.0f, o.m.y - o.m.x * o.m.x) / fmax_(o.len - 1.0f, 1.0f);
+  o.var = clamp0_(o.m.y - o.m.x * o.m.x) / fmax_(o.len - 1.0f, 1.0f);
   return o;
 }
 
@@ -434,7 +439,7 @@ PT_FN float spatial_var_pixel(const Fetch& fetch, int W, int H, int x, int y, in
     }
   }
   const float M1 = s1 / sw, M2 = s2 / sw;
-  return fmax_(0.0f, M2 - M1 * M1) / lenp;
+  return clamp0_(M2 - M1 * M1) / lenp;
 }
 
 struct SpatialImageFetch {

@@ -273,6 +273,19 @@ int pt_readback_end(pt_context* ctx, int ticket, float* rgba, size_t n_floats);
  * The centre tap weighs 9/64, so sum_w > 0 for finite input.  The passes
  * ping-pong between two library-owned images; the source is only read.
  *
+ * Non-finite and extreme input.  "The same bits" between a kernel and its host
+ * function, here and for every function further down, means: a NaN where the
+ * other has a NaN (its sign and payload are the platform's), every other float
+ * the same bits, the sign of a zero included.  That holds for any input bits:
+ * NaN, infinities, negative and subnormal values, magnitudes whose squares
+ * overflow.  No filter skips a tap of weight 0, so a tap on an infinite colour
+ * adds 0 * inf = NaN: one infinite pixel turns the 25 pixels that tap it into
+ * NaN in one pass, the (4 (2^k - 1) + 1)^2 block around it in k passes.  A range
+ * test written x < y or !(x > y) is false, respectively true, for a NaN, as
+ * written.  fmax(0, x), the clamp of a variance, is x where x > 0 and +0
+ * otherwise -- for a NaN and for -0 too; every other fmin / fmax is minNum /
+ * maxNum (a NaN operand yields the other one) and never sees two zeros.
+ *
  * Defaults (pt_denoise_default_params): 5 iterations, sigma_color 16,
  * sigma_normal 0.35, sigma_depth 0.25, chosen on two 256x256 8-spp frames
  * against 256-spp frames of the same view (mean squared rgb error, raw ->
@@ -498,6 +511,10 @@ int pt_temporal_denoise(pt_context* ctx, const pt_denoise_var_params* params, vo
  *     w   = exp(-(d2n / (sn*sn) + (dz*dz) / (sz*sz))) * len_q
  *     sw += w;   s1 += w * m_q.x;   s2 += w * m_q.y
  *   M1 = s1 / sw;   M2 = s2 / sw;   out_p = fmax(0, M2 - M1 * M1) / len_p
+ * A tap whose guide compares equal to the centre's in all four components (the
+ * centre itself, a miss beside a miss) weighs len_q itself: exp(-0) * len_q for
+ * a finite guide, and the defined weight where an infinite component would make
+ * dz = inf - inf.
  * The centre tap weighs len_p >= 1, so sw > 0 for finite input; a hit next to a
  * miss has dz*dz = inf, hence w = 0; two misses pool their zero moments.  A tap
  * weighs its sample count: M2 - M1 * M1 is the pooled variance of one sample,

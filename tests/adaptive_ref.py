@@ -12,6 +12,8 @@ inside the frame:
 Every operation is one float32 numpy operation (IEEE, rounded once)."""
 import numpy as np
 
+from denoise_var_ref import clamp0
+
 F = np.float32
 FLT_MAX = np.finfo(np.float32).max
 
@@ -24,7 +26,7 @@ def pixel_error(m1, m2, n, lum_floor):
     """e_p of arrays of moments at the per-pixel counts n (uint32, >= 2)."""
     m1, m2 = np.asarray(m1, F), np.asarray(m2, F)
     with np.errstate(all="ignore"):
-        var = np.fmax(F(0), m2 - m1 * m1) / (n.astype(np.uint32) - np.uint32(1)).astype(F)
+        var = clamp0(m2 - m1 * m1) / (n.astype(np.uint32) - np.uint32(1)).astype(F)
         e = np.sqrt(var) / np.fmax(m1, F(lum_floor))
         finite = (np.abs(m1) <= FLT_MAX) & (np.abs(m2) <= FLT_MAX)
     return np.where(finite, e, F(np.inf)).astype(F)

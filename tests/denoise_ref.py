@@ -49,7 +49,7 @@ def atrous(rgba, guide, W, H, params=DEFAULTS):
     ys, xs = np.mgrid[0:H, 0:W]
     sn2 = F(sigma_normal) * F(sigma_normal)
     sz2 = F(sigma_depth) * F(sigma_depth)
-    with np.errstate(over="ignore", invalid="ignore"):
+    with np.errstate(all="ignore"):
         for i in range(iterations):
             s = 1 << i
             sc = F(sigma_color) * F(2.0 ** -i)

@@ -33,9 +33,19 @@ def fold_moments(moments, colours, batch):
     return out
 
 
+def clamp0(x):
+    """The statement's fmax_(0, x): x where x > 0, else +0 -- for a NaN too
+    (fmax_ is maxNum) and for -0 (+0 is the first operand and the larger zero).
+    Spelt out because numpy's fmax returns either zero, by array length."""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.asarray(x, F) > 0, x, F(0)).astype(F)
+
+
 def var_of_mean(moments, n):
+    """clamp0(m2 - m1 * m1) / float(n - 1)."""
     m1, m2 = moments[..., 0], moments[..., 1]
-    return (np.maximum(F(0), m2 - m1 * m1) / F(n - 1)).astype(F)
+    with np.errstate(all="ignore"):
+        return (clamp0(m2 - m1 * m1) / F(n - 1)).astype(F)
 
 
 def atrous_var(rgba, moments, n_samples, guide, W, H, params=DEFAULTS):
@@ -48,7 +58,7 @@ def atrous_var(rgba, moments, n_samples, guide, W, H, params=DEFAULTS):
     sl = F(sigma_lum)
     sn2 = F(sigma_normal) * F(sigma_normal)
     sz2 = F(sigma_depth) * F(sigma_depth)
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+    with np.errstate(all="ignore"):
         for i in range(iterations):
             s = 1 << i
             gsum = np.zeros((H, W), F)

@@ -8,6 +8,7 @@ and tests/test_gpu_spatial_var.py."""
 import numpy as np
 
 import oracle_lib
+from denoise_var_ref import clamp0
 
 F = np.float32
 DEFAULTS = (2, 1, 1.0, 0.5)              # pt_spatial_var_default_params: below, radius, sigma_normal, sigma_depth
@@ -26,7 +27,7 @@ def spatial_variance(moments, length, variance, guide, W, H, params=DEFAULTS):
     sz2 = F(sigma_depth) * F(sigma_depth)
     ys, xs = np.mgrid[0:H, 0:W]
     sw, s1, s2 = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W), F)
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+    with np.errstate(all="ignore"):
         for dy in range(-r, r + 1):
             for dx in range(-r, r + 1):
                 qx, qy = xs + dx, ys + dy
@@ -38,18 +39,23 @@ def spatial_variance(moments, length, variance, guide, W, H, params=DEFAULTS):
                 dz = g[..., 3] - gq[..., 3]
                 arg = -(d2n / sn2 + (dz * dz) / sz2)
                 w = oracle_lib.math(1, arg.astype(F).reshape(-1)).reshape(H, W) * lq
+                # a tap whose guide compares equal to the centre's weighs len_q itself: exp(-0) * len_q for
+                # finite guides, and the defined weight where an infinite component would make dz inf - inf
+                w = np.where(np.all(g == gq, axis=-1), lq, w)
                 sw = np.where(ok, sw + w, sw)
                 s1 = np.where(ok, s1 + w * mq[..., 0], s1)
                 s2 = np.where(ok, s2 + w * mq[..., 1], s2)
         M1, M2 = s1 / sw, s2 / sw
-        est = (np.maximum(F(0), M2 - M1 * M1) / l).astype(F)
-    return np.where(l < F(below), est, v).astype(F)
+        est = (clamp0(M2 - M1 * M1) / l).astype(F)                # fmax_(0, x): a NaN difference gives 0
+        short = l < F(below)                                       # false for a NaN length: the variance passes
+    return np.where(short, est, v).astype(F)
 
 
 def variance_of(moments, length):
     """The reprojection statement's out_var of the moments and lengths."""
     m1, m2 = moments[..., 0], moments[..., 1]
-    return (np.maximum(F(0), m2 - m1 * m1) / np.maximum(length - F(1), F(1))).astype(F)
+    with np.errstate(all="ignore"):
+        return (clamp0(m2 - m1 * m1) / np.fmax(length - F(1), F(1))).astype(F)
 
 
 def make_inputs(W, H, seed, only=None):

@@ -41,6 +41,22 @@ def same(got, want, what=""):
                              f"want {wf[bad[0]]} ({w.reshape(-1)[bad[0]]:#010x})")
 
 
+def same_nan(got, want, what=""):
+    """NaN exactly where NaN (its sign and payload are the platform's), every
+    other float the same bits."""
+    g, w = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    assert g.size == w.size, f"{what}: {g.size} floats {g.shape} against {w.size} {w.shape}"
+    assert g.shape == w.shape or g.ndim == 1 or w.ndim == 1, f"{what}: shape {g.shape} against {w.shape}"
+    nan_g, nan_w = np.isnan(g).reshape(-1), np.isnan(w).reshape(-1)
+    bad = np.flatnonzero(nan_g != nan_w)
+    if bad.size:
+        at = np.unravel_index(bad[0], g.shape if g.ndim >= w.ndim else w.shape)
+        raise AssertionError(f"{what}: NaN pattern differs in {bad.size} of {g.size} floats; first at "
+                             f"{tuple(int(k) for k in at)}: got {g.reshape(-1)[bad[0]]}, want {w.reshape(-1)[bad[0]]}")
+    same(np.where(nan_g, np.float32(0), g.reshape(-1)).reshape(g.shape),
+         np.where(nan_w, np.float32(0), w.reshape(-1)).reshape(w.shape), what)
+
+
 def read_pfm(path):
     """A little-endian colour PFM as (h, w, 3) float32, rows in file order."""
     with open(path, "rb") as f:
@@ -146,6 +162,15 @@ def read_device(r, ptr, shape):
     out = np.empty(shape, np.float32)
     assert hip().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(out.nbytes), 2) == 0
     return out
+
+
+def write_device(r, ptr, array):
+    """read_device's counterpart: the float32 array copied over a library-owned
+    image, behind the context's work and done when the call returns."""
+    assert ptr, "no such device image"
+    r.synchronize()
+    a = np.ascontiguousarray(array, np.float32)
+    assert hip().hipMemcpy(ctypes.c_void_p(ptr), ctypes.c_void_p(a.ctypes.data), ctypes.c_size_t(a.nbytes), 1) == 0
 
 
 def dev(a):

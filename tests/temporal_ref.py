@@ -99,13 +99,13 @@ def reproject(cam_cur, cam_prev, W, H, n, color, moments, guide, history=None, p
                     sw = np.where(valid, sw + b, sw)
                     sc = np.where(valid[..., None], sc + b[..., None] * hcq[..., :3], sc)
                     sm = np.where(valid[..., None], sm + b[..., None] * hmq, sm)
-                    lmin = np.where(valid, np.minimum(lmin, hlq), lmin)
+                    lmin = np.where(valid, np.fmin(lmin, hlq), lmin)
                     nvalid += valid
             found = inside & (sw > F(0))
             h = (sc / sw[..., None]).astype(F)
             h_m = (sm / sw[..., None]).astype(F)
-            N = np.minimum(lmin, F(max_history))
-            a = np.maximum(F(alpha_min), fn / (N + fn)).astype(F)
+            N = np.fmin(lmin, F(max_history))
+            a = np.fmax(F(alpha_min), fn / (N + fn)).astype(F)
             bc = (h + (c[..., :3] - h) * a[..., None]).astype(F)
             bm = (h_m + (m - h_m) * a[..., None]).astype(F)
         out_c[..., :3] = np.where(found[..., None], bc, c[..., :3])
@@ -117,7 +117,8 @@ def reproject(cam_cur, cam_prev, W, H, n, color, moments, guide, history=None, p
         info["no_valid"] = int(np.count_nonzero(inside & ~found))
         info["blended"] = int(np.count_nonzero(found))
         info["taps"] = [int(np.count_nonzero(found & (nvalid == k))) for k in range(5)]
-    var = (np.maximum(F(0), out_m[..., 1] - out_m[..., 0] * out_m[..., 0]) / np.maximum(out_len - F(1), F(1))).astype(F)
+    with np.errstate(all="ignore"):
+        var = (V.clamp0(out_m[..., 1] - out_m[..., 0] * out_m[..., 0]) / np.fmax(out_len - F(1), F(1))).astype(F)
     return out_c, out_m, out_len, var, info
 
 
@@ -133,7 +134,7 @@ def atrous_var_plane(rgba, variance, guide, W, H, params=V.DEFAULTS):
     sz2 = F(sigma_depth) * F(sigma_depth)
     g5 = (F(3.0 / 8.0), F(1.0 / 4.0), F(1.0 / 16.0))
     g3 = (F(0.5), F(0.25))
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+    with np.errstate(all="ignore"):
         for i in range(iterations):
             s = 1 << i
             gsum, gw = np.zeros((H, W), F), np.zeros((H, W), F)

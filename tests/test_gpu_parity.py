@@ -11,7 +11,7 @@ import oracle_lib as O
 import ptamd
 import scenes
 import support
-from support import renderer, same
+from support import renderer, same, same_nan
 
 pytestmark = pytest.mark.gpu
 
@@ -668,11 +668,9 @@ def test_shadow_skip_light_intensities(lds, kernel):
     r.render(0, 3)
     gpu = r.read_accum()
     ref, _ = _oracle(v, i, n, 40, 32, nb=3, cam=cam, lights=lights)
-    nan_g, nan_r = np.isnan(gpu), np.isnan(ref)
-    assert np.array_equal(nan_g, nan_r), f"NaN pattern differs in {np.count_nonzero(nan_g != nan_r)} floats"
+    nan_r = np.isnan(ref)
     assert nan_r.any() and (~nan_r).any()
-    same(np.where(nan_g, 0, gpu).astype(np.float32), np.where(nan_r, 0, ref).astype(np.float32),
-                 f"kernel {kernel} lds {lds}")
+    same_nan(gpu, ref, f"kernel {kernel} lds {lds}")
 
 
 # ---- launch timing (bench.py's kernel_ms / launch_interval_ms) -------------

@@ -61,6 +61,38 @@ def test_oracle_math_special_values():
     assert abs(O.math(FN["log"], np.float32([1e-38]))[0] - np.log(1e-38)) < 1e-4
 
 
+def _exp_edges():
+    """exp's special paths: NaN of both signs and with a payload, the infinities, the overflow threshold
+    88.72284 and its neighbours, the underflow threshold -103.97208 and its neighbours, and arguments
+    across the subnormal results (k < -125: the two-step scaling)."""
+    x = np.float32([88.72283935546875, -103.972084045410156, 88.72284, -103.97208, 88.0, -87.0, -87.33655, -0.0, 0.0])
+    x = np.concatenate([x, np.nextafter(x[:2], np.float32(np.inf)), np.nextafter(x[:2], np.float32(-np.inf)),
+                        np.linspace(-104.0, -87.0, 4001).astype(np.float32)])
+    special = np.array([0x7fc00000, 0xffc00000, 0x7fc12345, 0x7f800000, 0xff800000], np.uint32).view(np.float32)
+    return np.concatenate([special, x])
+
+
+def test_oracle_exp_edges():
+    """Known answers, independent of the implementation: NaN for NaN, +inf for +inf and for every
+    argument whose exp exceeds FLT_MAX by more than rounding, +0 for -inf and below the last subnormal's
+    half, and within 1.5 ulp of the subnormal spacing of libm's double exp across the subnormal results."""
+    x = _exp_edges()
+    got = O.math(FN["exp"], x)
+    assert np.all(np.isnan(got[:3])) and got[3] == np.inf and got[4] == 0.0 and not np.signbit(got[4])
+    assert got[5] == np.inf                      # the last argument not cut off above: exp(x) = 1.0000003 * FLT_MAX
+    assert got[6] == 0.0                         # the last not cut off below: exp(x) = 0.499996 * 2^-149
+    assert got[12] == 1.0 and got[13] == 1.0
+    fin = x[5:].astype(np.float64)
+    want = np.exp(fin)
+    y = got[5:].astype(np.float64)
+    over = want > 1.0000001 * float(np.finfo(np.float32).max)
+    assert np.all(y[over] == np.inf) and np.count_nonzero(over) >= 2
+    sub = want < float(np.finfo(np.float32).tiny)
+    assert np.count_nonzero(sub) > 3000 and np.any(y[sub] == 0) and np.any(y[sub] > 0)
+    assert np.max(np.abs(y[sub] - want[sub])) <= 1.5 * 2.0 ** -149
+    assert not np.isnan(got[3:]).any() and np.all(got[3:] >= 0)
+
+
 def _pcg_numpy(seed, n):
     """Independent restatement of stepAndOutputRNGFloat (raytrace_comp.comp:209-216)."""
     s = np.uint32(seed)
@@ -96,6 +128,15 @@ def test_device_math_bitwise_equals_oracle(name):
     ref = O.math(FN[name], x)
     bad = np.flatnonzero(dev.view(np.uint32) != ref.view(np.uint32))
     assert bad.size == 0, f"{name}: {bad.size} mismatches, e.g. x={x[bad[:3]]} dev={dev[bad[:3]]} ref={ref[bad[:3]]}"
+
+
+@pytest.mark.gpu
+def test_device_exp_edges_equal_oracle():
+    """pt_math.h's exp_ on the device at the edges of test_oracle_exp_edges: NaN where NaN, all else bitwise."""
+    import ptamd
+    from support import same_nan
+    x = _exp_edges()
+    same_nan(ptamd.device_math(FN["exp"], x), O.math(FN["exp"], x), "exp_ at its edges")
 
 
 @pytest.mark.gpu

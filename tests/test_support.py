@@ -3,7 +3,7 @@ and the PFM reader."""
 import numpy as np
 import pytest
 
-from support import bits, read_pfm, same
+from support import bits, read_pfm, same, same_nan
 
 F = np.float32
 
@@ -28,6 +28,23 @@ def test_same_compares_nan_payloads():
     assert np.isnan(_nan(5)[0]) and np.isnan(_nan(6)[0]) and bits(_nan(5))[0] != bits(_nan(6))[0]
     with pytest.raises(AssertionError, match="differ"):
         same(_nan(5), _nan(6), "two NaNs")
+
+
+def test_same_nan_takes_any_nan_for_a_nan_and_nothing_else():
+    neg = np.array([0xFFC00000], np.uint32).view(F)
+    a = np.concatenate([_nan(5), [F(1.5), F(-0.0), F(np.inf)]]).astype(F)
+    a[0] = _nan(5)[0]
+    b = a.copy()
+    b[0] = neg[0]
+    same_nan(a, b, "another sign and payload")
+    with pytest.raises(AssertionError, match="NaN pattern differs in 1 of 4"):
+        same_nan(a, np.array([1.0, 1.5, -0.0, np.inf], F), "a number for a NaN")
+    with pytest.raises(AssertionError, match="NaN pattern differs"):
+        same_nan(np.array([np.inf], F), _nan(0), "inf is not NaN")
+    with pytest.raises(AssertionError, match="1 of 4 floats differ"):
+        same_nan(a, np.concatenate([a[:2], [F(0.0), F(np.inf)]]).astype(F), "the zeros apart")
+    with pytest.raises(AssertionError):
+        same_nan(np.zeros((2, 3), F), np.zeros((3, 2), F), "shape")
 
 
 def test_same_never_broadcasts():
