@@ -1096,6 +1096,7 @@ int pt_destroy(pt_context* c) {
   post_release(c);
   adaptive_release(c);
   display_release(c);
+  rays_release(c);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1588,6 +1589,7 @@ static const IntOption kIntOptions[] = {
     {PT_OPT_EXIT_SKIP, &pt_context::opt_exit_skip, 0, 1, "PT_OPT_EXIT_SKIP takes 0 or 1"},
     {PT_OPT_SWEEP_CUBE, &pt_context::opt_sweep_cube, 0, 1, "PT_OPT_SWEEP_CUBE takes 0 or 1"},
     {PT_OPT_ADAPTIVE_WF, &pt_context::opt_adaptive_wf, 0, 1, "PT_OPT_ADAPTIVE_WF takes 0 or 1"},
+    {PT_OPT_RAYS_REFILL, &pt_context::opt_rays_refill, 0, 1, "PT_OPT_RAYS_REFILL takes 0 or 1"},
 };
 
 int pt_set_option(pt_context* c, int key, int value) {

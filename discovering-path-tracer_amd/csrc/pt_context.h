@@ -4,7 +4,8 @@
 // exchange, stats, timing); pt_plan.h the launch plan, every policy render_impl
 // carries out, as one pure function (plan_launch); pt_post.cpp the
 // post-processing chain (guide, filters, temporal accumulation);
-// pt_adaptive.cpp adaptive sampling; pt_display.cpp the display transform; pt_dist.cpp
+// pt_adaptive.cpp adaptive sampling; pt_display.cpp the display transform; pt_rays.cpp
+// the batched ray queries; pt_dist.cpp
 // the RCCL step loop; pt_group.cpp the multi-device context.  The fields of
 // pt_context are grouped in that order.
 #pragma once
@@ -139,6 +140,7 @@ struct pt_context {
   int opt_moments = 0;        // PT_OPT_MOMENTS
   uint32_t opt_seed_base = 0; // PT_OPT_SEED_BASE
   int opt_adaptive_wf = 0;    // PT_OPT_ADAPTIVE_WF: adaptive rounds on the wavefront pipeline
+  int opt_rays_refill = 1;    // PT_OPT_RAYS_REFILL: pt_trace_rays' wide walk refills lanes from a ray counter
   bool stats_mode = false;    // pt_set_stats_mode
 
   // ---- pt_api.cpp: partition and item lists -------------------------------------
@@ -311,6 +313,15 @@ struct pt_context {
   } drb[2];
   int drb_next_ticket = 1;
 
+  // ---- pt_rays.cpp: batched ray queries (freed by rays_release) ---------------------------
+  uint32_t* d_rays_counters = nullptr; // the wide kernel's ray cursor and its count of marked rays
+  int* d_rays_slot = nullptr;          // rank -> triangle index of the scene's wide tree, built by the first
+  size_t rays_slot_cap = 0;            // query after an upload (rays_slot_serial == scene_serial: current)
+  int rays_slot_serial = -1;
+  void* d_rays_in = nullptr;           // pt_trace_rays_sync's staging buffers, grown on demand
+  void* d_rays_out = nullptr;
+  size_t rays_in_cap = 0, rays_out_cap = 0;   // rays / answers of 32 B they hold
+
   // ---- pt_dist.cpp, pt_group.cpp ------------------------------------------------------
   DistState* dist = nullptr;           // pt_dist_init
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
@@ -446,6 +457,7 @@ int unpack_table(pt_context* c, const ptd::RenderParams& p, const std::vector<fl
 void post_release(pt_context* c);      // frees what pt_post.cpp allocates (pt_destroy)
 void adaptive_release(pt_context* c);  // ... and pt_adaptive.cpp
 void display_release(pt_context* c);   // ... and pt_display.cpp
+void rays_release(pt_context* c);      // ... and pt_rays.cpp
 // ---- what pt_post.cpp gives pt_adaptive.cpp: the variance-guided filter's passes from a variance plane
 // (pt_post.cpp var_filter), and the validated filter parameters
 int post_var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,

@@ -271,6 +271,16 @@ hipError_t launch_wavefront_adaptive(const RenderParams& p, const WfBuffers& b, 
 // per pixel from p's camera, size and scene.  p.wide set: the culled wide
 // walk; else the exact walk, staged in LDS with lds_scene.
 hipError_t launch_guide(const RenderParams& p, float4* guide, bool lds_scene, hipStream_t stream);
+// Batched ray queries (pt_trace_rays, kernels/rays.h): n rays of 2 float4 {o.xyz, d.x} {d.yz, limit, -} into n
+// closest hits of 2 float4 {t, tri, u, v} {n.xyz, 0} (kRaysClosest) or n occlusion words (kRaysAny), from p's
+// scene alone.  p.wide set: the culled wide walk in the shape `refill` picks (PT_OPT_RAYS_REFILL), then the
+// exact walk over the rays it marked; else the exact walk, staged in LDS with lds_scene.  counters: two
+// library-owned words (the ray cursor, the marks), cleared here on the stream; slot_of: rank -> triangle index
+// of p's wide tree (launch_rays_slots), read with p.wide only.
+constexpr int kRaysClosest = 0, kRaysAny = 1;   // == PT_RAYS_CLOSEST, PT_RAYS_ANY
+hipError_t launch_rays(const RenderParams& p, int kind, const void* rays, size_t n, void* out, uint32_t* counters,
+                       const int* slot_of, bool lds_scene, bool refill, hipStream_t stream);
+hipError_t launch_rays_slots(const int* rank_of, int n, int* slot_of, hipStream_t stream);
 // One pass of the a-trous filter (pt_denoise.h atrous_pixel) from src to dst
 // (distinct images) at tap spacing `step` with the pass's squared sigmas;
 // staged: the tile and its halo go through LDS (steps 1 and 2 only).
@@ -629,6 +639,63 @@ constexpr bool adaptive_list_exact() {
   return ok && all_met(kAdaptiveVariants, met);
 }
 static_assert(adaptive_list_exact(), "the adaptive variant list and its pick disagree");
+
+// ... and of launch_rays' (batched ray queries, kernels/rays.h).  A scene whose wide walk is set up
+// (p.wide) is walked by rays_wide_kernel<KIND, QN, REFILL>, then once more by rays_exact_kernel<KIND, false>
+// over the rays that kernel marked; any other scene by rays_exact_kernel<KIND, LDS> alone.
+struct RaysExactVariant { int kind; bool lds; };          // rays_exact_kernel<KIND, LDS>
+struct RaysWideVariant { int kind; bool qn, refill; };    // rays_wide_kernel<KIND, QN, REFILL>
+constexpr bool operator==(const RaysExactVariant& a, const RaysExactVariant& b) {
+  return a.kind == b.kind && a.lds == b.lds;
+}
+constexpr bool operator==(const RaysWideVariant& a, const RaysWideVariant& b) {
+  return a.kind == b.kind && a.qn == b.qn && a.refill == b.refill;
+}
+#define PT_RAYS_EXACT_VARIANTS(X) X(0, false) X(0, true) X(1, false) X(1, true)
+#define PT_RAYS_WIDE_VARIANTS(X)                                                                    \
+  X(0, true, true) X(0, true, false) X(0, false, true) X(0, false, false) X(1, true, true)         \
+  X(1, true, false) X(1, false, true) X(1, false, false)
+constexpr long long kRaysMax = 0x7fffffffll - 255;   // rays a call takes: indices and the ray counter stay in 32 bits
+constexpr long long kRaysLdsGrid = 2048;             // workgroups of the LDS-staged exact kernel: each stages the scene once
+struct RaysLaunch {
+  Launch what = Launch::Refused;
+  bool wide = false;           // the wide kernel, then the exact one over its marks
+  RaysWideVariant wide_v = {};
+  long long grid_wide = 0;
+  RaysExactVariant exact_v = {};
+  long long grid_exact = 0;    // workgroups of the exact kernel (striding over the batch)
+  size_t lds = 0;              // its dynamic LDS bytes
+};
+// kind: kRaysClosest / kRaysAny.  refill: PT_OPT_RAYS_REFILL.  wide_blocks: workgroups of the wide kernel
+// resident on the device at once (the persistent grid before PT_OPT_WF_GRID and the overflow areas bound it).
+inline RaysLaunch plan_rays(const RenderParams& p, int kind, long long n, bool lds_scene, bool refill,
+                            long long wide_blocks) {
+  RaysLaunch l;
+  if ((kind != kRaysClosest && kind != kRaysAny) || n < 0 || n > kRaysMax) return l;
+  if (n == 0) {
+    l.what = Launch::Nothing;
+    return l;
+  }
+  const long long blocks = (n + 255) / 256;
+  l.wide = p.wide != nullptr;
+  if (l.wide) {
+    if (p.wide_ovf_lanes < 256 || wide_blocks < 1) return l;   // every lane needs its overflow stack area
+    long long g = wide_blocks;
+    if (p.wf_grid > 0 && p.wf_grid < 100) g = g * p.wf_grid / 100 > 1 ? g * p.wf_grid / 100 : 1;
+    if (g > p.wide_ovf_lanes / 256) g = p.wide_ovf_lanes / 256;
+    l.grid_wide = g < blocks ? g : blocks;
+    l.wide_v = {kind, p.wide_qn != 0, refill};
+    l.exact_v = {kind, false};
+    l.grid_exact = blocks;
+  } else {
+    l.lds = lds_scene ? scene_lds_bytes(p) : 0;
+    if (l.lds > kMaxSceneLds) return l;
+    l.exact_v = {kind, lds_scene};
+    l.grid_exact = lds_scene && blocks > kRaysLdsGrid ? kRaysLdsGrid : blocks;
+  }
+  l.what = Launch::Run;
+  return l;
+}
 #pragma GCC visibility pop
 
 }  // namespace ptd

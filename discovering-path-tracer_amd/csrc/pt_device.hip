@@ -54,6 +54,7 @@ namespace {
 #include "kernels/wf_adaptive.h"
 #include "kernels/guide.h"
 #include "kernels/adaptive.h"
+#include "kernels/rays.h"
 
 }  // namespace
 
@@ -394,6 +395,50 @@ hipError_t launch_wavefront_adaptive(const RenderParams& p0, const WfBuffers& b,
     }
     hipLaunchKernelGGL(kWfFoldAdaptive, dim3((unsigned)l.fold_grid), dim3(256), 0, stream, p, b, list, n_live);
   }
+  return hipGetLastError();
+}
+
+namespace {
+// ... and the ray queries' (last once more: kernels/rays.h)
+typedef void (*RaysExactKernel)(RenderParams, const float4*, void*, long long, int, const uint32_t*);
+typedef void (*RaysWideKernel)(RenderParams, const float4*, void*, uint32_t, uint32_t*, const int*);
+#define PT_ROW(K, L) {{K, L}, rays_exact_kernel<K, L>},
+const KernelEntry<RaysExactVariant, RaysExactKernel> kRaysExactKernels[] = {PT_RAYS_EXACT_VARIANTS(PT_ROW)};
+#undef PT_ROW
+#define PT_ROW(K, Q, R) {{K, Q, R}, rays_wide_kernel<K, Q, R>},
+const KernelEntry<RaysWideVariant, RaysWideKernel> kRaysWideKernels[] = {PT_RAYS_WIDE_VARIANTS(PT_ROW)};
+#undef PT_ROW
+}  // namespace
+
+hipError_t launch_rays_slots(const int* rank_of, int n, int* slot_of, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  rays_slot_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(rank_of, n, slot_of);
+  return hipGetLastError();
+}
+
+hipError_t launch_rays(const RenderParams& p, int kind, const void* rays, size_t n, void* out, uint32_t* counters,
+                       const int* slot_of, bool lds_scene, bool refill, hipStream_t stream) {
+  if (n > (size_t)kRaysMax) return hipErrorInvalidValue;
+  long long wide_blocks = 0;
+  RaysWideKernel wide = nullptr;
+  if (p.wide) {   // the wide kernel the plan will pick, for its residency
+    wide = find_kernel(kRaysWideKernels, RaysWideVariant{kind, p.wide_qn != 0, refill});
+    if (!wide || !counters || !slot_of) return hipErrorInvalidValue;
+    const hipError_t e = resident_blocks(wide, 0, 1, &wide_blocks);
+    if (e != hipSuccess) return e;
+  }
+  const RaysLaunch l = plan_rays(p, kind, (long long)n, lds_scene, refill, wide_blocks);
+  if (l.what == Launch::Nothing) return hipSuccess;
+  const RaysExactKernel exact = l.what == Launch::Run ? find_kernel(kRaysExactKernels, l.exact_v) : nullptr;
+  if (!exact) return hipErrorInvalidValue;
+  if (l.wide) {
+    const hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wide, dim3((unsigned)l.grid_wide), dim3(256), 0, stream, p, (const float4*)rays, out,
+                       (uint32_t)n, counters, slot_of);
+  }
+  hipLaunchKernelGGL(exact, dim3((unsigned)l.grid_exact), dim3(256), l.lds, stream, p, (const float4*)rays, out,
+                     (long long)n, l.wide ? 1 : 0, (const uint32_t*)counters);
   return hipGetLastError();
 }
 

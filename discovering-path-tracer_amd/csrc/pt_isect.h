@@ -41,6 +41,21 @@ PT_FN bool tri_test(v3 o, v3 d, float4 A, float4 B, float4 C, float* tout) {
   return true;
 }
 
+// intersectTriangle's barycentrics (:137, :143) of a record tri_test accepted:
+// u = inv * dot(s, p), v = inv * dot(d, q), the values its range tests read.
+// For the one winning record of a ray query (pt_trace_rays); tri_test itself
+// keeps its instruction stream.
+PT_FN void tri_uv(v3 o, v3 d, float4 A, float4 B, float4 C, float* uout, float* vout) {
+  const v3 v0 = mk(A.x, A.y, A.z);
+  const v3 e1 = mk(A.w, B.x, B.y);
+  const v3 e2 = mk(B.z, B.w, C.x);
+  const v3 p = cross(d, e2);
+  const float inv = rcp_(dot(e1, p));
+  const v3 s = sub(o, v0);
+  *uout = inv * dot(s, p);
+  *vout = inv * dot(d, cross(s, e1));
+}
+
 // sampleHemisphere (:229-243) from its two draws, r1 first.
 __host__ __device__ static __forceinline__ v3 hemisphere_dir(v3 n, float r1, float r2) {
   const float th = acos_(sqrt_(1.0f - r1));

@@ -8,8 +8,11 @@
 //             [-cache scene.ptscene] [-progressive N [-chunk K] [-orbit-at B]]
 //             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
 //             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]
-//             [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY]
+//             [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY] [-pick X Y]
 //
+// -pick X Y prints, before anything is rendered, the closest hit of the guide ray of pixel (X, Y)
+// (pt_guide_ray, pt_trace_rays_sync): t, the triangle's index, u, v, the normal and the position o + d * t,
+// floats with nine significant digits (which name their bits), or "miss".  A single-device context.
 // -progressive runs the reference's interactive loop (mainLoop, :717-865)
 // headless: up to N batches (cap 1024, :719) in launches of K, a readback of
 // every launch overlapped with the next one (double-buffered), and, with
@@ -72,7 +75,7 @@ int main(int argc, char** argv) {
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
             "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
             "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]\n"
-            "       [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY]\n",
+            "       [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY] [-pick X Y]\n",
             argv[0]);
     return 2;
   }
@@ -89,6 +92,8 @@ int main(int argc, char** argv) {
   bool display = false;
   pt_display_params dp;
   pt_display_default_params(&dp);
+  bool pick = false;
+  int pick_x = 0, pick_y = 0;
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -135,6 +140,11 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "-exposure")) {
       display = true;
       dp.exposure = (float)atof(next());
+    }
+    else if (!strcmp(argv[i], "-pick")) {
+      pick = true;
+      pick_x = atoi(next());
+      pick_y = atoi(next());
     }
     else if (!strcmp(argv[i], "-auto-exposure")) {
       display = true;
@@ -189,6 +199,20 @@ int main(int argc, char** argv) {
   check(pt_set_params(ctx, &params), "params");
   check(pt_resize_and_clear(ctx, W, H), "resize");
   check(pt_synchronize(ctx), "sync");
+  if (pick) {
+    pt_ray ray = {};
+    pt_hit hit = {};
+    check(pt_guide_ray(ubo, W, H, pick_x, pick_y, ray.o, ray.d), "guide ray");
+    check(pt_trace_rays_sync(ctx, PT_RAYS_CLOSEST, &ray, 1, &hit), "trace rays");
+    if (hit.tri < 0) {
+      printf("pick (%d, %d): miss\n", pick_x, pick_y);
+    } else {
+      float pos[3];
+      for (int k = 0; k < 3; ++k) pos[k] = ray.o[k] + ray.d[k] * hit.t;
+      printf("pick (%d, %d): t %.9g tri %d u %.9g v %.9g n %.9g %.9g %.9g p %.9g %.9g %.9g\n", pick_x, pick_y,
+             hit.t, hit.tri, hit.u, hit.v, hit.n[0], hit.n[1], hit.n[2], pos[0], pos[1], pos[2]);
+    }
+  }
   if (progressive > 0) {
     // orbit: the default camera rotated 30 degrees about +y around the origin
     float orbit[16];

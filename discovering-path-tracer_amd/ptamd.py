@@ -48,6 +48,11 @@ PT_OPT_EXIT_SKIP = 28
 PT_OPT_SEED_BASE = 29
 PT_OPT_SWEEP_CUBE = 30
 PT_OPT_ADAPTIVE_WF = 31
+PT_OPT_RAYS_REFILL = 32
+RAYS_CLOSEST, RAYS_ANY = 0, 1
+# pt_ray and pt_hit as numpy sees them (32 B each)
+RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("limit", "<f4"), ("reserved", "<u4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("tri", "<i4"), ("u", "<f4"), ("v", "<f4"), ("n", "<f4", 3), ("reserved", "<u4")])
 KERNEL_AUTO, KERNEL_RECURSIVE, KERNEL_WAVEFRONT = 0, 1, 3   # 2 (lane state machine) was removed
 
 # Every symbol include/pathtracer.h declares (tests check the .so exports them).
@@ -78,6 +83,7 @@ EXPORTS = [
     "pt_adaptive_device_ptr", "pt_adaptive_denoise",
     "pt_display_default_params", "pt_display", "pt_display_device_ptr", "pt_read_display", "pt_display_exposure",
     "pt_display_reset", "pt_display_readback_begin", "pt_display_readback_end", "pt_display_host", "pt_write_png8",
+    "pt_trace_rays", "pt_trace_rays_sync", "pt_trace_rays_host",
 ]
 
 
@@ -255,6 +261,8 @@ def lib():
             "pt_display_readback_end": ([vp, i32, vp, sz], i32),
             "pt_display_host": ([vp, i32, i32, ctypes.POINTER(DisplayParams), ctypes.POINTER(ctypes.c_float), vp], i32),
             "pt_write_png8": ([ctypes.c_char_p, vp, i32, i32], i32),
+            "pt_trace_rays": ([vp, i32, vp, sz, vp], i32), "pt_trace_rays_sync": ([vp, i32, vp, sz, vp], i32),
+            "pt_trace_rays_host": ([vp, sz, vp, sz, vp, sz, u32, i32, vp, sz, vp, i32], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -715,6 +723,35 @@ def adaptive_select_host(moments, counts, width, height, params=None):
     return nxt, err
 
 
+def _rays_in(rays):
+    """n rays as a contiguous (n, 8) float32 array {o, d, limit, -}: from that layout or from RAY_DTYPE records."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 8)
+    return a
+
+
+def _rays_out(kind, n):
+    if kind not in (RAYS_CLOSEST, RAYS_ANY):
+        raise PTError(f"kind is RAYS_CLOSEST or RAYS_ANY, not {kind!r}")
+    return np.zeros(n, HIT_DTYPE if kind == RAYS_CLOSEST else np.uint32)
+
+
+def trace_rays_host(vertices, indices, nodes, rays, kind=RAYS_CLOSEST, int_bits=False, threads=0):
+    """pt_trace_rays_host: the host statement of Renderer.trace_rays on the arrays of upload_scene.
+    Returns HIT_DTYPE records (RAYS_CLOSEST) or uint32 0 / 1 (RAYS_ANY)."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1)
+    i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    n = np.ascontiguousarray(nodes, np.float32).reshape(-1)
+    r = _rays_in(rays)
+    out = _rays_out(kind, r.shape[0])
+    _check(lib().pt_trace_rays_host(_ptr(v), v.size, _ptr(i), i.size, _ptr(n), n.size // 8,
+                                    PT_NODES_INT_BITS if int_bits else 0, kind, _ptr(r), r.shape[0], _ptr(out), threads),
+           "pt_trace_rays_host")
+    return out
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -1071,6 +1108,30 @@ class Renderer:
         out = np.empty(self.width * self.height * 4, np.uint8)
         _check(lib().pt_display_readback_end(self._c, ticket, out.ctypes.data, out.size), "pt_display_readback_end")
         return out.reshape(self.height, self.width, 4)
+
+    def trace_rays(self, rays, kind=RAYS_CLOSEST):
+        """The caller's own rays against the uploaded scene (needs nothing else): closest hits or occlusion.
+        A numpy array ((n, 8) float32 {o, d, limit, -} or RAY_DTYPE records) goes through pt_trace_rays_sync
+        and returns HIT_DTYPE records (RAYS_CLOSEST) or uint32 0 / 1 (RAYS_ANY).  A torch tensor on the device
+        ((n, 8) float32, contiguous) goes through pt_trace_rays, enqueued on the context's stream (set_stream)
+        and not waited for, and returns a tensor on the same device: (n, 8) float32 holding pt_hit records
+        (view it as int32 for `tri`) or (n,) int32."""
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
+                raise PTError("trace_rays: a contiguous float32 device tensor of n x 8 floats")
+            n = rays.numel() // 8
+            if kind not in (RAYS_CLOSEST, RAYS_ANY):
+                raise PTError(f"kind is RAYS_CLOSEST or RAYS_ANY, not {kind!r}")
+            out = (torch.empty((n, 8), dtype=torch.float32, device=rays.device) if kind == RAYS_CLOSEST
+                   else torch.empty((n,), dtype=torch.int32, device=rays.device))
+            _check(lib().pt_trace_rays(self._c, kind, rays.data_ptr() if n else None, n, out.data_ptr() if n else None),
+                   "pt_trace_rays")
+            return out
+        r = _rays_in(rays)
+        out = _rays_out(kind, r.shape[0])
+        _check(lib().pt_trace_rays_sync(self._c, kind, _ptr(r), r.shape[0], _ptr(out)), "pt_trace_rays_sync")
+        return out
 
     def set_stats_mode(self, on):
         _check(lib().pt_set_stats_mode(self._c, 1 if on else 0), "pt_set_stats_mode")
