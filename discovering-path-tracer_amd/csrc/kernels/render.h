@@ -64,16 +64,63 @@ __device__ __forceinline__ void emit_lane(const RenderParams& P, bool active, si
     store_lane(P.accum + pix, acc, spl, j);
 }
 
-// Whether a pixel lies in one of the tight rectangles (pt_cull.h); true
-// without them.  Static indices: P stays in SGPRs/kernarg.
-__device__ __forceinline__ bool pixel_tight(const RenderParams& P, float ndcX0, float ndcY0) {
-  if (P.n_cull_tight < 0) return true;
+// Whether a point lies in one region of the footprint table (pt_cull.h): a rectangle cut by half-planes.
+__device__ __forceinline__ bool region_holds(const float* __restrict__ f, float x, float y) {
+  bool in = x >= f[0] && x <= f[1] && y >= f[2] && y <= f[3];
+#pragma unroll
+  for (int k = 0; k < kFootprintPlanes; ++k) in = in && f[4 + 3 * k] * x + f[5 + 3 * k] * y <= f[6 + 3 * k];
+  return in;
+}
+
+// What a pixel's samples with both radius draws at least P.cull_u0 are: kSkipNever, they are traced like
+// any other (the pixel can reach something, or there are no tight rectangles); kSkipBlack, (0,0,0): the
+// pixel lies outside every tight rectangle, or with footprints (PT_OPT_CULL_FOOTPRINT, P.n_foot > 0: a
+// table in device memory walked with a run-time loop) outside every footprint; l >= 0, the intensity of
+// light l: the pixel lies in that light's sure region and in no footprint but the light's own.  Without
+// footprints the rectangles are tested with static indices: P stays in SGPRs/kernarg.
+constexpr int kSkipNever = -2, kSkipBlack = -1;
+__device__ __forceinline__ int pixel_skip(const RenderParams& P, float ndcX0, float ndcY0) {
+  if (P.n_cull_tight < 0) return kSkipNever;
+  if (P.n_foot > 0) {   // uniform
+    int inside = 0, last = 0;
+    for (int r = 0; r < P.n_foot; ++r) {   // at most kMaxCullRects (the host's table holds as many)
+      const bool in = region_holds(P.foot + kFootprintFloats * r, ndcX0, ndcY0);
+      inside += in ? 1 : 0;
+      last = in ? r : last;
+    }
+    if (inside == 0) return kSkipBlack;
+    // object r > 0 is light r - 1; its sure region follows the kMaxCullRects footprints
+    if (inside == 1 && last >= 1 && last <= P.n_sure &&
+        region_holds(P.foot + kFootprintFloats * (kMaxCullRects + last - 1), ndcX0, ndcY0))
+      return last - 1;
+    return kSkipNever;
+  }
   bool tight = false;
 #pragma unroll
   for (int r = 0; r < kMaxCullRects; ++r)
     tight = tight || (r < P.n_cull_tight && ndcX0 >= P.cull_tight[r][0] && ndcX0 <= P.cull_tight[r][1] &&
                       ndcY0 >= P.cull_tight[r][2] && ndcY0 <= P.cull_tight[r][3]);
-  return tight;
+  return tight ? kSkipNever : kSkipBlack;
+}
+// ... for the kernels that know only the black skip: a pixel of a sure region counts as tight and is traced.
+__device__ __forceinline__ bool pixel_tight(const RenderParams& P, float ndcX0, float ndcY0) {
+  return pixel_skip(P, ndcX0, ndcY0) != kSkipBlack;
+}
+// The light of a pixel that pixel_skip found sure: such a pixel lies in no other light's footprint, hence in
+// no other light's sure region.  From operands the compiler cannot match with the prologue's: it would
+// otherwise keep the index in a VGPR across the sample loop.
+__device__ __forceinline__ int skip_again(const RenderParams& P, float ndcX0, float ndcY0) {
+  asm volatile("" : "+v"(ndcX0), "+v"(ndcY0));
+  int l = 0;
+  for (int k = 1; k < P.n_sure; ++k)
+    l = region_holds(P.foot + kFootprintFloats * (kMaxCullRects + k), ndcX0, ndcY0) ? k : l;
+  return l;
+}
+// The colour of a skipped sample.
+__device__ __forceinline__ float4 skip_colour(const RenderParams& P, int skip) {
+  if (skip < 0) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+  const LightDev* L = P.lights + skip;
+  return make_float4(L->inten[0], L->inten[1], L->inten[2], 1.0f);
 }
 
 // Items (tile parts) whose every pixel is culled, listed by the host with
@@ -277,7 +324,12 @@ __global__ __launch_bounds__(256, SWEEP || (LDS && !STATS) ? 6 : PT_RENDER_MIN_B
   // them traces a sample only if one of the sample's two radius draws is below
   // P.cull_u0 (its radius may then exceed the bound); every other sample of it
   // is (0,0,0), the value the trace would produce.  Stats mode never skips.
-  const bool tight = STATS || pixel_tight(P, ndcX0, ndcY0);
+  // With footprints a pixel of a light's sure region skips them with the light's intensity (pixel_skip).
+  // Two lane masks are kept across the sample loop, not the light's index: a third live VGPR costs this
+  // kernel two more spilled ones, so a sure pixel's skipped sample finds its light again (skip_again).
+  const int skip0 = STATS ? kSkipNever : pixel_skip(P, ndcX0, ndcY0);
+  const bool tight = skip0 == kSkipNever;
+  const bool sure = skip0 >= 0;
   const size_t pix = (size_t)py * (size_t)W + (size_t)px;
   uint32_t nsamp = 0;
   if (active && (uint32_t)j < P.n_batches)
@@ -383,6 +435,8 @@ __global__ __launch_bounds__(256, SWEEP || (LDS && !STATS) ? 6 : PT_RENDER_MIN_B
       else
         col = path_trace_fused<CNT, EXIT>(P, origin, dir, seed, cand, c);
       col4 = make_float4(col.x, col.y, col.z, 1.0f);                      // vec4(color, 1.0)
+      } else if (sure) {
+        col4 = skip_colour(P, skip_again(P, ndcX0, ndcY0));
       }
      }
      if (spl == 1) {   // uniform: each lane folds its own sample, no hand-off (:467-469)

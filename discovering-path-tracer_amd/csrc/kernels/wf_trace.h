@@ -31,13 +31,18 @@ __global__ __launch_bounds__(256, 4) void wf_gen_kernel(RenderParams P, WfBuffer
       // rectangles a sample whose two radius draws are at least P.cull_u0
       // reaches nothing and is (0,0,0)
       bool reach = pixel_live(P, F.ndcX0, F.ndcY0);
-      if (reach && !pixel_tight(P, F.ndcX0, F.ndcY0)) {
+      const int skip = reach ? pixel_skip(P, F.ndcX0, F.ndcY0) : kSkipBlack;   // l >= 0: a sure region, the light's intensity
+      if (reach && skip != kSkipNever) {
         const uint32_t batch = (P.first_batch + P.seed_base) + S.s;   // the seed's batch (PT_OPT_SEED_BASE)
         uint32_t rng = (batch * (uint32_t)F.H + (uint32_t)F.py) * (uint32_t)F.W + (uint32_t)F.px;
         const float u1a = fmax_(1e-38f, rng_next(&rng));
         rng_next(&rng);
         const float u1j = fmax_(1e-38f, rng_next(&rng));
         reach = u1a < P.cull_u0 || u1j < P.cull_u0;
+        if (!reach) {
+          const float4 c4 = skip_colour(P, skip);
+          col = mk(c4.x, c4.y, c4.z);
+        }
       }
       if (reach) {
         gen = true;

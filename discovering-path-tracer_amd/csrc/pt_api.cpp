@@ -694,6 +694,54 @@ static void cull_rectangles(const pt_context* c, ptd::RenderParams* p) {
                                       c->n_lights, &p->cull_tight[0][0], ptd::kMaxCullRects, ptd::kCullTightR);
     if (p->n_cull_tight != p->n_cull) p->n_cull_tight = -1;
   }
+  p->n_foot = 0;
+  p->n_sure = 0;
+  p->foot = nullptr;
+}
+
+// The footprint table of the frame (PT_OPT_CULL_FOOTPRINT) into table[2][kMaxCullRects][kFootprintFloats]: the
+// footprints, one per tight rectangle, then the lights' sure regions.  Returns how many footprints are in
+// force, or 0: the rectangles decide; *n_sure: the lights that have a region in the table (0: none has a
+// non-empty one), *sure_regions: the non-empty ones.  The counting pass keeps the rectangles unless the
+// option is 1.
+constexpr size_t kFootTable = 2 * (size_t)ptd::kMaxCullRects * ptd::kFootprintFloats;
+static_assert(ptd::kMaxCullObjects == ptd::kMaxCullRects, "pt_cull.h's bound is pt_device.h's");
+static int cull_footprint_table(const pt_context* c, const ptd::RenderParams& p, float* table, int* n_sure,
+                                int* sure_regions) {
+  *n_sure = *sure_regions = 0;
+  const bool counting = c->opt_count != 0 && !c->stats_mode;
+  if (p.n_cull_tight < 1 || c->opt_cull_foot == 0 || (c->opt_cull_foot < 0 && counting)) return 0;
+  const int n = ptd::cull_footprints(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(),
+                                     c->n_lights, table, ptd::kMaxCullRects, ptd::kCullTightR);
+  if (n != p.n_cull_tight) return 0;
+  const int ns = ptd::cull_sure(c->cam, c->width, c->height, c->root_lo, c->root_hi, c->lights_host.data(), c->n_lights,
+                                table + ptd::kMaxCullRects * ptd::kFootprintFloats, ptd::kMaxCullRects, ptd::kCullTightR);
+  if (ns > 0) {
+    *n_sure = c->n_lights;
+    *sure_regions = ns;
+  }
+  return n;
+}
+
+// ... and into the context's table in device memory, which the kernels read (RenderParams::foot): uploaded
+// when it differs from what the table holds, after the launches that may still read it.
+static int cull_footprints(pt_context* c, ptd::RenderParams* p) {
+  static_assert(sizeof(c->foot_up) == kFootTable * sizeof(float), "pt_context::foot_up");
+  float table[kFootTable] = {};
+  int n_sure = 0, regions = 0;
+  const int n = cull_footprint_table(c, *p, table, &n_sure, &regions);
+  if (n == 0) return PT_OK;
+  if (!c->d_foot || memcmp(table, c->foot_up, sizeof(table)) != 0) {
+    { const int rc_ = quiesce(c); if (rc_) return rc_; }
+    PT_HIP(hipSetDevice(c->device));
+    if (!c->d_foot) PT_HIP(hipMalloc((void**)&c->d_foot, sizeof(table)));
+    PT_HIP(hipMemcpy(c->d_foot, table, sizeof(table), hipMemcpyHostToDevice));
+    memcpy(c->foot_up, table, sizeof(table));
+  }
+  p->n_foot = n;
+  p->n_sure = n_sure;
+  p->foot = c->d_foot;
+  return PT_OK;
 }
 
 // The cull rectangles and the item lists of the frame; mixed lanes where the plan admits them and the
@@ -702,6 +750,7 @@ static int cull_and_items(pt_context* c, const LaunchPlan& plan, uint32_t n_batc
   c->last_mix = 0;
   cull_rectangles(c, p);
   if (p->n_cull < 0) return PT_OK;
+  { const int rc = cull_footprints(c, p); if (rc) return rc; }
   MixPlan mix;
   const bool mixed = plan.mixed_eligible;
   if (mixed) {
@@ -940,7 +989,7 @@ int adaptive_render_params(pt_context* c, const AdaptivePlan& ap, int spl, ptd::
   { const int rc = render_params(c, plan, 0, 0, false, p); if (rc) return rc; }
   p->moments = c->d_moments;
   cull_rectangles(c, p);
-  return PT_OK;
+  return cull_footprints(c, p);
 }
 
 int adaptive_launch_wavefront(pt_context* c, const AdaptivePlan& ap, uint32_t reserve_batches, ptd::RenderParams* p) {
@@ -1085,6 +1134,7 @@ int pt_destroy(pt_context* c) {
   if (c->own_accum) dev_free(c->d_accum);
   dev_free(c->d_stats);
   dev_free(c->d_items);
+  dev_free(c->d_foot);
   dev_free(c->d_cost);
   if (c->h_cost) (void)hipHostFree(c->h_cost);
   if (c->cost_ev) (void)hipEventDestroy(c->cost_ev);
@@ -1590,6 +1640,7 @@ static const IntOption kIntOptions[] = {
     {PT_OPT_SWEEP_CUBE, &pt_context::opt_sweep_cube, 0, 1, "PT_OPT_SWEEP_CUBE takes 0 or 1"},
     {PT_OPT_ADAPTIVE_WF, &pt_context::opt_adaptive_wf, 0, 1, "PT_OPT_ADAPTIVE_WF takes 0 or 1"},
     {PT_OPT_RAYS_REFILL, &pt_context::opt_rays_refill, 0, 1, "PT_OPT_RAYS_REFILL takes 0 or 1"},
+    {PT_OPT_CULL_FOOTPRINT, &pt_context::opt_cull_foot, -1, 1, "PT_OPT_CULL_FOOTPRINT takes -1 (auto), 0 or 1"},
 };
 
 int pt_set_option(pt_context* c, int key, int value) {
@@ -1773,6 +1824,18 @@ int pt_sweep_info(pt_context* c, int* boxes, int* leaves) {
   const bool on = sweep_in_force(c);
   *boxes = on ? c->sweep_boxes : 0;
   *leaves = on ? c->sweep_leaves : 0;
+  return PT_OK;
+}
+
+int pt_cull_info(pt_context* c, int info[3]) {
+  if (c && c->group) return ptg::cull_info(c->group, info);
+  if (!c || !info) return fail(PT_ERR_INVALID, "null argument");
+  ptd::RenderParams p{};
+  cull_rectangles(c, &p);
+  float table[kFootTable];
+  int n_sure = 0;
+  info[0] = p.n_cull_tight > 0 ? p.n_cull_tight : 0;
+  info[1] = cull_footprint_table(c, p, table, &n_sure, &info[2]);
   return PT_OK;
 }
 

@@ -120,6 +120,7 @@ struct pt_context {
   int opt_mixed = -1;         // PT_OPT_MIXED_LANES: -1 auto, 0 off, k = whole tiles for k % of the resident slots
   int opt_cull = 1;           // PT_OPT_PRIMARY_CULL
   int opt_cull_tight = 1;     // PT_OPT_CULL_TIGHT
+  int opt_cull_foot = -1;     // PT_OPT_CULL_FOOTPRINT: -1 on unless counting, 0 off, 1 on
   int opt_count = 0;          // PT_OPT_COUNT_TRACED
   int opt_small_sweep = -1;   // PT_OPT_SMALL_SWEEP: -1 auto (kSweepAutoBoxes), 0 off, 1 whenever the scene has a table
   int opt_sweep_hull = 1;     // PT_OPT_SWEEP_HULL
@@ -164,6 +165,11 @@ struct pt_context {
   std::vector<int> h_items;
   std::vector<float> items_key;
   std::vector<float> items_scratch;   // the per-launch key, built without reallocating
+  // the footprint table the kernels read (PT_OPT_CULL_FOOTPRINT, RenderParams::foot) and the host's copy of
+  // what it holds: kMaxCullRects footprints, then as many sure regions, of 16 floats each (pt_cull.h
+  // kFootprintFloats, which this header does not include; pt_api.cpp asserts the size)
+  float* d_foot = nullptr;
+  float foot_up[2 * ptd::kMaxCullRects * 16] = {};
 
   // ---- pt_api.cpp: the mixed-lane scheduler (mix_feedback) ------------------------
   unsigned* d_cost = nullptr;                  // per 16x4 part: summed wave durations of a measuring launch

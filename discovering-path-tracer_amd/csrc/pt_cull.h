@@ -41,4 +41,33 @@ __attribute__((visibility("hidden"))) int cull_rects(const float cam[16], int W,
                                                      const float* hi, const pt_area_light* lights, int n_lights,
                                                      float* rects, int max_rects, double Rg = kGaussR);
 
+// A footprint (PT_OPT_CULL_FOOTPRINT): a convex region of pixel origins in
+// NDC, {x0, x1, y0, y1} cut by kFootprintPlanes half-planes {a, b, c}, a pixel
+// being inside when a * x + b * y <= c for each (an unused one is {0, 0, 1}).
+// One per object, in the order of cull_rects and with its guarantee -- outside
+// every footprint no primary ray with radii of at most Rg reaches the root box
+// or a light -- but the hull of the corners' own boxes, each dilated by its
+// own depth against the focal depths of the rays that can reach the object,
+// instead of one rectangle dilated by the worst pair.  Each footprint lies in
+// the object's rectangle for the same Rg.  Returns the count or -1.
+constexpr int kMaxCullObjects = 8;   // the root box and 7 lights (pt_device.h kMaxCullRects)
+constexpr int kFootprintPlanes = 4;
+constexpr int kFootprintFloats = 4 + 3 * kFootprintPlanes;
+__attribute__((visibility("hidden"))) int cull_footprints(const float cam[16], int W, int H, const float* lo,
+                                                          const float* hi, const pt_area_light* lights, int n_lights,
+                                                          float* foot, int max_foot, double Rg);
+
+// The sure regions (PT_OPT_CULL_FOOTPRINT), one per light in a footprint's
+// layout (an empty one where none is derived: a non-finite intensity, a size
+// that is not positive, a light seen within 3 degrees of edge-on, a corner
+// behind the camera): every
+// primary ray with radii of at most Rg from a pixel inside passes
+// intersectAreaLight's float tests for that light.  Where the pixel also lies
+// outside the footprint at Rg of the root box and of every other light, the
+// pre-pass hits exactly this light, the closest walk finds nothing, and the
+// sample is (intensity, 1).  Returns the count of non-empty regions or -1.
+__attribute__((visibility("hidden"))) int cull_sure(const float cam[16], int W, int H, const float* lo, const float* hi,
+                                                    const pt_area_light* lights, int n_lights, float* sure,
+                                                    int max_sure, double Rg);
+
 }  // namespace ptd

@@ -192,6 +192,20 @@ struct RenderParams {
   uint32_t cube_under[6] = {};
   uint32_t cube_all = 0;
   int sweep_cube = 0;
+  // the footprint table (pt_cull.h, PT_OPT_CULL_FOOTPRINT), read by pixel_skip only; after every older member.
+  // foot: device memory, kMaxCullRects footprints and then kMaxCullRects sure regions of kFootprintFloats
+  // floats each (a rectangle and kFootprintPlanes half-planes).
+  // n_foot > 0: a pixel outside every one of footprints 0 .. n_foot - 1 skips its samples with both radius
+  // draws at least cull_u0 as black, in place of a pixel outside every tight rectangle; 0: the rectangles decide.
+  // n_sure > 0: lights 0 .. n_sure - 1 have a sure region (maybe an empty one); a pixel in light l's region and
+  // in no footprint but that light's own (footprint l + 1) skips those samples as (intensity, 1), in
+  // render_kernel and the wavefront generation kernel.
+  // A table like `sweep`, not words of the argument: the LDS kernels keep the whole argument in scalar
+  // registers, and 97 more words cost them 90 spilled SGPRs and, with the option off, 2 % of their time
+  // (profiles/footprint/resource_usage.md).
+  int n_foot = 0;
+  int n_sure = 0;
+  const float* foot = nullptr;
 };
 constexpr int kMixShift = 24;
 constexpr int kMaxCullRects = 8;

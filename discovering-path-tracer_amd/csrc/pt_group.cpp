@@ -693,6 +693,7 @@ int get_traced(pt_group* g, pt_traced* out) {
 int wide_info(pt_group* g, int info[2]) { return pt_wide_info(g->m[0], info); }
 int sweep_info(pt_group* g, int* boxes, int* leaves) { return pt_sweep_info(g->m[0], boxes, leaves); }
 int sweep_walk(pt_group* g, int* walk) { return pt_sweep_walk(g->m[0], walk); }
+int cull_info(pt_group* g, int info[3]) { return pt_cull_info(g->m[0], info); }
 int last_launch_ms(pt_group* g, float* ms) { return pt_last_launch_ms(g->m[0], ms); }
 int launch_times_ms(pt_group* g, float* out, size_t max_n, size_t* n_out) {
   return pt_launch_times_ms(g->m[0], out, max_n, n_out);

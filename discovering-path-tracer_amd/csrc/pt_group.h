@@ -53,6 +53,7 @@ int get_traced(pt_group* g, pt_traced* out);
 int wide_info(pt_group* g, int info[2]);
 int sweep_info(pt_group* g, int* boxes, int* leaves);
 int sweep_walk(pt_group* g, int* walk);
+int cull_info(pt_group* g, int info[3]);
 int last_launch_ms(pt_group* g, float* ms);
 int launch_times_ms(pt_group* g, float* out, size_t max_n, size_t* n_out);
 int launch_span_ms(pt_group* g, float* ms, size_t* n_out);

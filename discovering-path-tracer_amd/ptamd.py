@@ -49,6 +49,7 @@ PT_OPT_SEED_BASE = 29
 PT_OPT_SWEEP_CUBE = 30
 PT_OPT_ADAPTIVE_WF = 31
 PT_OPT_RAYS_REFILL = 32
+PT_OPT_CULL_FOOTPRINT = 33
 RAYS_CLOSEST, RAYS_ANY = 0, 1
 # pt_ray and pt_hit as numpy sees them (32 B each)
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("limit", "<f4"), ("reserved", "<u4")])
@@ -71,6 +72,7 @@ EXPORTS = [
     "pt_dist_unique_id", "pt_dist_init", "pt_dist_run", "pt_dist_slot_floats", "pt_dist_finalize",
     "pt_dist_set_streams", "pt_dist_wait", "pt_dist_abort", "pt_create_multi", "pt_group_info",
     "pt_group_check", "pt_dist_info", "pt_mixed_info", "pt_sweep_info", "pt_sweep_walk",
+    "pt_primary_cull_footprints", "pt_primary_cull_sure", "pt_cull_info",
     "pt_denoise_default_params", "pt_guide_ray", "pt_render_guide", "pt_guide_device_ptr", "pt_read_guide",
     "pt_denoise", "pt_read_denoised", "pt_denoise_host",
     "pt_moments_device_ptr", "pt_read_moments", "pt_denoise_var_default_params", "pt_denoise_var",
@@ -183,6 +185,10 @@ def lib():
             "pt_mixed_info": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
             "pt_sweep_info": ([vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], i32),
             "pt_sweep_walk": ([vp, ctypes.POINTER(ctypes.c_int)], i32),
+            "pt_cull_info": ([vp, vp], i32),
+            "pt_primary_cull_footprints": ([vp, i32, i32, vp, vp, vp, i32, ctypes.c_double, vp, i32,
+                                            ctypes.POINTER(i32)], i32),
+            "pt_primary_cull_sure": ([vp, i32, i32, vp, vp, vp, i32, ctypes.c_double, vp, i32, ctypes.POINTER(i32)], i32),
             "pt_partition_items": ([i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, psz, vp, psz, vp], i32),
             "pt_dist_unique_id": ([vp, sz], i32), "pt_dist_init": ([vp, vp, i32, i32], i32),
             "pt_dist_run": ([vp, u32, i32, i32, vp, i32], i32), "pt_dist_slot_floats": ([vp, psz], i32),
@@ -465,6 +471,43 @@ def primary_cull_rects_r(camera_ubo, width, height, root_min, root_max, lights16
                                          out.ctypes.data, max_rects, ctypes.byref(n), ctypes.byref(u0)),
            "pt_primary_cull_rects_r")
     return (None if n.value < 0 else out[:n.value].copy()), float(u0.value)
+
+
+def primary_cull_footprints(camera_ubo, width, height, root_min, root_max, lights16, radius_bound=-1.0, max_footprints=8):
+    """pt_primary_cull_footprints: (n, 16) floats or None -- per object
+    {x0, x1, y0, y1} and four half-planes {a, b, c} (inside: a*x + b*y <= c),
+    outside all of which no primary ray whose two Box-Muller radii are at most
+    radius_bound (negative: the kernel's tight bound) reaches the root box or
+    a light (PT_OPT_CULL_FOOTPRINT)."""
+    cam = np.ascontiguousarray(camera_ubo, np.float32).reshape(16)
+    lo = np.ascontiguousarray(root_min, np.float32).reshape(3)
+    hi = np.ascontiguousarray(root_max, np.float32).reshape(3)
+    l = np.ascontiguousarray(lights16, np.float32).reshape(-1)
+    out = np.zeros((max_footprints, 16), np.float32)
+    n = ctypes.c_int(0)
+    _check(lib().pt_primary_cull_footprints(cam.ctypes.data, width, height, lo.ctypes.data, hi.ctypes.data,
+                                            l.ctypes.data if l.size else None, l.size // 16, float(radius_bound),
+                                            out.ctypes.data, max_footprints, ctypes.byref(n)),
+           "pt_primary_cull_footprints")
+    return None if n.value < 0 else out[:n.value].copy()
+
+
+def primary_cull_sure(camera_ubo, width, height, root_min, root_max, lights16, radius_bound=-1.0):
+    """pt_primary_cull_sure: (one region of 16 floats per light, in a
+    footprint's layout, empty (x0 > x1) where none is derived; the count of
+    non-empty ones), or (None, -1) without footprints.  Every primary ray with
+    radii of at most radius_bound from a pixel inside hits that light."""
+    cam = np.ascontiguousarray(camera_ubo, np.float32).reshape(16)
+    lo = np.ascontiguousarray(root_min, np.float32).reshape(3)
+    hi = np.ascontiguousarray(root_max, np.float32).reshape(3)
+    l = np.ascontiguousarray(lights16, np.float32).reshape(-1)
+    nl = l.size // 16
+    out = np.zeros((max(nl, 1), 16), np.float32)
+    n = ctypes.c_int(0)
+    _check(lib().pt_primary_cull_sure(cam.ctypes.data, width, height, lo.ctypes.data, hi.ctypes.data,
+                                      l.ctypes.data if l.size else None, nl, float(radius_bound), out.ctypes.data,
+                                      max(nl, 1), ctypes.byref(n)), "pt_primary_cull_sure")
+    return (None, -1) if n.value < 0 else (out[:nl].copy(), n.value)
 
 
 def write_image(path, rgba, width, height, fmt="png"):
@@ -1204,6 +1247,14 @@ class Renderer:
         b, n = ctypes.c_int(0), ctypes.c_int(0)
         _check(lib().pt_sweep_info(self._c, ctypes.byref(b), ctypes.byref(n)), "pt_sweep_info")
         return b.value, n.value
+
+    def cull_info(self):
+        """(tight rectangles, footprints among them, non-empty sure regions) the
+        per-sample skip of the next launch decides by, as the options stand
+        (PT_OPT_CULL_FOOTPRINT)."""
+        info = (ctypes.c_int * 3)()
+        _check(lib().pt_cull_info(self._c, info), "pt_cull_info")
+        return info[0], info[1], info[2]
 
     def sweep_walk(self):
         """Which walk the launches run as the options stand: 0 the threaded

@@ -1138,6 +1138,24 @@ int pt_dist_finalize(pt_context* ctx);
  * on the coherent rays of a 1080p frame 0 took 14 % less on the sphere and 10 %
  * more on the cloud (profiles/rays/timing.json).  Output is identical. */
 #define PT_OPT_RAYS_REFILL 32
+/* PT_OPT_CULL_FOOTPRINT: the per-sample skip of PT_OPT_CULL_TIGHT decides by
+ * footprints instead of the tight rectangles (pt_primary_cull_footprints): per
+ * object a convex region inside its tight rectangle -- every corner dilated by
+ * its own depth against the focal depths of the rays that can reach the
+ * object, and the hull of the results cut out of the rectangle by up to four
+ * half-planes.  A live pixel outside every footprint traces a sample only if
+ * one of its two radius draws is below the threshold, exactly as a pixel
+ * outside every tight rectangle does; there are more such pixels.  A pixel in
+ * a light's sure region (pt_primary_cull_sure) and in no footprint but that
+ * light's own takes (intensity, 1) for such samples instead of (0,0,0).  -1
+ * (default) = on, but off while PT_OPT_COUNT_TRACED is set: the counting pass
+ * then keeps the rectangle definition above, counts the margin samples by the
+ * rectangles, and so reports somewhat more primaries and closest walks than
+ * the fast kernel starts.  1 = on in counting mode too; 0 = off, the tight
+ * rectangles decide.  Off whenever PT_OPT_PRIMARY_CULL or PT_OPT_CULL_TIGHT
+ * is; stats mode never skips.  pt_cull_info reports what is in force.  Output
+ * is identical. */
+#define PT_OPT_CULL_FOOTPRINT 33
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
@@ -1167,6 +1185,34 @@ int pt_primary_cull_rects(const float camera_ubo[16], int width, int height, con
 int pt_primary_cull_rects_r(const float camera_ubo[16], int width, int height, const float root_min[3],
                             const float root_max[3], const pt_area_light* lights, int n_lights, double radius_bound,
                             float* rects, int max_rects, int* n_rects, float* u0);
+/* The footprints of the same objects for the same radius bound
+ * (PT_OPT_CULL_FOOTPRINT): 16 floats each, {x0, x1, y0, y1} then four
+ * half-planes {a, b, c}; a pixel origin (x, y) is inside when it is inside the
+ * rectangle and a * x + b * y <= c in float arithmetic for all four (an unused
+ * half-plane is {0, 0, 1}).  Outside every footprint no primary ray with such
+ * radii hits the root box or a light.  Each footprint lies inside the
+ * rectangle pt_primary_cull_rects_r gives its object for the same bound.
+ * *n_footprints = -1 as above (the kernel then goes by the rectangles).  Pure
+ * host function. */
+int pt_primary_cull_footprints(const float camera_ubo[16], int width, int height, const float root_min[3],
+                               const float root_max[3], const pt_area_light* lights, int n_lights,
+                               double radius_bound, float* footprints, int max_footprints, int* n_footprints);
+/* The sure regions for the same bound, one per light, in a footprint's layout
+ * (an empty one, x0 > x1, where none is derived: a non-finite intensity, a
+ * size component that is not positive -- intersectAreaLight never hits such
+ * a light -- a light seen nearly edge-on, a corner behind the camera).  Every primary ray
+ * with such radii from a pixel inside a light's region hits that light; where
+ * the pixel also lies outside the footprint of the root box and of every
+ * other light, the sample is exactly (intensity, 1).  *n_sure = the number of
+ * non-empty regions, or -1 when there are no footprints.  Pure host function. */
+int pt_primary_cull_sure(const float camera_ubo[16], int width, int height, const float root_min[3],
+                         const float root_max[3], const pt_area_light* lights, int n_lights, double radius_bound,
+                         float* regions, int max_regions, int* n_sure);
+/* What the per-sample skip of the context's next launch decides by, as its
+ * camera, size, scene, lights and options stand: info[0] = tight rectangles,
+ * info[1] = footprints among them (0: the rectangles alone decide), info[2] =
+ * non-empty sure regions.  Zeros when nothing is derived or the skip is off. */
+int pt_cull_info(pt_context* ctx, int info[3]);
 
 /* ---- instrumentation --------------------------------------------------- */
 /* Stats mode runs the reference-exhaustive traversal with counters (output is
