@@ -1147,6 +1147,7 @@ int pt_destroy(pt_context* c) {
   adaptive_release(c);
   display_release(c);
   rays_release(c);
+  upsample_release(c);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1233,6 +1234,7 @@ int pt_upload_scene(pt_context* c, const float* vertices, size_t n_vertex_floats
   c->guide_valid = false;
   temporal_forget(c);
   display_forget(c);
+  upsample_forget(c);
   adaptive_forget(c);
   const int T = (int)(n_indices / 3);
   struct Staging {   // vertex/index copies live only until the triangle records are built

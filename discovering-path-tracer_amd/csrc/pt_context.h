@@ -4,8 +4,8 @@
 // exchange, stats, timing); pt_plan.h the launch plan, every policy render_impl
 // carries out, as one pure function (plan_launch); pt_post.cpp the
 // post-processing chain (guide, filters, temporal accumulation);
-// pt_adaptive.cpp adaptive sampling; pt_display.cpp the display transform; pt_rays.cpp
-// the batched ray queries; pt_dist.cpp
+// pt_adaptive.cpp adaptive sampling; pt_display.cpp the display transform; pt_upsample.cpp
+// guide-driven upsampling; pt_rays.cpp the batched ray queries; pt_dist.cpp
 // the RCCL step loop; pt_group.cpp the multi-device context.  The fields of
 // pt_context are grouped in that order.
 #pragma once
@@ -319,6 +319,22 @@ struct pt_context {
   } drb[2];
   int drb_next_ticket = 1;
 
+  // ---- pt_upsample.cpp: guide-driven upsampling (freed by upsample_release) ----------------
+  // the guide of the full frame, (up_scale * width) x (up_scale * height), kept until the scene, the camera,
+  // the frame size or the scale changes
+  float4* d_up_guide = nullptr;
+  size_t up_guide_cap = 0;
+  int up_scale = 0;                    // the scale d_up_guide was rendered for (0: it holds no guide)
+  int up_w = 0, up_h = 0;              // ... and the render size
+  float up_cam[16] = {0};              // ... and the camera
+  int up_guide_launches = 0;           // guide launches of pt_upsample and pt_upsample_display so far
+  float4* d_upsampled = nullptr;       // pt_upsample's destination when the caller gives none
+  size_t upsampled_cap = 0;
+  int upsampled_w = 0, upsampled_h = 0;   // full size of the image d_upsampled holds (0: none yet)
+  uint32_t* d_up_display = nullptr;    // pt_upsample_display's destination when the caller gives none
+  size_t up_display_cap = 0;
+  int up_display_w = 0, up_display_h = 0;
+
   // ---- pt_rays.cpp: batched ray queries (freed by rays_release) ---------------------------
   uint32_t* d_rays_counters = nullptr; // the wide kernel's ray cursor and its count of marked rays
   int* d_rays_slot = nullptr;          // rank -> triangle index of the scene's wide tree, built by the first
@@ -345,6 +361,10 @@ inline void temporal_forget(pt_context* c) {
 // The metering state of the display transform is forgotten (pt_display_reset; a new scene, frame size or
 // bound buffer): the next metering pt_display runs without a previous scale.
 inline void display_forget(pt_context* c) { c->meter_have = false; }
+
+// The full-size guide of pt_upsample is forgotten (a new scene; a new camera, frame size or scale is seen by
+// the call itself): the next pt_upsample renders it again.
+inline void upsample_forget(pt_context* c) { c->up_scale = 0; }
 
 // The adaptive state ends (a scene, light or params upload, a resize, a rebind, pt_clear_accum, any render):
 // pt_adaptive_advance and the reads then ask for a new pt_adaptive_begin.  The buffers stay.
@@ -464,6 +484,15 @@ void post_release(pt_context* c);      // frees what pt_post.cpp allocates (pt_d
 void adaptive_release(pt_context* c);  // ... and pt_adaptive.cpp
 void display_release(pt_context* c);   // ... and pt_display.cpp
 void rays_release(pt_context* c);      // ... and pt_rays.cpp
+void upsample_release(pt_context* c);  // ... and pt_upsample.cpp
+// ---- what pt_post.cpp gives pt_upsample.cpp: the parameters of a guide launch of the context's scene and camera
+// for a width x height frame as pt_render_guide makes them (the walk its rules choose, the wide walk's arrays
+// grown); *lds: the scene is staged in LDS.  The checks of pt_render_guide are the caller's.
+int guide_launch_params(pt_context* c, int width, int height, ptd::RenderParams* p, bool* lds);
+// ... and pt_display.cpp: the metering launch of a w x h source (buffers grown, the state advanced); the state the
+// display kernels read
+int display_meter(pt_context* c, const pt_display_params& p, const float4* src, int w, int h);
+int display_checked_params(const pt_display_params* in, pt_display_params* p);
 // ---- what pt_post.cpp gives pt_adaptive.cpp: the variance-guided filter's passes from a variance plane
 // (pt_post.cpp var_filter), and the validated filter parameters
 int post_var_filter(pt_context* c, const pt_denoise_var_params& p, const float4* src, const float* var0,

@@ -40,6 +40,22 @@ static int display_params(const pt_display_params* in, pt_display_params* p) {
   return PT_OK;
 }
 
+int display_checked_params(const pt_display_params* in, pt_display_params* p) { return display_params(in, p); }
+
+// The metering of a w x h source on the context's stream, behind order_shared: the scale lands in the
+// state (c->d_meter_state), which the next metering call reads as the previous one.
+int display_meter(pt_context* c, const pt_display_params& p, const float4* src, int w, int h) {
+  const size_t tiles = (size_t)((w + 15) / 16) * (size_t)((h + 15) / 16);
+  int rg = grow_dev(c, &c->d_meter_sum, &c->meter_cap[0], tiles);
+  if (!rg) rg = grow_dev(c, &c->d_meter_n, &c->meter_cap[1], tiles);
+  if (rg) return rg;
+  if (!c->d_meter_state) PT_HIP(hipMalloc(&c->d_meter_state, sizeof(ptdp::MeterState)));
+  PT_HIP(ptd::launch_display_meter(src, w, h, c->d_meter_sum, c->d_meter_n, p.key, p.adapt,
+                                   display_has_prev(c) ? 1 : 0, (ptdp::MeterState*)c->d_meter_state, c->stream));
+  c->meter_have = true;
+  return PT_OK;
+}
+
 // The checks pt_display and pt_display_readback_begin share.
 static int display_args(pt_context* c, const pt_display_params* params, const void* src, const void* dst,
                         pt_display_params* p) {
@@ -61,19 +77,11 @@ static int display_args(pt_context* c, const pt_display_params* params, const vo
 static int display_launch(pt_context* c, const pt_display_params& p, const float4* src, uint32_t* out) {
   const int w = c->width, h = c->height;
   const ptdp::MeterState* state = nullptr;
-  if (p.auto_exposure) {
-    const size_t tiles = (size_t)((w + 15) / 16) * (size_t)((h + 15) / 16);
-    int rg = grow_dev(c, &c->d_meter_sum, &c->meter_cap[0], tiles);
-    if (!rg) rg = grow_dev(c, &c->d_meter_n, &c->meter_cap[1], tiles);
-    if (rg) return rg;
-    if (!c->d_meter_state) PT_HIP(hipMalloc(&c->d_meter_state, sizeof(ptdp::MeterState)));
-  }
   const int ro = order_shared(c);
   if (ro) return ro;
   if (p.auto_exposure) {
-    PT_HIP(ptd::launch_display_meter(src, w, h, c->d_meter_sum, c->d_meter_n, p.key, p.adapt,
-                                     display_has_prev(c) ? 1 : 0, (ptdp::MeterState*)c->d_meter_state, c->stream));
-    c->meter_have = true;
+    const int rm = display_meter(c, p, src, w, h);
+    if (rm) return rm;
     state = (const ptdp::MeterState*)c->d_meter_state;
   }
   PT_HIP(ptd::launch_display(src, out, (size_t)w * h, p.tonemap, p.exposure, p.white * p.white, state,

@@ -39,6 +39,23 @@ static P params_or(const P* in, int (*defaults)(P*)) {
   return p;
 }
 
+// The parameters of a guide launch for a width x height frame (pt_render_guide at the context's size,
+// pt_upsample at the full one): the scene and the camera, the frame fields for that size, and the walk.
+int guide_launch_params(pt_context* c, int width, int height, ptd::RenderParams* p, bool* lds) {
+  frame_params(c, false, p);
+  p->width = width;
+  p->height = height;
+  p->blocks_x = (width + 15) / 16;
+  p->blocks_total = p->blocks_x * ((height + 15) / 16);
+  p->n_cull = -1;
+  // the wide walk first, then the LDS rule (pt_plan.h)
+  const bool wide = c->opt_wide && c->n_wide > 0;
+  const bool fits = lds_fits(*c, c->n_nodes);
+  if (!wide && lds_refused(*c, fits)) return fail(PT_ERR_UNSUPPORTED, kLdsTooLarge);
+  *lds = !wide && lds_staged(*c, fits);
+  return wide ? wide_params(c, p) : PT_OK;
+}
+
 extern "C" {
 
 // ---- first-hit guide image and a-trous denoiser (pt_denoise.h) --------------
@@ -98,17 +115,9 @@ int pt_render_guide(pt_context* c) {
   PT_HIP(hipSetDevice(c->device));
   c->guide_valid = false;
   ptd::RenderParams p{};
-  frame_params(c, false, &p);
-  p.n_cull = -1;
-  // the wide walk first, then the LDS rule (pt_plan.h)
-  const bool wide = c->opt_wide && c->n_wide > 0;
-  const bool fits = lds_fits(*c, c->n_nodes);
-  if (!wide && lds_refused(*c, fits)) return fail(PT_ERR_UNSUPPORTED, kLdsTooLarge);
-  const bool lds = !wide && lds_staged(*c, fits);
-  if (wide) {
-    const int rw = wide_params(c, &p);
-    if (rw) return rw;
-  }
+  bool lds = false;
+  const int rp = guide_launch_params(c, c->width, c->height, &p, &lds);
+  if (rp) return rp;
   // the temporal history's guide is put aside before the image is written again (stream order keeps
   // whatever still reads it correct: only the pointers move)
   if (c->t_frames > 0 && !c->t_guide_aside && c->guide_serial == c->t_guide_serial) {

@@ -9,6 +9,7 @@
 //             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
 //             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]
 //             [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY] [-pick X Y]
+//             [-upsample S]
 //
 // -pick X Y prints, before anything is rendered, the closest hit of the guide ray of pixel (X, Y)
 // (pt_guide_ray, pt_trace_rays_sync): t, the triangle's index, u, v, the normal and the position o + d * t,
@@ -48,6 +49,10 @@
 // parameters at their defaults) and write its bytes with pt_write_png8; a
 // filter then writes into an image of the driver's own.  Without any of the
 // three -png is pt_write_image's encode of the floats, as ever.
+// -upsample S (2 to 8) renders at -w / -h and writes the (S*w) x (S*h) frame: whatever image the other flags
+// produced (raw, -denoise, -denoise-var, -temporal, -adaptive) goes through pt_upsample at the default sigmas
+// before -o / -png are written, and with the display flags -png holds pt_upsample_display's bytes (the fused
+// kernel; metering sees the rendered pixels).  A single-device context.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -75,7 +80,7 @@ int main(int argc, char** argv) {
             "usage: %s scene.obj [-w W] [-h H] [-spp N] [-depth D] [-sss S] [-fused] [-o out.pfm] [-png out.png]\n"
             "       [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]] [-device D | -devices D0,D1,..] [-cache scene.ptscene]\n"
             "       [-progressive N [-chunk K] [-orbit-at B]] [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]\n"
-            "       [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY] [-pick X Y]\n",
+            "       [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY] [-pick X Y] [-upsample S]\n",
             argv[0]);
     return 2;
   }
@@ -94,6 +99,7 @@ int main(int argc, char** argv) {
   pt_display_default_params(&dp);
   bool pick = false;
   int pick_x = 0, pick_y = 0;
+  int upsample = 0;   // -upsample: the scale, 0 = off
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -146,6 +152,7 @@ int main(int argc, char** argv) {
       pick_x = atoi(next());
       pick_y = atoi(next());
     }
+    else if (!strcmp(argv[i], "-upsample")) upsample = atoi(next());
     else if (!strcmp(argv[i], "-auto-exposure")) {
       display = true;
       dp.auto_exposure = 1;
@@ -301,7 +308,7 @@ int main(int argc, char** argv) {
     const void* src = nullptr;   // null: the accumulation image
     const bool filters = (temporal > 0 && progressive == 0) ? (temporal_spatial || denoise_var)
                                                             : (denoise_var || denoise);
-    if (shown && filters && hipMalloc(&filtered, rgba.size() * sizeof(float)) != hipSuccess) {
+    if ((shown || upsample) && filters && hipMalloc(&filtered, rgba.size() * sizeof(float)) != hipSuccess) {
       fprintf(stderr, "no device memory for the filtered image\n");
       return 1;
     }
@@ -328,12 +335,32 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    if (!out_path.empty()) check(pt_write_image(out_path.c_str(), rgba.data(), W, H, PT_IMAGE_PFM), "write pfm");
+    // the frame written: the rendered one, or with -upsample the full-size one of the image src names
+    int FW = W, FH = H;
+    if (upsample) {
+      pt_upsample_params up;
+      pt_upsample_default_params(&up);
+      up.scale = upsample;
+      FW = W * upsample;
+      FH = H * upsample;
+      if (!out_path.empty() || !shown) {
+        check(pt_upsample(ctx, &up, src, nullptr), "upsample");
+        rgba.resize((size_t)FW * FH * 4);
+        check(pt_read_upsampled(ctx, rgba.data(), rgba.size()), "read upsampled");
+      }
+      if (shown) check(pt_upsample_display(ctx, &up, &dp, src, nullptr), "upsample display");
+      printf("upsampled %dx%d to %dx%d\n", W, H, FW, FH);
+    }
+    if (!out_path.empty()) check(pt_write_image(out_path.c_str(), rgba.data(), FW, FH, PT_IMAGE_PFM), "write pfm");
     if (shown) {
-      std::vector<unsigned char> rgba8((size_t)W * H * 4);
-      check(pt_display(ctx, &dp, src, nullptr), "display");
-      check(pt_read_display(ctx, rgba8.data(), rgba8.size()), "read display");
-      check(pt_write_png8(png_path.c_str(), rgba8.data(), W, H), "write png");
+      std::vector<unsigned char> rgba8((size_t)FW * FH * 4);
+      if (upsample) {
+        check(pt_read_display_upsampled(ctx, rgba8.data(), rgba8.size()), "read upsampled display");
+      } else {
+        check(pt_display(ctx, &dp, src, nullptr), "display");
+        check(pt_read_display(ctx, rgba8.data(), rgba8.size()), "read display");
+      }
+      check(pt_write_png8(png_path.c_str(), rgba8.data(), FW, FH), "write png");
       if (dp.auto_exposure) {
         float scale = 0.0f;
         uint32_t n = 0;
@@ -341,7 +368,7 @@ int main(int argc, char** argv) {
         printf("display: auto exposure %.6g from %u metered pixels\n", scale, n);
       }
     } else if (!png_path.empty()) {
-      check(pt_write_image(png_path.c_str(), rgba.data(), W, H, PT_IMAGE_PNG), "write png");
+      check(pt_write_image(png_path.c_str(), rgba.data(), FW, FH, PT_IMAGE_PNG), "write png");
     }
     if (filtered) (void)hipFree(filtered);
   }

@@ -86,6 +86,9 @@ EXPORTS = [
     "pt_display_default_params", "pt_display", "pt_display_device_ptr", "pt_read_display", "pt_display_exposure",
     "pt_display_reset", "pt_display_readback_begin", "pt_display_readback_end", "pt_display_host", "pt_write_png8",
     "pt_trace_rays", "pt_trace_rays_sync", "pt_trace_rays_host",
+    "pt_upsample_default_params", "pt_upsample_host", "pt_upsample_images", "pt_upsample", "pt_upsampled_device_ptr",
+    "pt_read_upsampled", "pt_upsample_guide_device_ptr", "pt_upsample_info", "pt_upsample_display",
+    "pt_display_upsampled_device_ptr", "pt_read_display_upsampled",
 ]
 
 
@@ -138,6 +141,10 @@ class DisplayParams(ctypes.Structure):
 
 
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+
+
+class UpsampleParams(ctypes.Structure):
+    _fields_ = [("scale", ctypes.c_int), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float)]
 
 
 class ReprojectImages(ctypes.Structure):
@@ -269,6 +276,14 @@ def lib():
             "pt_write_png8": ([ctypes.c_char_p, vp, i32, i32], i32),
             "pt_trace_rays": ([vp, i32, vp, sz, vp], i32), "pt_trace_rays_sync": ([vp, i32, vp, sz, vp], i32),
             "pt_trace_rays_host": ([vp, sz, vp, sz, vp, sz, u32, i32, vp, sz, vp, i32], i32),
+            "pt_upsample_default_params": ([ctypes.POINTER(UpsampleParams)], i32),
+            "pt_upsample_host": ([vp, i32, i32, vp, ctypes.POINTER(UpsampleParams), vp], i32),
+            "pt_upsample_images": ([vp, ctypes.POINTER(UpsampleParams), vp, i32, i32, vp, vp], i32),
+            "pt_upsample": ([vp, ctypes.POINTER(UpsampleParams), vp, vp], i32),
+            "pt_upsampled_device_ptr": ([vp], vp), "pt_read_upsampled": ([vp, vp, sz], i32),
+            "pt_upsample_guide_device_ptr": ([vp], vp), "pt_upsample_info": ([vp, ctypes.POINTER(i32)], i32),
+            "pt_upsample_display": ([vp, ctypes.POINTER(UpsampleParams), ctypes.POINTER(DisplayParams), vp, vp], i32),
+            "pt_display_upsampled_device_ptr": ([vp], vp), "pt_read_display_upsampled": ([vp, vp, sz], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -556,6 +571,49 @@ def display_host(rgba, width, height, params=None, auto_scale=0.0):
     _check(lib().pt_display_host(a.ctypes.data, width, height, _display_params(params), ctypes.byref(scale),
                                  out.ctypes.data), "pt_display_host")
     return out.reshape(height, width, 4), scale.value
+
+
+def upsample_default_params():
+    """pt_upsample_default_params as an UpsampleParams."""
+    p = UpsampleParams()
+    _check(lib().pt_upsample_default_params(ctypes.byref(p)), "pt_upsample_default_params")
+    return p
+
+
+def _upsample_params(params):
+    """None (the library's defaults), an UpsampleParams, a scale alone, or
+    (scale, sigma_normal, sigma_depth) -> what ctypes passes."""
+    if params is None:
+        return None
+    if isinstance(params, UpsampleParams):
+        return ctypes.byref(params)
+    if isinstance(params, int):
+        p = upsample_default_params()
+        p.scale = params
+        return ctypes.byref(p)
+    s, sn, sz = params
+    return ctypes.byref(UpsampleParams(int(s), float(sn), float(sz)))
+
+
+def _upsample_scale(params):
+    """The scale of what _upsample_params takes."""
+    if params is None:
+        return upsample_default_params().scale
+    return params.scale if isinstance(params, UpsampleParams) else params if isinstance(params, int) else int(params[0])
+
+
+def upsample_host(src, width, height, guide_full, params=None):
+    """pt_upsample_host: the (height, width, 4) image src onto the grid of the
+    (s*height, s*width, 4) guide, as (s*height, s*width, 4) float32."""
+    s = _upsample_scale(params)
+    a = np.ascontiguousarray(src, np.float32).reshape(-1)
+    g = np.ascontiguousarray(guide_full, np.float32).reshape(-1)
+    if a.size != width * height * 4 or g.size != a.size * s * s:
+        raise PTError("src must hold width*height*4 floats, guide_full scale*scale as many")
+    out = np.empty(g.size, np.float32)
+    _check(lib().pt_upsample_host(a.ctypes.data, width, height, g.ctypes.data, _upsample_params(params),
+                                  out.ctypes.data), "pt_upsample_host")
+    return out.reshape(height * s, width * s, 4)
 
 
 def default_camera():
@@ -1151,6 +1209,58 @@ class Renderer:
         out = np.empty(self.width * self.height * 4, np.uint8)
         _check(lib().pt_display_readback_end(self._c, ticket, out.ctypes.data, out.size), "pt_display_readback_end")
         return out.reshape(self.height, self.width, 4)
+
+    def upsample_info(self):
+        """pt_upsample_info: {"scale", "guide_size", "guide_launches", "size", "display_size"} (sizes as (W, H))."""
+        info = (ctypes.c_int * 8)()
+        _check(lib().pt_upsample_info(self._c, info), "pt_upsample_info")
+        return {"scale": info[0], "guide_size": (info[1], info[2]), "guide_launches": info[3],
+                "size": (info[4], info[5]), "display_size": (info[6], info[7])}
+
+    def read_upsampled(self):
+        """The library-owned upsampled image, (H, W, 4) float32 at the full size."""
+        W, H = self.upsample_info()["size"]
+        out = np.empty(W * H * 4, np.float32)
+        _check(lib().pt_read_upsampled(self._c, out.ctypes.data, out.size), "pt_read_upsampled")
+        return out.reshape(H, W, 4)
+
+    def upsample(self, params=None, src_ptr=None, dst_ptr=None):
+        """pt_upsample: src (default: the accumulation image) of the context's
+        render size onto the full grid under the full-size guide the context
+        renders and keeps; with dst_ptr None the library-owned result is read
+        back and returned as (s*H, s*W, 4) float32."""
+        _check(lib().pt_upsample(self._c, _upsample_params(params), src_ptr, dst_ptr), "pt_upsample")
+        return self.read_upsampled() if dst_ptr is None else None
+
+    def upsample_images(self, src_ptr, width, height, guide_full_ptr, dst_ptr=None, params=None):
+        """pt_upsample_images: the same on explicit device images (no scene needed)."""
+        _check(lib().pt_upsample_images(self._c, _upsample_params(params), src_ptr, width, height, guide_full_ptr,
+                                        dst_ptr), "pt_upsample_images")
+        return self.read_upsampled() if dst_ptr is None else None
+
+    def upsampled_ptr(self):
+        return lib().pt_upsampled_device_ptr(self._c)
+
+    def upsample_guide_ptr(self):
+        """pt_upsample_guide_device_ptr: the full-size guide pt_upsample keeps, or None."""
+        return lib().pt_upsample_guide_device_ptr(self._c)
+
+    def upsample_display(self, params=None, display_params=None, src_ptr=None, dst_ptr=None):
+        """pt_upsample_display: upsampling and the display transform in one
+        kernel; with dst_ptr None the library-owned result is read back and
+        returned as (s*H, s*W, 4) uint8.  Metering sees the rendered pixels."""
+        _check(lib().pt_upsample_display(self._c, _upsample_params(params), _display_params(display_params), src_ptr,
+                                         dst_ptr), "pt_upsample_display")
+        return self.read_display_upsampled() if dst_ptr is None else None
+
+    def display_upsampled_ptr(self):
+        return lib().pt_display_upsampled_device_ptr(self._c)
+
+    def read_display_upsampled(self):
+        W, H = self.upsample_info()["display_size"]
+        out = np.empty(W * H * 4, np.uint8)
+        _check(lib().pt_read_display_upsampled(self._c, out.ctypes.data, out.size), "pt_read_display_upsampled")
+        return out.reshape(H, W, 4)
 
     def trace_rays(self, rays, kind=RAYS_CLOSEST):
         """The caller's own rays against the uploaded scene (needs nothing else): closest hits or occlusion.

@@ -64,7 +64,11 @@ extern "C" {
  * pt_display_readback_begin, pt_display_readback_end, pt_display_host,
  * pt_write_png8); batched ray queries (pt_ray, pt_hit, PT_RAYS_CLOSEST,
  * PT_RAYS_ANY, pt_trace_rays, pt_trace_rays_sync, pt_trace_rays_host,
- * PT_OPT_RAYS_REFILL). */
+ * PT_OPT_RAYS_REFILL); guide-driven upsampling (pt_upsample_params,
+ * pt_upsample_default_params, pt_upsample_host, pt_upsample_images,
+ * pt_upsample, pt_upsampled_device_ptr, pt_read_upsampled,
+ * pt_upsample_guide_device_ptr, pt_upsample_info, pt_upsample_display,
+ * pt_display_upsampled_device_ptr, pt_read_display_upsampled). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -730,6 +734,107 @@ int pt_display_readback_end(pt_context* ctx, int ticket, unsigned char* rgba8, s
  * none; out, the scale this call used. */
 int pt_display_host(const float* rgba, int w, int h, const pt_display_params* params,
                     float* auto_scale_io, unsigned char* rgba8);
+
+/* ---- guide-driven upsampling: render at 1/s size, present at full size ----
+ * An interactive host lowers the render size while the camera moves and still
+ * presents a full-size frame.  The context stays at the render size w x h; the
+ * calls below put a w x h float4 image onto the W x H = (s*w) x (s*h) grid by
+ * joint bilateral upsampling (Kopf et al. 2007) under the full-size guide image
+ * {n.xyz, t}, which costs one ray a pixel and carries the silhouettes.
+ *
+ * A pixel's samples are jittered around ndc = 2 * px / W - 1, the pixel's
+ * lattice point, so pixel (i, j) of the w x h frame looks along exactly the
+ * guide ray of pixel (s*i, s*j) of the full frame (pt_guide_ray gives the same
+ * bits for both): the rendered frame is the full frame sampled at every s-th
+ * lattice point, its guide is the full guide at stride s, and one guide serves
+ * both ends of a tap.  The statement (csrc/pt_upsample.h), for the output pixel
+ * (X, Y), src the w x h image and G the full guide:
+ *
+ *   i0 = X / s, j0 = Y / s;  fx = float(X - i0*s) / float(s), fy likewise
+ *   bx = {1 - fx, fx}, by = {1 - fy, fy}
+ *   over the taps (i0 + di, j0 + dj), dj = 0..1 outer, di = 0..1 inner, those
+ *   outside the w x h frame and those with bx[di] == 0 or by[dj] == 0 skipped:
+ *     gq = G[(j*s) * W + i*s], gp = G[Y * W + X]
+ *     d2n = (nx*nx + ny*ny) + nz*nz over gp.xyz - gq.xyz;  dz = gp.w - gq.w
+ *     wt  = (bx[di] * by[dj]) * exp(-(d2n / sn2 + (dz*dz) / sz2))
+ *     sum.rgb += wt * src[j*w + i].rgb;  sum.w += wt
+ *   out.rgb = sum.w > 0 ? sum.rgb / sum.w : src[j0*w + i0].rgb;  out.a = src[j0*w + i0].a
+ *
+ * sn2 = sigma_normal^2, sz2 = sigma_depth^2.  Every operation is a single IEEE
+ * fp32 operation in the stated order and exp the library's own, so the device
+ * calls and pt_upsample_host give the same bits.  At the lattice points the
+ * result is the rendered value (out[s*j][s*i] == src[j][i]; a -0 comes out +0):
+ * one tap is left, its guide is the pixel's own, its weight exactly 1.  A hit
+ * beside a miss weighs 0 (dz * dz = inf), so silhouettes stay where the full
+ * guide has them; a tap of zero bilinear weight is skipped, so a NaN or
+ * infinite colour reaches only the pixels strictly inside its four cells.  The
+ * fallback src[j0*w + i0] applies when no tap is left a weight (also when a NaN
+ * guide makes the sum NaN).
+ *
+ * Time and error against a full-size render: profiles/upsample/, DESIGN.md
+ * section 9h. */
+typedef struct pt_upsample_params {
+  int   scale;          /* s: 2 to 8; default 2 */
+  float sigma_normal;   /* finite, > 0, its square finite and non-zero; default 0.35 */
+  float sigma_depth;    /* the same; default 0.25 */
+} pt_upsample_params;
+int pt_upsample_default_params(pt_upsample_params* out);
+/* The statement on the host: src w*h*4 floats, guide_full (s*w)*(s*h)*4 floats,
+ * out as many.  PT_ERR_INVALID for bad parameters, and for a full frame of more
+ * than 2^31 pixels; a 1x1 source is valid.  params null: the defaults. */
+int pt_upsample_host(const float* src, int w, int h, const float* guide_full, const pt_upsample_params* params,
+                     float* out);
+/* Enqueues the statement on explicit device images, as pt_reproject and
+ * pt_spatial_variance take theirs: src_device w x h float4, guide_full_device
+ * and dst_device (s*w) x (s*h) float4, all 16-B aligned, the destination
+ * overlapping neither input.  dst_device null: a library-owned image
+ * (pt_upsampled_device_ptr, pt_read_upsampled).  Needs no scene, camera or
+ * frame.  PT_ERR_UNSUPPORTED on a pt_create_multi context, as every call below
+ * that takes a context. */
+int pt_upsample_images(pt_context* ctx, const pt_upsample_params* params, const void* src_device, int w, int h,
+                       const void* guide_full_device, void* dst_device);
+/* The same with the context's own inputs.  The context stays at the render
+ * size w x h (pt_resize_and_clear / pt_bind_accum).  src_device null: the
+ * accumulation image; else any w x h float4 image (pt_denoise's,
+ * pt_temporal_device_ptr's, the adaptive filter's).  dst_device null: the
+ * library-owned (s*w) x (s*h) image.  The call renders the full-size guide
+ * itself into a library-owned image (pt_upsample_guide_device_ptr), by the
+ * launch pt_render_guide makes, with the frame size (s*w) x (s*h) and the walk
+ * that pt_render_guide would take, and keeps it until the scene, the camera,
+ * the frame size or the scale changes: while none does, a call launches the
+ * upsampling kernel alone.  The context's own w x h guide (pt_render_guide) is
+ * neither read nor written.  PT_ERR_INVALID without a scene, a camera or a
+ * frame. */
+int pt_upsample(pt_context* ctx, const pt_upsample_params* params, const void* src_device, void* dst_device);
+/* The library-owned image of the last pt_upsample or pt_upsample_images with a
+ * null destination (null: none), and its copy to the host behind the enqueued
+ * work: n_floats >= W*H*4 of that image (pt_upsample_info gives W and H). */
+void* pt_upsampled_device_ptr(pt_context* ctx);
+int pt_read_upsampled(pt_context* ctx, float* rgba, size_t n_floats);
+/* The full-size guide pt_upsample keeps, (s*w) x (s*h) float4; null when there
+ * is none for the current scene, camera and frame size. */
+void* pt_upsample_guide_device_ptr(pt_context* ctx);
+/* info[0] the scale of the kept guide (0: none for the current inputs), [1] and
+ * [2] its width and height, [3] the guide launches pt_upsample and
+ * pt_upsample_display have made on this context (a call that finds its guide
+ * kept adds none), [4] and [5] the size of the library-owned upsampled image,
+ * [6] and [7] that of the library-owned upsampled display image (0: none). */
+int pt_upsample_info(pt_context* ctx, int info[8]);
+/* pt_upsample and pt_display in one kernel: the upsampled pixel goes through
+ * the display transform (display_params; null: the defaults) and is written as
+ * the RGBA8 word; the full-size float image is never written or read back,
+ * 32 B a pixel less.  The bytes are those of pt_display_host of
+ * pt_upsample_host's image.  With auto_exposure the metering sees the rendered
+ * w x h pixels (src_device), not the upsampled ones: it is the metering launch
+ * and state of pt_display, so the scale adapts across pt_display and this call
+ * alike, and pt_display_exposure / pt_display_reset apply.  dst_device null: a
+ * library-owned image (pt_display_upsampled_device_ptr,
+ * pt_read_display_upsampled: n_bytes >= W*H*4); else W*H 32-bit words, 4-B
+ * aligned. */
+int pt_upsample_display(pt_context* ctx, const pt_upsample_params* upsample_params,
+                        const pt_display_params* display_params, const void* src_device, void* dst_device);
+void* pt_display_upsampled_device_ptr(pt_context* ctx);
+int pt_read_display_upsampled(pt_context* ctx, unsigned char* rgba8, size_t n_bytes);
 
 /* ---- batched ray queries: closest hit and occlusion -------------------- */
 /* The caller's own rays against the uploaded scene, answered by the walks the
