@@ -103,37 +103,8 @@ __device__ __forceinline__ bool trav_step(const RenderParams& P, Trav& T, int* c
   return false;
 }
 
-struct CamFrame {
-  v3 cpos, cdir, right, up;
-  float tanFov, aspect, ndcX0, ndcY0;
-  int W, H, px, py;
-};
-
-// main() ray generation (:430-460) for one sample batch.
-__device__ __forceinline__ void camera_ray(const CamFrame& F, uint32_t seed, v3* origin, v3* dir) {
-  uint32_t rng = seed;
-  float u1 = fmax_(1e-38f, rng_next(&rng));
-  float u2 = rng_next(&rng);
-  float r = sqrt_(-2.0f * log_(u1));
-  float th = (2.0f * 0x1.921fb6p+1f) * u2;
-  float sn, cs;
-  sincos_(th, &sn, &cs);
-  const float ax = (r * cs) * 0.02f;
-  const float ay = (r * sn) * 0.02f;
-  *origin = add(add(F.cpos, muls(F.right, ax)), muls(F.up, ay));
-  u1 = fmax_(1e-38f, rng_next(&rng));
-  u2 = rng_next(&rng);
-  r = sqrt_(-2.0f * log_(u1));
-  th = (2.0f * 0x1.921fb6p+1f) * u2;
-  sincos_(th, &sn, &cs);
-  const float jx = r * cs, jy = r * sn;
-  const float ndcX = F.ndcX0 + (jx * 0.5f) / (float)F.W;
-  const float ndcY = F.ndcY0 + (jy * 0.5f) / (float)F.H;
-  const v3 bdir =
-      normalize(sub(add(F.cdir, muls(neg(F.right), (ndcX * F.tanFov) * F.aspect)), muls(F.up, ndcY * F.tanFov)));
-  const v3 focal = add(F.cpos, muls(bdir, 3.0f));
-  *dir = normalize(sub(focal, *origin));
-}
+// CamFrame and camera_ray, main()'s ray generation (:430-460) for one sample batch: pt_camera_ray.h, which the
+// host compiles too (pt_camera_rays_host).
 
 // pathTrace (:300-418) as a state machine over one sample: runs shading from
 // the current phase until a ray must be traced (returns true, T set up; the

@@ -1009,6 +1009,15 @@ int adaptive_launch_wavefront(pt_context* c, const AdaptivePlan& ap, uint32_t re
   return PT_OK;
 }
 
+int radiance_wf_buffers(pt_context* c, long long paths, ptd::WfBuffers* b) {
+  long long chunk_paths = 0;
+  const int rc = wf_reserve(c, paths, 1, &chunk_paths);   // one "batch" of `paths` "pixels": no less than asked for
+  if (rc) return rc;
+  *b = c->wf;
+  b->cap = chunk_paths;
+  return PT_OK;
+}
+
 // The device arrays of the uploaded scene: pt_upload_scene replaces them,
 // pt_destroy frees them.
 static void scene_release(pt_context* c) {
@@ -1148,6 +1157,7 @@ int pt_destroy(pt_context* c) {
   display_release(c);
   rays_release(c);
   upsample_release(c);
+  radiance_release(c);
   for (auto& r : c->rb) {
     dev_free(r.dev);
     if (r.host) (void)hipHostFree(r.host);
@@ -1643,6 +1653,7 @@ static const IntOption kIntOptions[] = {
     {PT_OPT_ADAPTIVE_WF, &pt_context::opt_adaptive_wf, 0, 1, "PT_OPT_ADAPTIVE_WF takes 0 or 1"},
     {PT_OPT_RAYS_REFILL, &pt_context::opt_rays_refill, 0, 1, "PT_OPT_RAYS_REFILL takes 0 or 1"},
     {PT_OPT_CULL_FOOTPRINT, &pt_context::opt_cull_foot, -1, 1, "PT_OPT_CULL_FOOTPRINT takes -1 (auto), 0 or 1"},
+    {PT_OPT_RADIANCE_CHUNK, &pt_context::opt_radiance_chunk, 0, INT_MAX, "PT_OPT_RADIANCE_CHUNK takes 0 (auto) or a path count"},
 };
 
 int pt_set_option(pt_context* c, int key, int value) {

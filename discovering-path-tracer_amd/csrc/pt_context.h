@@ -344,8 +344,16 @@ struct pt_context {
   void* d_rays_out = nullptr;
   size_t rays_in_cap = 0, rays_out_cap = 0;   // rays / answers of 32 B they hold
 
+  // ---- pt_radiance.cpp: radiance queries (freed by radiance_release) ------------------------
+  int opt_radiance_chunk = 0;          // PT_OPT_RADIANCE_CHUNK: paths per chunk, 0 auto (kRadianceAutoChunk)
+  float4* d_rad_colors = nullptr;      // the path-recursive kernel's colour per path of a chunk, grown on demand
+  size_t rad_colors_cap = 0;           // (the wavefront pipeline's are wf.colors)
+  void* d_rad_in = nullptr;            // pt_trace_radiance_sync's staging buffers, grown on demand
+  float4* d_rad_out = nullptr;
+  size_t rad_in_cap = 0, rad_out_cap = 0;   // queries of 32 B / answers of 16 B they hold
+
   // ---- pt_dist.cpp, pt_group.cpp ------------------------------------------------------
-  DistState* dist = nullptr;           // pt_dist_init
+  DistState* dist = nullptr;          // pt_dist_init
   bool in_dist = false;                // inside pt_dist_run: it records the use events itself
   pt_group* group = nullptr;           // pt_create_multi: every call goes to the group (pt_group.cpp)
 };
@@ -485,6 +493,10 @@ void adaptive_release(pt_context* c);  // ... and pt_adaptive.cpp
 void display_release(pt_context* c);   // ... and pt_display.cpp
 void rays_release(pt_context* c);      // ... and pt_rays.cpp
 void upsample_release(pt_context* c);  // ... and pt_upsample.cpp
+void radiance_release(pt_context* c);  // ... and pt_radiance.cpp
+// ---- what the core gives pt_radiance.cpp: the wavefront pipeline's path buffers, grown to hold `paths` paths
+// (they are the renders' own: a query between two renders finds them, or leaves them larger); b->cap = paths
+int radiance_wf_buffers(pt_context* c, long long paths, ptd::WfBuffers* b);
 // ---- what pt_post.cpp gives pt_upsample.cpp: the parameters of a guide launch of the context's scene and camera
 // for a width x height frame as pt_render_guide makes them (the walk its rules choose, the wide walk's arrays
 // grown); *lds: the scene is staged in LDS.  The checks of pt_render_guide are the caller's.

@@ -295,6 +295,20 @@ constexpr int kRaysClosest = 0, kRaysAny = 1;   // == PT_RAYS_CLOSEST, PT_RAYS_A
 hipError_t launch_rays(const RenderParams& p, int kind, const void* rays, size_t n, void* out, uint32_t* counters,
                        const int* slot_of, bool lds_scene, bool refill, hipStream_t stream);
 hipError_t launch_rays_slots(const int* rank_of, int n, int* slot_of, hipStream_t stream);
+// Radiance queries (pt_trace_radiance, kernels/radiance.h): one chunk, queries q0 .. q0 + n_queries of `rays`
+// (2 float4 each: {o.xyz, d.x} {d.yz, -, seed}), n_samples samples each from the seeds seed + s * seed_stride,
+// folded into out[q0 ..] (one float4 a query).  p: the scene, lights, parameters and walk choices (plan_radiance).
+// launch_radiance: the path-recursive kernel; colors holds n_queries * n_samples float4, library-owned.
+// launch_wavefront_rays: the wavefront pipeline's rounds behind wf_gen_rays_kernel, in b (cap >= the paths).
+hipError_t launch_radiance(const RenderParams& p, bool lds_scene, const void* rays, long long q0, long long n_queries,
+                           uint32_t n_samples, uint32_t seed_stride, float4* colors, void* out, hipStream_t stream);
+hipError_t launch_wavefront_rays(const RenderParams& p, const WfBuffers& b, bool lds_scene, const void* rays,
+                                 long long q0, long long n_queries, uint32_t n_samples, uint32_t seed_stride, void* out,
+                                 hipStream_t stream);
+// main()'s own rays of p's camera and size as queries (pt_camera_rays): n entries of pixels (null: every pixel
+// in raster order) for sample batch `batch`.
+hipError_t launch_camera_rays(const RenderParams& p, uint32_t batch, const int* pixels, long long n, void* rays,
+                              hipStream_t stream);
 // One pass of the a-trous filter (pt_denoise.h atrous_pixel) from src to dst
 // (distinct images) at tap spacing `step` with the pass's squared sigmas;
 // staged: the tile and its halo go through LDS (steps 1 and 2 only).
@@ -706,6 +720,59 @@ inline RaysLaunch plan_rays(const RenderParams& p, int kind, long long n, bool l
     if (l.lds > kMaxSceneLds) return l;
     l.exact_v = {kind, lds_scene};
     l.grid_exact = lds_scene && blocks > kRaysLdsGrid ? kRaysLdsGrid : blocks;
+  }
+  l.what = Launch::Run;
+  return l;
+}
+
+// ... and of launch_radiance's (radiance queries, kernels/radiance.h): one chunk of n_queries whole queries of
+// n_samples samples each.  wf false: radiance_kernel<LDS, SWEEP, EXIT>, render_adaptive_kernel's variants
+// under the same pick (pick_adaptive: the plain kernels, no stats, counters or packed output), one workgroup
+// per 256 paths.  wf true: wf_gen_rays_kernel, then the ray rounds of pick_wavefront's kernels (counters and
+// moments off) over path buffers of `cap` paths.  Both end with radiance_fold_kernel, one lane per query.
+typedef AdaptiveVariant RadianceVariant;   // radiance_kernel<LDS, SWEEP, EXIT>
+#define PT_RADIANCE_VARIANTS(X) PT_ADAPTIVE_VARIANTS(X)
+constexpr uint32_t kRadianceMaxSamples = 65536;
+constexpr long long kRadianceMaxPaths = 0x7fffffffll - 255;   // paths of one chunk: a path index stays an int
+struct RadianceLaunch {
+  Launch what = Launch::Refused;
+  bool wf = false;
+  long long paths = 0;       // n_queries * n_samples
+  long long grid = 0;        // radiance_kernel's or wf_gen_rays_kernel's workgroups
+  long long fold_grid = 0;   // radiance_fold_kernel's
+  size_t lds = 0;            // dynamic LDS bytes: radiance_kernel's, or the threaded trace kernel's
+  RadianceVariant v = {};    // !wf
+  WfPick k = {};             // wf
+};
+inline RadianceLaunch plan_radiance(const RenderParams& p, bool wf, bool lds_scene, long long n_queries,
+                                    uint32_t n_samples, long long cap, int group4_tris) {
+  RadianceLaunch l;
+  l.wf = wf;
+  if (n_samples < 1u || n_samples > kRadianceMaxSamples || n_queries < 0) return l;
+  if (n_queries > kRadianceMaxPaths / (long long)n_samples) return l;
+  l.paths = n_queries * (long long)n_samples;
+  if (l.paths == 0) {
+    l.what = Launch::Nothing;
+    return l;
+  }
+  l.grid = (l.paths + 255) / 256;
+  l.fold_grid = (n_queries + 255) / 256;
+  const size_t lds = lds_scene ? scene_lds_bytes(p) : 0;
+  if (wf) {
+    if (l.paths > cap || cap > 0x7fffffffll || lds > kMaxSceneLds) return l;
+    const WfPick k = pick_wavefront(lds_scene, p.wide != nullptr, p.wide_qn != 0, false, p.exit_skip != 0, false,
+                                    p.wf_tail > 0, p.n_tris < group4_tris);
+    if (!k.ok) return l;
+    if (k.wide && p.wide_ovf_lanes < 256) return l;   // every lane needs its overflow stack area
+    l.lds = k.wide ? 0 : lds;
+    l.k = k;
+  } else {
+    const int table = !p.sweep ? 0 : p.sweep_cube ? 3 : p.sweep_hull ? 2 : 1;
+    const RadianceVariant v = pick_adaptive(lds_scene, table, p.exit_skip != 0);
+    if (v.sweep && (p.sweep_boxes < 1 || p.sweep_boxes > 64 || p.sweep_leaves < 1 || p.sweep_leaves > 32)) return l;
+    l.lds = v.sweep ? sweep_lds_bytes(p) : lds;
+    if (l.lds > kMaxSceneLds) return l;
+    l.v = v;
   }
   l.what = Launch::Run;
   return l;

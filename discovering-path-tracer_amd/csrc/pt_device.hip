@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "pt_device.h"
+#include "pt_camera_ray.h"
 #include "pt_cull.h"
 #include "pt_denoise.h"
 #include "pt_isect.h"
@@ -55,6 +56,7 @@ namespace {
 #include "kernels/guide.h"
 #include "kernels/adaptive.h"
 #include "kernels/rays.h"
+#include "kernels/radiance.h"
 
 }  // namespace
 
@@ -439,6 +441,70 @@ hipError_t launch_rays(const RenderParams& p, int kind, const void* rays, size_t
   }
   hipLaunchKernelGGL(exact, dim3((unsigned)l.grid_exact), dim3(256), l.lds, stream, p, (const float4*)rays, out,
                      (long long)n, l.wide ? 1 : 0, (const uint32_t*)counters);
+  return hipGetLastError();
+}
+
+namespace {
+// ... and the radiance queries' (last: kernels/radiance.h)
+typedef void (*RadianceKernel)(RenderParams, const float4*, float4*, long long, int, uint32_t, uint32_t);
+#define PT_ROW(L, W, E) {{L, W, E}, radiance_kernel<L, W, E>},
+const KernelEntry<RadianceVariant, RadianceKernel> kRadianceKernels[] = {PT_RADIANCE_VARIANTS(PT_ROW)};
+#undef PT_ROW
+typedef void (*WfGenRaysKernel)(RenderParams, WfBuffers, const float4*, long long, int, uint32_t, uint32_t);
+typedef void (*RadianceFoldKernel)(const float4*, float4*, long long, int, uint32_t);
+typedef void (*CameraRaysKernel)(RenderParams, uint32_t, const int*, long long, float4*);
+const WfGenRaysKernel kWfGenRays = wf_gen_rays_kernel<1>;
+const RadianceFoldKernel kRadianceFold = radiance_fold_kernel<1>;
+const CameraRaysKernel kCameraRays = camera_rays_kernel<1>;
+}  // namespace
+
+hipError_t launch_radiance(const RenderParams& p, bool lds_scene, const void* rays, long long q0, long long n_queries,
+                           uint32_t n_samples, uint32_t seed_stride, float4* colors, void* out, hipStream_t stream) {
+  const RadianceLaunch l = plan_radiance(p, false, lds_scene, n_queries, n_samples, 0, kWfGroup4Tris);
+  if (l.what == Launch::Nothing) return hipSuccess;
+  const RadianceKernel kern = l.what == Launch::Run ? find_kernel(kRadianceKernels, l.v) : nullptr;
+  if (!kern || !rays || !colors || !out || q0 < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(256), l.lds, stream, p, (const float4*)rays, colors, q0,
+                     (int)l.paths, n_samples, seed_stride);
+  hipLaunchKernelGGL(kRadianceFold, dim3((unsigned)l.fold_grid), dim3(256), 0, stream, (const float4*)colors,
+                     (float4*)out, q0, (int)n_queries, n_samples);
+  return hipGetLastError();
+}
+
+// A chunk of queries on the wavefront pipeline: launch_wavefront's rounds on one stream behind the queries'
+// generation, with the queries' fold in place of the pixels'.  No item lists, no fill, no second stream.
+hipError_t launch_wavefront_rays(const RenderParams& p, const WfBuffers& b, bool lds_scene, const void* rays,
+                                 long long q0, long long n_queries, uint32_t n_samples, uint32_t seed_stride, void* out,
+                                 hipStream_t stream) {
+  const RadianceLaunch l = plan_radiance(p, true, lds_scene, n_queries, n_samples, b.cap, kWfGroup4Tris);
+  if (l.what == Launch::Nothing) return hipSuccess;
+  if (l.what != Launch::Run || !rays || !out || q0 < 0) return hipErrorInvalidValue;
+  WfKernels k;
+  hipError_t e = wf_kernels(l.k, l.lds, p, &k);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(b.counters, 0, 3 * sizeof(int), stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kWfGenRays, dim3((unsigned)l.grid), dim3(256), 0, stream, p, b, (const float4*)rays, q0,
+                     (int)l.paths, n_samples, seed_stride);
+  const int iters = wf_max_rays(p);
+  int cur = 0;
+  for (int it = 0; it < iters; ++it) {
+    hipLaunchKernelGGL(k.trace, dim3(k.grid_t), dim3(256), l.lds, stream, p, b, cur);
+    if (l.k.tail) hipLaunchKernelGGL(k.tail, dim3(k.grid_x), dim3(256), 0, stream, p, b, cur);
+    hipLaunchKernelGGL(k.shade, dim3(k.grid_s), dim3(256), 0, stream, p, b, cur);
+    cur ^= 1;
+  }
+  hipLaunchKernelGGL(kRadianceFold, dim3((unsigned)l.fold_grid), dim3(256), 0, stream, (const float4*)b.colors,
+                     (float4*)out, q0, (int)n_queries, n_samples);
+  return hipGetLastError();
+}
+
+hipError_t launch_camera_rays(const RenderParams& p, uint32_t batch, const int* pixels, long long n, void* rays,
+                              hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n < 0 || n > kRaysMax || !rays || p.width <= 0 || p.height <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kCameraRays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, batch, pixels, n,
+                     (float4*)rays);
   return hipGetLastError();
 }
 

@@ -13,14 +13,6 @@
 namespace ptr {
 using namespace ptd;
 
-namespace {
-
-struct Scene {
-  const float* nodes;
-  std::vector<int32_t> left, right;   // the links, decoded once
-  std::vector<float4> tris;           // by triangle index: {v0, e1.x} {e1.yz, e2.xy} {e2.z, n} (pt_device.h)
-};
-
 // traceRay: the explicit stack, left pushed first and right popped first (:198-199), strict '<' (:185).
 // limit null: the closest hit; else the occlusion query, which may stop at the first triangle that settles it.
 bool walk(const Scene& s, v3 o, v3 d, const float* limit, std::vector<int32_t>& stack, float* best, int32_t* bt) {
@@ -53,6 +45,8 @@ bool walk(const Scene& s, v3 o, v3 d, const float* limit, std::vector<int32_t>& 
   return false;
 }
 
+namespace {
+
 void run(const Scene& s, int kind, const float* rays, size_t i0, size_t i1, void* out) {
   std::vector<int32_t> stack;
   stack.reserve(64);
@@ -82,15 +76,15 @@ void run(const Scene& s, int kind, const float* rays, size_t i0, size_t i1, void
 
 }  // namespace
 
-std::string trace_rays_host(const float* V, size_t nvf, const uint32_t* I, size_t ni, const float* nodes, size_t nn,
-                            bool int_bits, int kind, const float* rays, size_t n, void* out, int threads) {
+std::string make_scene(const float* V, size_t nvf, const uint32_t* I, size_t ni, const float* nodes, size_t nn,
+                       bool int_bits, Scene* out) {
+  Scene& s = *out;
   if (nvf % 3 || ni % 3 || ni == 0) return "vertex/index array sizes must be non-zero multiples of 3";
   const size_t nt = ni / 3, nv = nvf / 3;
   if (nn != 2 * nt - 1) return "expected 2T-1 = " + std::to_string(2 * nt - 1) + " nodes, got " + std::to_string(nn);
   if (nt > 0x7fffffffull) return "too many triangles";
   for (size_t i = 0; i < ni; ++i)
     if (I[i] >= nv) return "vertex index out of range at " + std::to_string(i);
-  Scene s;
   s.nodes = nodes;
   {   // a tree of valid links (the walk then ends, and reads inside the arrays)
     std::vector<float> threaded;
@@ -122,6 +116,14 @@ std::string trace_rays_host(const float* V, size_t nvf, const uint32_t* I, size_
     s.tris[3 * t + 1] = make_float4(e1.y, e1.z, e2.x, e2.y);
     s.tris[3 * t + 2] = make_float4(e2.z, nr.x, nr.y, nr.z);
   }
+  return "";
+}
+
+std::string trace_rays_host(const float* V, size_t nvf, const uint32_t* I, size_t ni, const float* nodes, size_t nn,
+                            bool int_bits, int kind, const float* rays, size_t n, void* out, int threads) {
+  Scene s;
+  const std::string bad = make_scene(V, nvf, I, ni, nodes, nn, int_bits, &s);
+  if (!bad.empty()) return bad;
   size_t nth = threads > 0 ? (size_t)threads : std::max(1u, std::thread::hardware_concurrency());
   nth = std::min<size_t>(std::min<size_t>(nth, 256), std::max<size_t>(1, n / 64));
   if (nth <= 1) {

@@ -9,8 +9,12 @@
 //             [-denoise | -denoise-var] [-guide normals.pfm] [-temporal K [-temporal-spatial]]
 //             [-adaptive MIN MAX STEP THRESHOLD [-lum-floor F] [-adaptive-wf]]
 //             [-display clamp|reinhard|aces] [-exposure X] [-auto-exposure KEY] [-pick X Y]
-//             [-upsample S]
+//             [-upsample S] [-radiance IN OUT [-samples S] [-seed-stride K]]
 //
+// -radiance IN OUT reads n pt_ray records (32 B each: o, d, -, seed) from the file IN, path-traces them in the
+// scene under the driver's light, -depth and -sss (pt_trace_radiance_sync; -samples S samples a query from the
+// seeds seed + s * K, default 1 and 1) and writes n float4 {r, g, b, a} to OUT; nothing is rendered after it
+// (-spp is taken as 0).  A single-device context.
 // -pick X Y prints, before anything is rendered, the closest hit of the guide ray of pixel (X, Y)
 // (pt_guide_ray, pt_trace_rays_sync): t, the triangle's index, u, v, the normal and the position o + d * t,
 // floats with nine significant digits (which name their bits), or "miss".  A single-device context.
@@ -100,6 +104,9 @@ int main(int argc, char** argv) {
   bool pick = false;
   int pick_x = 0, pick_y = 0;
   int upsample = 0;   // -upsample: the scale, 0 = off
+  std::string radiance_in, radiance_out;   // -radiance: the queries' file and the answers'
+  pt_radiance_params rad;
+  pt_radiance_default_params(&rad);
   std::vector<int> devices;   // -devices: a multi-device context
   for (int i = 2; i < argc; ++i) {
     auto next = [&](void) { return (i + 1 < argc) ? argv[++i] : (char*)"0"; };
@@ -153,6 +160,13 @@ int main(int argc, char** argv) {
       pick_y = atoi(next());
     }
     else if (!strcmp(argv[i], "-upsample")) upsample = atoi(next());
+    else if (!strcmp(argv[i], "-radiance")) {
+      radiance_in = next();
+      radiance_out = next();
+      spp = 0;
+    }
+    else if (!strcmp(argv[i], "-samples")) rad.n_samples = (uint32_t)atoi(next());
+    else if (!strcmp(argv[i], "-seed-stride")) rad.seed_stride = (uint32_t)strtoul(next(), nullptr, 0);
     else if (!strcmp(argv[i], "-auto-exposure")) {
       display = true;
       dp.auto_exposure = 1;
@@ -219,6 +233,28 @@ int main(int argc, char** argv) {
       printf("pick (%d, %d): t %.9g tri %d u %.9g v %.9g n %.9g %.9g %.9g p %.9g %.9g %.9g\n", pick_x, pick_y,
              hit.t, hit.tri, hit.u, hit.v, hit.n[0], hit.n[1], hit.n[2], pos[0], pos[1], pos[2]);
     }
+  }
+  if (!radiance_in.empty()) {
+    FILE* f = fopen(radiance_in.c_str(), "rb");
+    if (!f) {
+      fprintf(stderr, "-radiance: cannot read %s\n", radiance_in.c_str());
+      return 1;
+    }
+    std::vector<pt_ray> queries;
+    pt_ray q;
+    while (fread(&q, sizeof q, 1, f) == 1) queries.push_back(q);
+    fclose(f);
+    std::vector<float> answers(4 * queries.size());
+    check(pt_trace_radiance_sync(ctx, &rad, queries.data(), queries.size(), answers.data()), "trace radiance");
+    f = fopen(radiance_out.c_str(), "wb");
+    if (!f || fwrite(answers.data(), 16, queries.size(), f) != queries.size() || fclose(f) != 0) {
+      fprintf(stderr, "-radiance: cannot write %s\n", radiance_out.c_str());
+      return 1;
+    }
+    printf("radiance: %zu queries x %u samples -> %s\n", queries.size(), rad.n_samples, radiance_out.c_str());
+    pt_destroy(ctx);
+    pt_scene_free(scene);
+    return 0;
   }
   if (progressive > 0) {
     // orbit: the default camera rotated 30 degrees about +y around the origin

@@ -50,6 +50,7 @@ PT_OPT_SWEEP_CUBE = 30
 PT_OPT_ADAPTIVE_WF = 31
 PT_OPT_RAYS_REFILL = 32
 PT_OPT_CULL_FOOTPRINT = 33
+PT_OPT_RADIANCE_CHUNK = 34
 RAYS_CLOSEST, RAYS_ANY = 0, 1
 # pt_ray and pt_hit as numpy sees them (32 B each)
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("limit", "<f4"), ("reserved", "<u4")])
@@ -89,6 +90,8 @@ EXPORTS = [
     "pt_upsample_default_params", "pt_upsample_host", "pt_upsample_images", "pt_upsample", "pt_upsampled_device_ptr",
     "pt_read_upsampled", "pt_upsample_guide_device_ptr", "pt_upsample_info", "pt_upsample_display",
     "pt_display_upsampled_device_ptr", "pt_read_display_upsampled",
+    "pt_radiance_default_params", "pt_trace_radiance", "pt_trace_radiance_sync", "pt_trace_radiance_host",
+    "pt_camera_rays", "pt_camera_rays_host",
 ]
 
 
@@ -145,6 +148,10 @@ TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 
 class UpsampleParams(ctypes.Structure):
     _fields_ = [("scale", ctypes.c_int), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float)]
+
+
+class RadianceParams(ctypes.Structure):
+    _fields_ = [("n_samples", ctypes.c_uint32), ("seed_stride", ctypes.c_uint32)]
 
 
 class ReprojectImages(ctypes.Structure):
@@ -284,6 +291,13 @@ def lib():
             "pt_upsample_guide_device_ptr": ([vp], vp), "pt_upsample_info": ([vp, ctypes.POINTER(i32)], i32),
             "pt_upsample_display": ([vp, ctypes.POINTER(UpsampleParams), ctypes.POINTER(DisplayParams), vp, vp], i32),
             "pt_display_upsampled_device_ptr": ([vp], vp), "pt_read_display_upsampled": ([vp, vp, sz], i32),
+            "pt_radiance_default_params": ([ctypes.POINTER(RadianceParams)], i32),
+            "pt_trace_radiance": ([vp, ctypes.POINTER(RadianceParams), vp, sz, vp], i32),
+            "pt_trace_radiance_sync": ([vp, ctypes.POINTER(RadianceParams), vp, sz, vp], i32),
+            "pt_trace_radiance_host": ([vp, sz, vp, sz, vp, sz, u32, vp, sz, i32, i32, ctypes.POINTER(RadianceParams),
+                                        vp, sz, vp, i32], i32),
+            "pt_camera_rays": ([vp, u32, vp, sz, vp], i32),
+            "pt_camera_rays_host": ([vp, i32, i32, u32, vp, sz, vp], i32),
         }
         for name, (args, res) in sig.items():
             if not hasattr(L, name):   # older library (A/B timing); calls to it fail loudly
@@ -853,6 +867,53 @@ def trace_rays_host(vertices, indices, nodes, rays, kind=RAYS_CLOSEST, int_bits=
     return out
 
 
+def _radiance_params(samples, seed_stride):
+    return ctypes.byref(RadianceParams(int(samples), int(seed_stride) & 0xFFFFFFFF))
+
+
+def radiance_queries(origins, directions, seeds=0):
+    """RAY_DTYPE records for trace_radiance: n origins, n directions (taken as given) and the paths' seeds."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    q = np.zeros(len(o), RAY_DTYPE)
+    q["o"], q["d"] = o, np.asarray(directions, np.float32).reshape(-1, 3)
+    q["limit"], q["reserved"] = 1e30, np.asarray(seeds, np.uint32)
+    return q
+
+
+def trace_radiance_host(vertices, indices, nodes, lights, rays, samples=1, seed_stride=1, max_depth=4, sss_bounces=3,
+                        int_bits=False, threads=0):
+    """pt_trace_radiance_host: the host statement of Renderer.trace_radiance on the arrays of upload_scene and
+    upload_lights (16 floats a light; None or empty: no light).  rays as trace_rays takes them, the seed in
+    `reserved`.  Returns (n, 4) float32."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1)
+    i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    n = np.ascontiguousarray(nodes, np.float32).reshape(-1)
+    L = np.ascontiguousarray(lights if lights is not None else [], np.float32).reshape(-1)
+    if L.size % 16:
+        raise PTError("lights hold 16 floats each")
+    r = _rays_in(rays)
+    out = np.zeros((r.shape[0], 4), np.float32)
+    _check(lib().pt_trace_radiance_host(_ptr(v), v.size, _ptr(i), i.size, _ptr(n), n.size // 8,
+                                        PT_NODES_INT_BITS if int_bits else 0, _ptr(L), L.size // 16, max_depth,
+                                        sss_bounces, _radiance_params(samples, seed_stride), _ptr(r), r.shape[0],
+                                        _ptr(out), threads), "pt_trace_radiance_host")
+    return out
+
+
+def camera_rays_host(camera_ubo, width, height, batch, pixels=None):
+    """pt_camera_rays_host: main()'s own rays of a camera block, a frame size and a sample batch as RAY_DTYPE
+    records, for the pixels y * width + x listed (None: every pixel in raster order)."""
+    cam = np.ascontiguousarray(camera_ubo, np.float32).reshape(-1)
+    if cam.size != 16:
+        raise PTError("the camera block holds 16 floats")
+    px = None if pixels is None else np.ascontiguousarray(pixels, np.int32).reshape(-1)
+    n = width * height if px is None else px.size
+    rays = np.zeros(n, RAY_DTYPE)
+    _check(lib().pt_camera_rays_host(_ptr(cam), width, height, int(batch) & 0xFFFFFFFF, _ptr(px) if px is not None else None,
+                                     n, _ptr(rays)), "pt_camera_rays_host")
+    return rays
+
+
 class Renderer:
     """One GPU's path tracer: upload, dispatch/render, read back."""
 
@@ -867,6 +928,7 @@ class Renderer:
             d = np.ascontiguousarray(devices, np.int32)
             _check(lib().pt_create_multi(d.ctypes.data, d.size, ctypes.byref(self._c)), "pt_create_multi")
         self.width = self.height = 0
+        self._device = device if devices is None else int(devices[0])
 
     def group_info(self):
         """(device ordinals, members store straight into the frame)."""
@@ -1284,6 +1346,45 @@ class Renderer:
         r = _rays_in(rays)
         out = _rays_out(kind, r.shape[0])
         _check(lib().pt_trace_rays_sync(self._c, kind, _ptr(r), r.shape[0], _ptr(out)), "pt_trace_rays_sync")
+        return out
+
+    def trace_radiance(self, rays, samples=1, seed_stride=1):
+        """The radiance arriving along the caller's own rays: pathTrace from each ray's origin, direction and seed
+        (`reserved`) in the uploaded scene under the uploaded lights and parameters, `samples` samples a query
+        from the seeds seed + s * seed_stride, folded by the shader's running mean.  A numpy array ((n, 8)
+        float32 or RAY_DTYPE records, radiance_queries) goes through pt_trace_radiance_sync and returns (n, 4)
+        float32; a torch tensor on the device ((n, 8) float32, contiguous) goes through pt_trace_radiance,
+        enqueued on the context's stream and not waited for, and returns an (n, 4) tensor on the same device."""
+        params = _radiance_params(samples, seed_stride)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
+                raise PTError("trace_radiance: a contiguous float32 device tensor of n x 8 floats")
+            n = rays.numel() // 8
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            _check(lib().pt_trace_radiance(self._c, params, rays.data_ptr() if n else None, n,
+                                           out.data_ptr() if n else None), "pt_trace_radiance")
+            return out
+        r = _rays_in(rays)
+        out = np.zeros((r.shape[0], 4), np.float32)
+        _check(lib().pt_trace_radiance_sync(self._c, params, _ptr(r), r.shape[0], _ptr(out)), "pt_trace_radiance_sync")
+        return out
+
+    def camera_rays(self, batch, pixels=None):
+        """pt_camera_rays: main()'s own rays of the context's camera and frame size for a sample batch, as an
+        (n, 8) float32 tensor on the device (the seed's bits in column 7), enqueued on the context's stream.
+        pixels: an int32 device tensor of y * width + x, or None for every pixel in raster order."""
+        import torch
+        W, H = self.width, self.height
+        if pixels is None:
+            n, pp = W * H, None
+        else:
+            if not pixels.is_cuda or pixels.dtype != torch.int32 or not pixels.is_contiguous():
+                raise PTError("camera_rays: pixels is a contiguous int32 device tensor")
+            n, pp = pixels.numel(), pixels.data_ptr() if pixels.numel() else None
+        out = torch.empty((n, 8), dtype=torch.float32, device=f"cuda:{self._device}" if pixels is None else pixels.device)
+        _check(lib().pt_camera_rays(self._c, int(batch) & 0xFFFFFFFF, pp, n, out.data_ptr() if n else None),
+               "pt_camera_rays")
         return out
 
     def set_stats_mode(self, on):

@@ -68,7 +68,10 @@ extern "C" {
  * pt_upsample_default_params, pt_upsample_host, pt_upsample_images,
  * pt_upsample, pt_upsampled_device_ptr, pt_read_upsampled,
  * pt_upsample_guide_device_ptr, pt_upsample_info, pt_upsample_display,
- * pt_display_upsampled_device_ptr, pt_read_display_upsampled). */
+ * pt_display_upsampled_device_ptr, pt_read_display_upsampled); radiance
+ * queries (pt_radiance_params, pt_radiance_default_params, pt_trace_radiance,
+ * pt_trace_radiance_sync, pt_trace_radiance_host, pt_camera_rays,
+ * pt_camera_rays_host, PT_OPT_RADIANCE_CHUNK). */
 #define PT_ABI_VERSION 3
 
 enum {
@@ -885,6 +888,86 @@ int pt_trace_rays_host(const float* vertices, size_t n_vertex_floats, const uint
                        const pt_bvh_node* nodes, size_t n_nodes, uint32_t flags, int kind, const pt_ray* rays,
                        size_t n, void* out, int threads);
 
+/* ---- radiance queries: path-trace the caller's own rays ---------------- */
+/* What radiance arrives along a given ray: the shader's pathTrace
+ * (raytrace_comp.comp:300-418) from the caller's origin, direction and seed,
+ * with the lights of pt_upload_lights and max_depth / sss_bounces of
+ * pt_set_params, bit for bit what pt_render computes for a pixel whose ray and
+ * seed these are.  Needs a scene and parameters; zero lights are valid; no
+ * camera and no frame.
+ *
+ * A query is a pt_ray read as {o, d, -, seed}: limit is ignored and reserved
+ * is the path's seed, so rays made for pt_trace_rays are queries with seed 0.
+ * Sample s = 0 .. n_samples-1 of a query is
+ *   c_s = pathTrace(o, d, seed + s * seed_stride)        (uint32 wrap-around)
+ * -- the re-seed rng = seed (:307), the light pre-pass on the given ray
+ * (:311-328), then the bounces -- and the answer is the shader's running mean
+ * (:467-469) of them in order from {+0, +0, +0, +0}:
+ *   acc.rgb = (acc.rgb * float(s) + c_s) / float(s + 1)
+ *   acc.a   = (acc.a   * float(s) + 1)   / float(s + 1)
+ * always applied, so one sample is (0 * 0 + c) / 1 and a -0 radiance comes
+ * out +0.  d is taken as given and never normalised; no ray is refused:
+ * pt_trace_radiance_host defines the answer for NaN, infinite, zero and
+ * subnormal components and the device equals it (NaN where NaN, every other
+ * float the same bits).
+ *
+ * Nothing that belongs to a camera applies: not PT_OPT_SEED_BASE, not the
+ * primary culling.  Queries are not counted by stats mode (pt_get_stats) or
+ * PT_OPT_COUNT_TRACED (pt_get_traced) and leave the accumulation image
+ * untouched.  The kernel family, the LDS staging, the sweep and wide walks and
+ * the exit skip are chosen by pt_render's own rules for a launch of as many
+ * paths (PT_OPT_KERNEL, PT_OPT_SCENE_IN_LDS, PT_OPT_SMALL_SWEEP, PT_OPT_WIDE,
+ * PT_OPT_WIDE_NODE, PT_OPT_WF_GRID, PT_OPT_EXIT_SKIP, ...); the answers are the
+ * same bits under all of them.  Work is cut into chunks of whole queries
+ * (PT_OPT_RADIANCE_CHUNK); the path buffers are the library's, allocated on
+ * demand and freed with the context.
+ *
+ * PT_ERR_INVALID: no scene, a null pointer with n > 0, n_samples outside
+ * 1 .. 65536, a device pointer not 16-B aligned, d_out overlapping d_rays,
+ * n > 2^31 - 256.  PT_ERR_UNSUPPORTED on a pt_create_multi context, and where
+ * PT_OPT_SCENE_IN_LDS 2 asks for a staging the scene does not fit.  n == 0 is
+ * a successful no-op. */
+typedef struct pt_radiance_params {
+  uint32_t n_samples;    /* samples folded into each answer, 1 .. 65536 */
+  uint32_t seed_stride;  /* sample s draws from seed + s * seed_stride */
+} pt_radiance_params;
+/* {1, 1}: one sample; with more, consecutive seeds. */
+int pt_radiance_default_params(pt_radiance_params* out);
+/* d_rays: n pt_ray, d_out: n float4 {r, g, b, a}, both device memory, distinct.
+ * params null: the defaults.  Enqueued on the context's stream; waits for
+ * nothing. */
+int pt_trace_radiance(pt_context* ctx, const pt_radiance_params* params, const void* d_rays, size_t n, void* d_out);
+/* The same from and to host memory (out: 4 n floats), staged in chunks through
+ * library-owned buffers; returns when the answers are in `out`. */
+int pt_trace_radiance_sync(pt_context* ctx, const pt_radiance_params* params, const pt_ray* rays, size_t n,
+                           float* out);
+/* The host statement, without a context or a GPU: pathTrace in pt_math.h's
+ * IEEE forms over the vertex, index and node arrays of pt_upload_scene (flags:
+ * PT_NODES_INT_BITS), every ray the reference's depth-first walk, the lights'
+ * frames as pt_upload_lights derives them; `threads` host threads over the
+ * queries (<= 0: one per core), the same bytes whatever their number.
+ * PT_ERR_SCENE for arrays pt_upload_scene would refuse; PT_ERR_INVALID for
+ * negative max_depth or sss_bounces. */
+int pt_trace_radiance_host(const float* vertices, size_t n_vertex_floats, const uint32_t* indices, size_t n_indices,
+                           const pt_bvh_node* nodes, size_t n_nodes, uint32_t flags, const pt_area_light* lights,
+                           size_t n_lights, int max_depth, int sss_bounces, const pt_radiance_params* params,
+                           const pt_ray* rays, size_t n, float* out, int threads);
+/* main()'s own ray (:430-460) of a pixel and a sample batch, as a query: the
+ * aperture draw, the jitter draw and the focal point of the context's camera
+ * and frame size, from the seed (batch * H + y) * W + x, which is also written
+ * to reserved; limit is written 1e30f.  pt_trace_radiance of these rays is the
+ * colour pt_render folds for that pixel and batch; a caller building another
+ * camera model starts from them.  d_pixels: n int32 y * W + x in device memory,
+ * each inside the frame, or null = every pixel in raster order (then
+ * n <= W * H); d_rays: n pt_ray, device memory, 16-B aligned.  Needs a camera
+ * and a frame size (pt_resize_and_clear / pt_bind_accum), no scene.  Enqueued
+ * on the context's stream. */
+int pt_camera_rays(pt_context* ctx, uint32_t batch, const int32_t* d_pixels, size_t n, void* d_rays);
+/* The host statement: camera_ubo as pt_set_camera takes it, pixels in host
+ * memory (checked: PT_ERR_INVALID for one outside the frame). */
+int pt_camera_rays_host(const float camera_ubo[16], int width, int height, uint32_t batch, const int32_t* pixels,
+                        size_t n, pt_ray* rays);
+
 /* ---- multi-GPU screen-space partition ------------------ */
 /* Pixels are grouped into 16x16 blocks.  Block (bx, by) is tile
  * b = by*blocks_x + (bx - by) mod blocks_x (rows rotated by their index, so
@@ -1261,6 +1344,13 @@ int pt_dist_finalize(pt_context* ctx);
  * is; stats mode never skips.  pt_cull_info reports what is in force.  Output
  * is identical. */
 #define PT_OPT_CULL_FOOTPRINT 33
+/* PT_OPT_RADIANCE_CHUNK: the paths (queries x samples) pt_trace_radiance runs
+ * in one chunk; a chunk holds whole queries, at least one.  0 (default) = auto,
+ * 2^22 paths: 64 MiB of colours on the path-recursive kernel, 1.7 GB of path
+ * state (416 B a path) on the wavefront pipeline, and one chunk for the rays of
+ * a 1080p frame.  Output is identical; small values exist so that tests reach
+ * chunk seams with few queries. */
+#define PT_OPT_RADIANCE_CHUNK 34
 int pt_set_option(pt_context* ctx, int key, int value);
 /* The kernel the last pt_render / pt_dispatch ran (PT_OPT_KERNEL values 1-3,
  * after auto selection); 0 before the first render. */
